@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the batched Sus-Net environment hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4] [--mode fused|step]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4] [--mode fused|step] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: set-up, `--settle-ms` of untimed launches on an env of its own, W warm-up steps
+and K timed steps on a fresh env from the fixed seed, then the line.  `--full` adds everything else the script measures (below: the
+repeats and the event-pair cross-check of the timed region, the network kernel alone, the other policy forms, `secondary`, `obs_modes`,
+`other_configs`, `cpu_baseline`).  `--dump-outputs DIR` writes what the timed path computed in its last step as float32
+`DIR/<name>.npy` (fused: the trajectory fields of the last launch; step: that tick's actions, rewards, done, truncated and observation;
+policy: the observation after the last tick), for a fixed seeded sample of the envs where the whole batch would pass 48 MiB: the same
+arguments give the same inputs, so two builds can be compared output for output.
 
 One pass of the hot path = every env samples uniform role-valid actions, steps, and auto-resets on done|truncated:
 the random-action rollout BASELINE.json names (`ReplayBuffer.populate`'s loop, reference
@@ -18,7 +26,7 @@ The JSON line: `value` = env-steps/s of the named configuration (default cfg2 = 
 `achieved` / `frac` are computed from the bytes a launch actually has to move -- the trajectory records it stores (the state
 of a fused rollout never leaves the chip; the committed PMC pass measures the same bytes: `traffic`); the figure SURVEY.md
 section 8(d) defines for the one-step API (12A + 4J + 6 bytes per env-step, state read + written every step) is reported next
-to it as `survey_8d_*`.  `other_configs` holds the same measurement (5 warm-up + 20 timed launches) for the other BASELINE
+to it as `survey_8d_*`.  `other_configs` (--full) holds the same measurement (5 warm-up + 20 timed launches) for the other BASELINE
 configurations: cfg3, cfg4 (the 8-GPU shard: 32 768 envs), tag5 and cfg5 (policy in the loop: eager and as a replayed
 hipGraph).
 
@@ -154,7 +162,7 @@ def roofline_block(config, spec, B, ticks, obs, packed, raw_size, record_bytes, 
                 "API's state read + write, which a fused rollout does not perform: r01 / r02 lines reported this figure as frac); "
                 "avg_launch_us = HIP-event time of the timed region (events on the launch stream around the K timed launches) / K; "
                 "avg_launch_us_event_pairs = mean of 8 further launches bracketed one by one (cross-check, outside the timed "
-                "region); traffic = PMC bytes of the committed rocprofv3 pass of this command and layout (profiles/), null when "
+                "region; --full, else null); traffic = PMC bytes of the committed rocprofv3 pass of this command and layout (profiles/), null when "
                 "none matches",
     }
 
@@ -166,6 +174,36 @@ def make_env(pkg, spec, batch, seed, env_id_base, device, obs_cfg=None):
     walls = kw.pop("include_walls", True)
     return cls(**kw, grid=pkg.four_room_grid(spec["n"], walls), batch=batch, device=device, rng="philox", seed=seed,
                env_id_base=env_id_base, auto_reset=True, export_state=False, check_errors=False, obs=obs_cfg)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: float32 bytes in all (the files stay under 64 MB)
+
+
+def sample_outputs(arrays, env_dim, batch, budget=DUMP_BUDGET_BYTES):
+    """float32 host copies of the timed path's outputs, every array cut along its env dimension to the same sorted, seeded choice of
+    envs: as many as fit `budget` (all of them where the batch fits).  A trajectory that passes the budget for one env keeps its last ticks."""
+    import numpy as np
+    import torch
+
+    per_env = sum(t.numel() // batch for t in arrays.values()) * 4
+    n = max(1, min(batch, budget // max(1, per_env)))
+    idx = np.sort(np.random.default_rng(0).choice(batch, n, replace=False))
+    keep = None
+    if env_dim == 1 and per_env > budget:
+        keep = max(1, next(iter(arrays.values())).shape[0] * budget // per_env)
+    out = {}
+    for name, t in arrays.items():
+        t = t.index_select(env_dim, torch.as_tensor(idx, device=t.device))
+        out[name] = (t[-keep:] if keep else t).to(torch.float32).cpu().numpy()
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(spec, target_seconds=12.0):
@@ -305,22 +343,27 @@ def main():
                     "the same fields, one or a few wide stores per lane instead of one narrow store per tensor), 0 = separate "
                     "trajectory tensors, 2 = the COMPACT record where the configuration has one (cfg2: 16 bytes, actions and flags in one "
                     "byte), -1 (default) = compact, else packed, where the configuration has it")
-    ap.add_argument("--settle-ms", type=float, default=150.0, help="before the W warm-up steps: untimed launches of the same bench step until the device "
-                    "has been busy this long.  An MI355X that has been idle takes tens of milliseconds of sustained load to reach its steady clocks: 5 "
+    ap.add_argument("--settle-ms", type=float, default=150.0, help="before the W warm-up steps: untimed launches of the same bench step, on an env of their "
+                    "own, until the device has been busy this long.  An MI355X that has been idle takes tens of milliseconds of sustained load to reach its steady clocks: 5 "
                     "warm-up launches of 0.1-0.3 ms each leave the timed region on the ramp (cfg3: 107 G with 5 warm-up launches, 118.5 G with 50 "
                     "or 400 -- same box, same binary).  Reported in the line as `settle_ms`; 0 = none")
     ap.add_argument("--policy-block", type=int, default=5, help="cfg5: ticks per launch of the policy loop (susnet_qnet_policy_rollout: the network image and the "
                     "launch are paid once per block, the weights are fixed within it).  Default 5 = the reference trainer's train_step_interval (train.py:295, "
                     "402-416: the networks change every 5 env steps), i.e. its acting loop between two optimizer steps; 64 = run_game's loop with fixed networks "
                     "(visualize.py:547-582; reported next to the headline as `policy_forms`); 0 = one launch per tick (susnet_qnet_policy_step)")
-    ap.add_argument("--repeats", type=int, default=5, help="the K-launch timed region is run this many more times back to back (after the "
+    ap.add_argument("--repeats", type=int, default=5, help="--full: the K-launch timed region is run this many more times back to back (after the "
                     "headline measurement, which stays as it is): median / min / max of the repeats are reported in `repeats`")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else the script measures: the repeats and the event-pair "
+                    "cross-check of the timed region, the network kernel alone and the other policy forms (cfg5), the other mode, the observation "
+                    "sweep, other_configs and the CPU baseline (--no-secondary / --no-cpu-baseline / --repeats 0 leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy "
+                    "(float32; a fixed seeded sample of the envs where the batch would pass 48 MiB)")
     ap.add_argument("--dry-run", action="store_true", help="rehearse the N-rank launch on a box without N GPUs: the ranks start, rendezvous and run every "
                     "collective of the real run (world check, barrier, max over ranks, the metrics all-gather) on host tensors, make NO device call, and rank 0 "
                     "prints the line with its config block as the real run builds it and `value` null, `dry_run` true (tests/test_dist_gloo.py: BASELINE "
                     "config 4 = --gpus 8 --config cfg4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the step-API leg, the observation sweep and other_configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the step-API leg, the observation sweep and other_configs")
     args = ap.parse_args()
     assert args.gpus >= 1 and args.steps >= 1 and args.warmup >= 0 and args.ticks >= 1
 
@@ -378,56 +421,70 @@ def main():
                 env.rollout_into(T, bufs)
         return n_launches
 
-    def run_step(env, n_ticks):
+    def run_step(env, n_ticks, last):
         for _ in range(n_ticks):
             a = env.sample_actions()
-            env.step(a)
+            last["step"] = (a, env.step(a))
         return 2 * n_ticks
 
-    def measure(spec, B, mode, obs_mode, K, W, ticks, want_packed=-1, graph_ticks=0, policy_fused=True, n_repeats=0, block_ticks=0, crew_network=False):
+    def measure(spec, B, mode, obs_mode, K, W, ticks, want_packed=-1, graph_ticks=0, policy_fused=True, n_repeats=0, block_ticks=0, crew_network=False,
+                dump=False):
         """W untimed + K timed bench steps of one configuration.  fused: a step is one launch of `ticks` ticks; step / policy:
-        one tick (policy with graph_ticks > 0: the tick loop replayed as hipGraphs of graph_ticks ticks, K rounded up to whole graphs)."""
+        one tick (policy with graph_ticks > 0: the tick loop replayed as hipGraphs of graph_ticks ticks, K rounded up to whole graphs).
+        dump: also return `outputs`, sample_outputs() of what the last timed step computed."""
         oc = obs_config(obs_mode) if mode == "fused" else None
         step_obs = obs_config(obs_mode) if mode == "step" else None
         if mode == "policy":
             step_obs = pkg.ObsConfig("flat", POLICY_COMPONENTS)
-        env = make_env(pkg, spec, B, seed, rank * B, device, obs_cfg=step_obs)
-        env.reset()
-        lay = env.record_layout()
-        packed = (mode == "fused" and obs_mode == "raw" and want_packed != 0 and lay is not None)
-        if want_packed in (1, 2) and mode == "fused" and obs_mode == "raw":
-            assert packed, "this configuration has no packed record mode"
-        compact = packed and want_packed in (-1, 2) and env.record_layout("compact") is not None
-        if want_packed == 2:
-            assert compact, "this configuration has no compact record"
-        if compact:
-            lay = env.record_layout("compact")
-        bufs = env.alloc_rollout(ticks, obs=oc, packed=("compact" if compact else packed)) if mode == "fused" else None
-        if mode == "policy":
-            model = pkg.policy.reference_imposter_mlp(env, POLICY_COMPONENTS, seed=0)
-            crew_model = pkg.policy.reference_crew_mlp(env, POLICY_COMPONENTS, seed=1) if crew_network else None  # (run_game: both teams by their networks)
-            pr = pkg.PolicyRollout(env, model, crew_model=crew_model, components=POLICY_COMPONENTS, fused=policy_fused)
-            assert (pr.fused_imposter is not None) == policy_fused, "the reference MLP on this layout is served by susnet_qnet_forward"
-            if graph_ticks > 0:
-                graph, _ = pr.capture(graph_ticks)
-                K = (K + graph_ticks - 1) // graph_ticks * graph_ticks
-                W = (W + graph_ticks - 1) // graph_ticks * graph_ticks
+        if mode == "policy" and graph_ticks > 0:
+            K = (K + graph_ticks - 1) // graph_ticks * graph_ticks
+            W = (W + graph_ticks - 1) // graph_ticks * graph_ticks
 
-                def runner(n):
-                    for _ in range(n // graph_ticks):
-                        graph.replay()
-                    return n // graph_ticks
+        def setup():
+            """A fresh env from the seed, its output buffers and the runner of n bench steps on it."""
+            env = make_env(pkg, spec, B, seed, rank * B, device, obs_cfg=step_obs)
+            env.reset()
+            lay = env.record_layout()
+            packed = (mode == "fused" and obs_mode == "raw" and want_packed != 0 and lay is not None)
+            if want_packed in (1, 2) and mode == "fused" and obs_mode == "raw":
+                assert packed, "this configuration has no packed record mode"
+            compact = packed and want_packed in (-1, 2) and env.record_layout("compact") is not None
+            if want_packed == 2:
+                assert compact, "this configuration has no compact record"
+            if compact:
+                lay = env.record_layout("compact")
+            bufs = env.alloc_rollout(ticks, obs=oc, packed=("compact" if compact else packed)) if mode == "fused" else None
+            pr, last = None, {}
+            if mode == "policy":
+                model = pkg.policy.reference_imposter_mlp(env, POLICY_COMPONENTS, seed=0)
+                crew_model = pkg.policy.reference_crew_mlp(env, POLICY_COMPONENTS, seed=1) if crew_network else None  # (run_game: both teams by their networks)
+                pr = pkg.PolicyRollout(env, model, crew_model=crew_model, components=POLICY_COMPONENTS, fused=policy_fused)
+                assert (pr.fused_imposter is not None) == policy_fused, "the reference MLP on this layout is served by susnet_qnet_forward"
+                if graph_ticks > 0:
+                    graph, _ = pr.capture(graph_ticks)
+
+                    def runner(n):
+                        for _ in range(n // graph_ticks):
+                            graph.replay()
+                        return n // graph_ticks
+                else:
+                    def runner(n):  # (block_ticks > 0: that many ticks per launch where the env serves the whole tick as one kernel)
+                        pr.run(n, block_ticks=block_ticks)
+                        return n if block_ticks <= 0 else (n + block_ticks - 1) // block_ticks
             else:
-                def runner(n):  # (block_ticks > 0: that many ticks per launch where the env serves the whole tick as one kernel)
-                    pr.run(n, block_ticks=block_ticks)
-                    return n if block_ticks <= 0 else (n + block_ticks - 1) // block_ticks
-        else:
-            runner = (lambda n: run_fused(env, n, ticks, bufs)) if mode == "fused" else (lambda n: run_step(env, n))
-        if args.settle_ms > 0:  # steady clocks first (see --settle-ms): untimed, not part of the W warm-up steps
+                runner = (lambda n: run_fused(env, n, ticks, bufs)) if mode == "fused" else (lambda n: run_step(env, n, last))
+            return env, lay, packed, compact, bufs, pr, last, runner
+
+        env, lay, packed, compact, bufs, pr, last, runner = setup()
+        settle = None
+        if args.settle_ms > 0:  # steady clocks first (see --settle-ms): untimed, not part of the W warm-up steps, on an env of their own --
+            # the measured env starts from the seed, so what its steps compute does not depend on how many launches fit in the settle time;
+            # both are set up before, so the device does not idle between the settle launches and the warm-up
+            settle = setup()
             unit = graph_ticks if (mode == "policy" and graph_ticks > 0) else 1
             t_s = time.perf_counter()
             while (time.perf_counter() - t_s) * 1e3 < args.settle_ms:
-                runner(4 * unit)
+                settle[-1](4 * unit)
                 torch.cuda.synchronize(device)
         runner(W)
         sync_all()
@@ -440,6 +497,21 @@ def main():
         sync_all()
         dt = time.perf_counter() - t0
         dev_ms = ev0.elapsed_time(ev1)  # HIP events around the timed region, on the launch stream
+        del settle
+        outputs = None
+        if dump:  # before anything else runs on the env: what a caller of the timed path received from its last step
+            if mode == "fused":
+                fields = (env.record_fields(bufs["record"], "compact" if compact else packed) if "record" in bufs else
+                          {k: v for k, v in bufs.items() if k in ("actions", "rewards", "done", "truncated", "obs", "obs_non_spatial")})
+                outputs = sample_outputs(fields, 1, B)
+            else:
+                fields = {"obs": env.obs} if env.obs is not None else {}
+                if env.obs_non_spatial is not None:
+                    fields["obs_non_spatial"] = env.obs_non_spatial
+                if mode == "step":
+                    a, (_, rew, done, trunc, _) = last["step"]
+                    fields.update(actions=a, rewards=rew, done=done, truncated=trunc)
+                outputs = sample_outputs(fields, 0, B)
         # the same K-launch region `repeats` more times, back to back (outside the headline's timed region): how much one such
         # measurement moves on this box
         rep = None
@@ -455,7 +527,7 @@ def main():
             vals.sort()
             rep = {"n": n_repeats, "launches_each": K, "median_launch_us": vals[len(vals) // 2], "min_launch_us": vals[0], "max_launch_us": vals[-1]}
         pair_us = None
-        if mode == "fused":  # cross-check OUTSIDE the timed region: 8 launches, each bracketed by its own event pair
+        if mode == "fused" and args.full:  # cross-check OUTSIDE the timed region: 8 launches, each bracketed by its own event pair
             pairs = []
             run_fused(env, 8, ticks, bufs, pairs)
             torch.cuda.synchronize(device)
@@ -472,45 +544,47 @@ def main():
         env.poll_errors()
         metrics = pkg.dist.node_metrics(env)  # the ONE collective: all-gather of the episode totals
         qnet = None
-        if mode == "policy" and policy_fused:  # the network kernel by itself, outside the timed region: 50 launches between two events
+        if mode == "policy" and policy_fused:
             net = pr.fused_imposter
-            for _ in range(5):
-                env.qnet_forward(net)
-            q0, q1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            q0.record(stream)
-            for _ in range(50):
-                env.qnet_forward(net)
-            q1.record(stream)
-            torch.cuda.synchronize(device)
-            us = q0.elapsed_time(q1) * 1e3 / 50
             pad = [net.dims[0], 256, 128, 64, 32, 32]
             issued = 2.0 * B * sum(a * b for a, b in zip(pad[1:-1], pad[2:]))       # layers 2..5 at their padded widths: what the matrix core executes
             model_flops = 2.0 * B * sum(a * b for a, b in zip(net.dims[:-1], net.dims[1:]))  # the reference MLP's own multiply-adds, layer 1 included
-            traffic, traffic_source = None, None
-            import glob
+            traffic, traffic_source, us, alone = None, None, None, None
+            if args.full:  # the network kernel by itself, outside the timed region: 50 launches between two events
+                for _ in range(5):
+                    env.qnet_forward(net)
+                q0, q1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                q0.record(stream)
+                for _ in range(50):
+                    env.qnet_forward(net)
+                q1.record(stream)
+                torch.cuda.synchronize(device)
+                us = q0.elapsed_time(q1) * 1e3 / 50
+                import glob
 
-            cpaths = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r*_qnet_counters.json")))
-            if B == 65536 and cpaths:  # WRITE_SIZE + 2 x FETCH_SIZE of the same kernel on the same batch (tools/profile_cfg5.sh): the newest round's
-                traffic, traffic_source = json.load(open(cpaths[-1])).get("traffic_bytes_per_launch"), "profiles/" + os.path.basename(cpaths[-1])
-            alone = {"kernel": "k_qnet<FlatRow<2,3,14>> (susnet_qnet_forward), 50 launches outside the timed region", "avg_launch_us": us,
-                     "achieved": issued / us / 1e6, "frac": issued / us / 1e6 / MFMA_F32_PEAK_TFLOPS, "model_tflops": model_flops / us / 1e6,
-                     "traffic": traffic, "traffic_source": traffic_source}
+                cpaths = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r*_qnet_counters.json")))
+                if B == 65536 and cpaths:  # WRITE_SIZE + 2 x FETCH_SIZE of the same kernel on the same batch (tools/profile_cfg5.sh): the newest round's
+                    traffic, traffic_source = json.load(open(cpaths[-1])).get("traffic_bytes_per_launch"), "profiles/" + os.path.basename(cpaths[-1])
+                alone = {"kernel": "k_qnet<FlatRow<2,3,14>> (susnet_qnet_forward), 50 launches outside the timed region", "avg_launch_us": us,
+                         "achieved": issued / us / 1e6, "frac": issued / us / 1e6 / MFMA_F32_PEAK_TFLOPS, "model_tflops": model_flops / us / 1e6,
+                         "traffic": traffic, "traffic_source": traffic_source}
             one = bool(getattr(pr, "one_kernel_tick", False))
             # the kernel of the TIMED region: with the one-kernel tick every launch there is k_qnet_step (network + argmax + crew draws + step:
-            # the matrix core idles while the wave steps its environments); else the network kernel as timed alone
+            # the matrix core idles while the wave steps its environments); else the network kernel as timed alone (--full; else null)
             tick_us = dev_ms * 1e3 / K if one else us
+            per_s = (lambda flops: flops / tick_us / 1e6) if tick_us else (lambda flops: None)
             qnet = {"kernel": (("k_qnet_step<FlatRow<2,3,14>, Spec<3,4,..>> (susnet_qnet_policy_step: the whole tick, one launch per bench step)" if block_ticks <= 0 else
                                 f"k_qnet_step<FlatRow<2,3,14>, Spec<3,4,..>> (susnet_qnet_policy_rollout: the whole tick, {block_ticks} ticks = bench steps per launch; "
                                 "avg_launch_us is per TICK)") if one
                                else "k_qnet<FlatRow<2,3,14>> (susnet_qnet_forward)"),
                     "bound": "mfma", "avg_launch_us": tick_us, "unit": "TFLOP/s", "traffic": None if one else traffic,
-                    "peak": MFMA_F32_PEAK_TFLOPS, "achieved": issued / tick_us / 1e6, "frac": issued / tick_us / 1e6 / MFMA_F32_PEAK_TFLOPS,
-                    "model_flops_per_launch": model_flops, "model_tflops": model_flops / tick_us / 1e6, "network_kernel_alone": alone,
+                    "peak": MFMA_F32_PEAK_TFLOPS, "achieved": per_s(issued), "frac": per_s(issued / MFMA_F32_PEAK_TFLOPS),
+                    "model_flops_per_launch": model_flops, "model_tflops": per_s(model_flops), "network_kernel_alone": alone,
                     "note": "achieved = flops of the v_mfma_f32_32x32x2_f32 instructions issued (layers 2..5, padded widths) / launch time; layer 1 "
                             "(35 % of the model's multiply-adds) is a gather of W1 columns and issues no MFMA, so model_tflops exceeds it"}
         return dict(seconds=dt, launches=launches, device_ms=dev_ms, metrics=metrics, pair_us=pair_us, packed=packed, steps=K, warmup=W,
                     raw_size=env.flattened_state_size, record_bytes=lay.record_bytes if lay is not None else None,
-                    launch_us_ranks=launch_us_ranks, qnet=qnet, repeats=rep,
+                    launch_us_ranks=launch_us_ranks, qnet=qnet, repeats=rep, outputs=outputs,
                     layout=("compact record per env-step (16 bytes: rewards f32[2] | raw obs u8[6] | actions and flags in one byte | 0)" if mode == "fused" and compact
                             else ("packed record per env-step" + (", stored as planes of 16-byte pieces" if lay is not None and lay.planar else "")) if packed
                             else "separate tensors"))
@@ -522,8 +596,10 @@ def main():
     if spec.get("policy"):
         args.mode, args.obs = "policy", "flat"
     ticks_per_step = args.ticks if args.mode == "fused" else 1
-    res = measure(spec, B, args.mode, args.obs, K, W, args.ticks, args.packed, n_repeats=args.repeats if world == 1 else 0,
-                  block_ticks=args.policy_block if args.mode == "policy" else 0)
+    res = measure(spec, B, args.mode, args.obs, K, W, args.ticks, args.packed, n_repeats=args.repeats if world == 1 and args.full else 0,
+                  block_ticks=args.policy_block if args.mode == "policy" else 0, dump=bool(args.dump_outputs) and rank == 0)
+    if res["outputs"] is not None:
+        write_outputs(args.dump_outputs, res["outputs"])
     steps_per_launch = B * ticks_per_step          # env-steps one launch of the dominant kernel processes (this rank)
     total_steps = steps_per_launch * world * K
     value = total_steps / res["seconds"]
@@ -558,18 +634,19 @@ def main():
         line["config"]["ticks_per_launch"] = max(1, args.policy_block)
         line["headline_definition"] = (f"cfg5 value = batch x ticks / wall time of the policy loop at {max(1, args.policy_block)} tick(s) per launch with fixed weights "
                                        "(default 5 = the reference trainer's train_step_interval: rounds 1-3 timed one launch per tick, round 4 blocks of 64 ticks -- "
-                                       "both are in `policy_forms`)")
-        forms = {}
-        for label, blk in (("one_launch_per_tick", 0), ("blocks_of_5_ticks", 5), ("blocks_of_64_ticks", 64)):
-            if blk == args.policy_block:
-                forms[label] = {"value": value, "us_per_tick": res["seconds"] * 1e6 / K, "ticks_per_launch": max(1, blk), "headline": True}
-                continue
-            rp = measure(spec, B, "policy", "flat", 320 if blk else 64, 64 if blk else 16, 1, block_ticks=blk)
-            forms[label] = {"value": B * rp["steps"] / rp["seconds"], "us_per_tick": rp["seconds"] * 1e6 / rp["steps"], "ticks_per_launch": max(1, blk)}
-            del rp
-        line["policy_forms"] = forms
+                                       "both are in `policy_forms`, with --full)")
+        if args.full:
+            forms = {}
+            for label, blk in (("one_launch_per_tick", 0), ("blocks_of_5_ticks", 5), ("blocks_of_64_ticks", 64)):
+                if blk == args.policy_block:
+                    forms[label] = {"value": value, "us_per_tick": res["seconds"] * 1e6 / K, "ticks_per_launch": max(1, blk), "headline": True}
+                    continue
+                rp = measure(spec, B, "policy", "flat", 320 if blk else 64, 64 if blk else 16, 1, block_ticks=blk)
+                forms[label] = {"value": B * rp["steps"] / rp["seconds"], "us_per_tick": rp["seconds"] * 1e6 / rp["steps"], "ticks_per_launch": max(1, blk)}
+                del rp
+            line["policy_forms"] = forms
     del res
-    secondary = rank == 0 and world == 1 and not args.no_secondary and args.mode != "policy"
+    secondary = rank == 0 and world == 1 and args.full and not args.no_secondary and args.mode != "policy"
     if secondary:
         other = "step" if args.mode == "fused" else "fused"
         k2 = 512 if other == "step" else 8
@@ -705,7 +782,7 @@ def main():
                           for e in line["other_configs"]}
     if world > 1:
         dist.barrier()  # the timed region and its collectives are over on every rank before rank 0 spends host time below
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(spec)
     elif rank == 0:
         line["cpu_baseline"] = None

@@ -109,6 +109,33 @@ def test_bench_self_launch_builds_the_drivers_command():
         bench.check_world(2, 4)
 
 
+def test_bench_output_sample_is_seeded_and_within_the_budget():
+    """`--dump-outputs`: float32 copies of every array, the whole batch where it fits, else the same seeded choice of envs for every
+    array and every run; a trajectory too long for the budget at one env keeps its last ticks."""
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    T, B = 7, 1000
+    arrays = {"rewards": torch.arange(T * B * 2, dtype=torch.float32).reshape(T, B, 2), "done": torch.ones(T, B, dtype=torch.bool)}
+    whole = bench.sample_outputs(arrays, 1, B)
+    assert whole["rewards"].dtype == np.float32 and whole["done"].dtype == np.float32
+    np.testing.assert_array_equal(whole["rewards"], arrays["rewards"].numpy())
+    np.testing.assert_array_equal(whole["done"], np.ones((T, B), np.float32))
+    per_env = T * 3 * 4
+    some = bench.sample_outputs(arrays, 1, B, budget=100 * per_env)
+    assert some["rewards"].shape == (T, 100, 2) and some["done"].shape == (T, 100)
+    envs = some["rewards"][0, :, 0] / 2
+    assert np.all(np.diff(envs) > 0) and envs[-1] < B
+    np.testing.assert_array_equal(some["rewards"], bench.sample_outputs(arrays, 1, B, budget=100 * per_env)["rewards"])
+    tail = bench.sample_outputs(arrays, 1, B, budget=per_env * 2 // T)
+    assert tail["rewards"].shape == (2, 1, 2)
+    e = int(tail["rewards"][0, 0, 0]) // 2 - (T - 2) * B  # (the value at [t, e, 0] is 2 (t B + e))
+    np.testing.assert_array_equal(tail["rewards"], arrays["rewards"][T - 2:, e:e + 1].numpy())
+    rows = bench.sample_outputs({"obs": torch.zeros(B, 5, dtype=torch.uint8)}, 0, B, budget=10 * 5 * 4)
+    assert rows["obs"].shape == (10, 5)
+
+
 def test_bench_refuses_a_world_that_differs_from_gpus_under_gloo(tmp_path):
     """Two real ranks (torch.distributed.run, gloo rendezvous on 127.0.0.1) started with --gpus 3: every rank stops at the
     world check -- non-zero exit, the refusal on stderr, no JSON line on stdout."""

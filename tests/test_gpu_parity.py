@@ -524,7 +524,8 @@ def test_two_rank_bench_line_equals_one_process_over_the_same_env_ids(pkg):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     Bshard, K, W, T = 4096, 3, 1, 64
-    flags = ["--steps", str(K), "--warmup", str(W), "--ticks", str(T), "--config", "cfg3", "--no-cpu-baseline", "--no-secondary", "--repeats", "0", "--settle-ms", "0"]
+    flags = ["--steps", str(K), "--warmup", str(W), "--ticks", str(T), "--config", "cfg3", "--full", "--no-cpu-baseline", "--no-secondary", "--repeats", "0",
+             "--settle-ms", "0"]
     env = dict(os.environ, SUSNET_BENCH_BACKEND="gloo", SUSNET_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(bench.launch_command(2, port, ["--gpus", "2", "--batch", str(Bshard)] + flags), env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -541,6 +542,42 @@ def test_two_rank_bench_line_equals_one_process_over_the_same_env_ids(pkg):
     one = json.loads([ln for ln in q.stdout.splitlines() if ln.startswith('{"metric"')][0])
     assert one["episode_metrics"] == two["episode_metrics"], (one["episode_metrics"], two["episode_metrics"])
     assert one["episode_metrics"]["episodes"] > 0
+
+
+@pytest.mark.parametrize("config", ["cfg2", "cfg3"])
+def test_bench_dump_is_the_last_timed_launch_from_the_seed(pkg, tmp_path, config):
+    """`bench.py --dump-outputs DIR` (a plain run: settle, W warm-up, K timed launches) writes the trajectory of the K-th timed launch of
+    an env that started from the bench's seed -- the settle launches run on an env of their own, so the files do not depend on how many
+    of them fit in --settle-ms.  cfg2: the compact record; cfg3: packed records stored as planes."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, K, W, T = 4096, 3, 2, 32
+    out = tmp_path / "dump"
+    q = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", config, "--batch", str(B), "--steps", str(K),
+                        "--warmup", str(W), "--ticks", str(T), "--settle-ms", "30", "--dump-outputs", str(out)],
+                       env=dict(os.environ), capture_output=True, text=True, timeout=600)
+    assert q.returncode == 0, q.stderr[-2000:]
+    line = json.loads([ln for ln in q.stdout.splitlines() if ln.startswith('{"metric"')][0])
+    assert line["steps"] == K and line["ms_per_step"] > 0 and line["cpu_baseline"] is None and "other_configs" not in line
+    env = bench.make_env(pkg, bench.CONFIGS[config], B, 1234, 0, torch.device("cuda:0"))
+    env.reset()
+    fmt = "compact" if env.record_layout("compact") is not None else True
+    bufs = env.alloc_rollout(T, obs=pkg.ObsConfig("raw", dtype=torch.uint8), packed=fmt)
+    for _ in range(W + K):
+        env.rollout_into(T, bufs)
+    want = bench.sample_outputs(env.record_fields(bufs["record"], fmt), 1, B)
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sorted(got) == sorted(want) == ["actions", "done", "obs", "rewards", "truncated"]
+    for k in want:
+        assert got[k].dtype == np.float32 and got[k].shape[:2] == (T, B)
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
 
 
 def test_node_metrics_over_rccl(pkg):

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/prof_${PROF_TAG:-cur}/cfg5
 rm -rf "$OUT" && mkdir -p "$OUT"
-CMD="bench.py --config cfg5 --steps 256 --warmup 32 --no-cpu-baseline"
+CMD="bench.py --config cfg5 --full --steps 256 --warmup 32 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $CMD > $OUT/bench_under_rocprofv3.json 2> $OUT/stats.err || exit 1
 echo "profiled cfg5"
 python3 $CMD > $OUT/bench_unprofiled.json 2> $OUT/unprofiled.err || exit 1
