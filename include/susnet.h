@@ -24,6 +24,7 @@
  *   susnet_featurize       SequenceStateFeaturizer.fit(state_sequence[B,T,S]) on windows / replay batches
  *                          src/features/model_ready.py:41-57, 254-289, 338-354 (callers: src/train.py:345-347)
  *   susnet_scent           ImposterScentFeaturizer.extract_features   src/features/component.py:336-380
+ *   susnet_dqn_train_step  DQNTeamTrainer.train_step on ReplayBuffer.sample's rows  src/train.py:50-149, src/replay_memory.py:75-94
  *   susnet_seed / _tick    np.random.seed(seed)            src/environment/base.py:126,267 (production stream)
  *   susnet_device_tick     (new) step counter in device memory: captured launches replay as a hipGraph
  *   susnet_bind_tape       (numpy's own MT19937 words: decisions equal the reference's for that seed)
@@ -465,6 +466,57 @@ int susnet_reduce_lifetime(susnet_env *env, int64_t *out_device, void *stream);
  * susnet_step}) can be replayed any number of times.  enable = 0 reads it back (synchronises `stream`).  susnet_tick()
  * keeps working in both modes. */
 int susnet_device_tick(susnet_env *env, int32_t enable, void *stream);
+
+/* The learner's train step -- DQNTeamTrainer.train_step (src/train.py:50-149) on a replay batch drawn by index from the device ring
+ * (ReplayBuffer.sample, src/replay_memory.py:75-94; the ring tensors of susnet_ring_io are read in place, nothing is gathered):
+ * for agent i = 0 .. A-1, first the imposter team (rows with imposters[row][0] == i, train.py:83-84), then the crew team (the other
+ * rows): Q = online(features(states))[rows, actions[rows][i]], y = rewards[rows][i] + gamma * max_a target(features(next_states))
+ * (y = rewards on done rows, train.py:121-134; truncation ignored as there), loss = mean MSE (train.py:136), backward -- the
+ * gradients ACCUMULATE over the agents, the reference zeroes them once per call (train.py:64-67) -- and one torch.optim.Adam step
+ * (train.py:24-38: betas, eps, no weight decay; torch's single-tensor update order).  A team without rows in the batch takes no step
+ * and its step count does not advance (train.py:101).  Everything is decided on the device: no host synchronisation, at most two
+ * launches per (agent, team) update, one launch per call to split the batch and one per team to rewrite its packed image, so a
+ * whole call can be captured as a hipGraph.  Sums of partials run in a fixed order: results are bitwise reproducible.
+ * Served: what susnet_qnet_forward serves (the compiled-in feature layouts, dims [F, <=256, <=128, <=64, <=32, <=32]) with
+ * trajectory_size == 1 and one imposter (the reference's own train_step fails on two: `(batch.imposters == agent_idx).view(-1)`,
+ * train.py:83, has n_imposters * N entries); anything else returns SUSNET_E_INVALID and the caller runs the step in torch.
+ * Input validity is the caller's: the kernels do not stop on bad data but keep every access in bounds -- an index outside
+ * 0 .. max_size-1 is clamped into it, an action outside 0 .. n_actions-1 likewise, and a state row with a coordinate off the grid
+ * featurizes as all zeros (where the reference would raise).  DeviceDQNTeamTrainer draws the indices itself, and the ring is written
+ * by susnet_ring_append, whose rows are valid by construction. */
+typedef struct susnet_dqn_team {
+    int32_t enabled;          /* != 0: the team has an optimizer (OptimizerType.build returns None for a random model, train.py:33-34) */
+    int32_t n_dims;           /* 6 */
+    int32_t dims[8];          /* [F, h1, h2, h3, h4, n_actions] (MLP layer_dims, dqn.py:72-82) */
+    double lr, beta1, beta2, eps; /* torch.optim.Adam(params, lr=learning_rate) (train.py:35-37): betas (0.9, 0.999), eps 1e-8 */
+    float *params;            /* device, torch parameter order of MLP.parameters() (model.0.weight [h1][F], model.0.bias, model.1.weight (the
+                               * PReLU slope), model.2.weight, ...), contiguous; updated in place */
+    const float *target_params; /* the target network (train.py:341-343), same layout */
+    float *exp_avg, *exp_avg_sq;  /* Adam state (torch's state['exp_avg'], state['exp_avg_sq']), same layout */
+    float *step;              /* [1] float32: Adam's state['step'], advanced on the device */
+    float *packed;            /* susnet_qnet_pack image of `params` to rewrite after the call (bitwise what the host packer makes), or NULL */
+} susnet_dqn_team;
+typedef struct susnet_dqn_io {
+    int32_t n_components;     /* the FlatFeaturizer components the networks read (model_ready.py:309-367) */
+    int32_t components[16];
+    int32_t trajectory_size;  /* ring window T (replay_memory.py:33-44); 1 is served */
+    const float *states;      /* ring [max_size][T][S] float32 (replay_memory.py:33-44) */
+    const float *next_states; /* ring [max_size][T][S] float32 */
+    const int64_t *actions;   /* ring [max_size][A] int64 */
+    const float *rewards;     /* ring [max_size][A] float32 */
+    const uint8_t *dones;     /* ring [max_size][1] bool */
+    const int16_t *imposters; /* ring [max_size][n_imposters] int16 */
+    int64_t max_size;
+    const int64_t *indices;   /* [n] device: the sampled ring rows (torch.randint(0, size, (batch_size,)), replay_memory.py:89) */
+    int64_t n;
+    double gamma;             /* DQNTeamTrainer.gamma (train.py:42-45) */
+    susnet_dqn_team team[2];  /* [0] imposters, [1] crew (train.py:91-99) */
+    float *losses_out;        /* [2] float32 device: the accumulated losses [imposter, crew] (train.py:60, 139) */
+    void *workspace;          /* device scratch of susnet_dqn_workspace_bytes bytes, 256-byte aligned */
+    uint64_t workspace_bytes;
+} susnet_dqn_io;
+int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out);
+int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream);
 
 /* Synchronises `stream`, reads and clears the device error word. Returns 0 or the most severe
  * SUSNET_E_ACTION_* / SUSNET_E_TAPE / SUSNET_E_ROW code; *bits_out receives the raw bits. */

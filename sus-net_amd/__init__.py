@@ -16,8 +16,9 @@ from .env import (  # noqa: F401,E402
     Action, BatchedFourRoomEnv, BatchedFourRoomEnvWithTagging, BatchedImposterTrainingGround, ObsConfig,
     StateFields, four_room_grid,
 )
-from . import _lib, build_hip, dist, features, policy, replay  # noqa: F401,E402
+from . import _lib, build_hip, dist, features, policy, replay, trainer  # noqa: F401,E402
 from .replay import Batch, DeviceReplayBuffer  # noqa: F401,E402
+from .trainer import DeviceDQNTeamTrainer, torch_train_step  # noqa: F401,E402
 from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout  # noqa: F401,E402
 from .features import FlatFeaturizer, GlobalFeaturizer, PerspectiveFeaturizer  # noqa: F401,E402
 

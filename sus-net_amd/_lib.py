@@ -34,6 +34,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step",
 ]
 
 
@@ -100,6 +101,19 @@ class FeedIO(C.Structure):
 class PolicyOpts(C.Structure):
     _fields_ = [("epsilon", C.c_float), ("mask_dead", C.c_int32), ("crew_packed", C.c_void_p), ("crew_dims", C.POINTER(C.c_int32)),
                 ("crew_n_dims", C.c_int32), ("pad_", C.c_int32), ("crew_q_out", C.c_void_p)]
+
+
+class DqnTeam(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("n_dims", C.c_int32), ("dims", C.c_int32 * 8), ("lr", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("params", C.c_void_p), ("target_params", C.c_void_p), ("exp_avg", C.c_void_p),
+                ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("packed", C.c_void_p)]
+
+
+class DqnIO(C.Structure):
+    _fields_ = [("n_components", C.c_int32), ("components", C.c_int32 * 16), ("trajectory_size", C.c_int32), ("states", C.c_void_p),
+                ("next_states", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("imposters", C.c_void_p),
+                ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double), ("team", DqnTeam * 2),
+                ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
 
 
 class RecordLayout(C.Structure):
@@ -194,6 +208,8 @@ def lib():
     L.susnet_poll_errors.argtypes = [C.c_void_p, P(C.c_uint32), C.c_void_p]
     L.susnet_ring_append.argtypes = [C.c_void_p, P(RingIO), C.c_void_p]
     L.susnet_scent.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    L.susnet_dqn_workspace_bytes.argtypes = [C.c_void_p, P(DqnIO), P(C.c_uint64)]
+    L.susnet_dqn_train_step.argtypes = [C.c_void_p, P(DqnIO), C.c_void_p]
     for name in EXPORTS:
         if name not in ("susnet_last_error", "susnet_destroy"):
             getattr(L, name).restype = C.c_int

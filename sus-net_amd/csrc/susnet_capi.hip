@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -16,6 +17,7 @@
 #include "susnet_kernels.h"
 #include "susnet_family.h"
 #include "susnet_qnet.h"
+#include "susnet_train.h"
 
 namespace susnet {
 SUSNET_DECLARE(GenericSpec) SUSNET_DECLARE(SpecCfg2) SUSNET_DECLARE(SpecCfg3) SUSNET_DECLARE(SpecCfg4) SUSNET_DECLARE(SpecTag5)
@@ -2153,4 +2155,140 @@ extern "C" int susnet_poll_errors(susnet_env *env, uint32_t *bits_out, void *str
     if (bits & SUSNET_ERRBIT_TAPE) return fail(SUSNET_E_TAPE, "random tape exhausted");
     if (bits & SUSNET_ERRBIT_ROW) return fail(SUSNET_E_ROW, "susnet_featurize: a state row holds a coordinate outside the grid");
     return SUSNET_OK;
+}
+
+// ---- the learner's train step (susnet_train.h) ----
+struct DqnPlan {
+    int feat = 0;
+    TrainNet net[2];
+    int64_t G = 1;
+    uint64_t off_lists = 0, off_counts = 0, off_gacc[2] = {0, 0}, off_partial = 0, bytes = 0;
+};
+static int dqn_net(const susnet_dqn_team &tm, int feat, TrainNet &net) {
+    bool ok = false;
+    switch (feat) {
+    case FEAT_ONEHOT: ok = qnet_dims_ok<QRow1>(tm.dims, tm.n_dims); break;
+    case FEAT_ONEHOT_ALIVE_CLOSEST: ok = qnet_dims_ok<QRow3>(tm.dims, tm.n_dims); break;
+    case FEAT_COORD: ok = qnet_dims_ok<QRowC>(tm.dims, tm.n_dims); break;
+    }
+    if (!ok || tm.dims[0] > kTrMaxF) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: served are five Linear layers [F, <=256, <=128, <=64, <=32, <=32] on the "
+                                                             "compiled-in feature layouts (those of susnet_qnet_forward)");
+    int off = 0;
+    for (int l = 0; l < 6; l++) net.d[l] = tm.dims[l];
+    for (int l = 0; l < 5; l++) { // MLP.parameters(): Linear weight, Linear bias, PReLU weight, ... (dqn.py:322-329)
+        net.oW[l] = off;
+        off += net.d[l + 1] * net.d[l];
+        net.oB[l] = off;
+        off += net.d[l + 1];
+        if (l < 4) net.oA[l] = off++;
+    }
+    net.P = off;
+    net.Pp = (off + 1 + 3) / 4 * 4;
+    return SUSNET_OK;
+}
+static int dqn_plan(const susnet_env *env, const susnet_dqn_io *io, DqnPlan &pl) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null env / io");
+    if (env->c.n_imp != 1)
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: one imposter is served -- the reference's train_step fails on two or more, "
+                                      "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (io->trajectory_size != 1) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: trajectory_size 1 is served (MLP on one state)");
+    if (io->n < 0 || io->n > (1ll << 30)) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n out of range");
+    if (io->n_components < 1 || io->n_components > 16) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n_components");
+    pl.feat = qnet_feat(env, io->components, io->n_components);
+    if (!pl.feat) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: the feature layout has no compiled-in writer");
+    int64_t pmax = 4;
+    for (int tm = 0; tm < 2; tm++) {
+        pl.net[tm] = TrainNet{};
+        if (!io->team[tm].enabled) continue;
+        if (int rc = dqn_net(io->team[tm], pl.feat, pl.net[tm])) return rc;
+        pmax = std::max<int64_t>(pmax, pl.net[tm].Pp);
+    }
+    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
+    pl.G = std::max<int64_t>(1, std::min<int64_t>(kTrMaxGrid, tiles));
+    const int A = env->c.A;
+    uint64_t o = 0;
+    pl.off_lists = o;
+    o = up(o + 4ull * 2 * A * (uint64_t)std::max<int64_t>(io->n, 1), 256);
+    pl.off_counts = o;
+    o = up(o + 4ull * 2 * A, 256);
+    for (int tm = 0; tm < 2; tm++) {
+        pl.off_gacc[tm] = o;
+        o = up(o + 4ull * (uint64_t)std::max(pl.net[tm].Pp, 4), 256);
+    }
+    pl.off_partial = o;
+    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)pmax, 256);
+    pl.bytes = o;
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out) {
+    DqnPlan pl;
+    if (int rc = dqn_plan(env, io, pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_dqn_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+template <class ROW>
+static int dqn_launch(const susnet_env *env, const susnet_dqn_io *io, const DqnPlan &pl, hipStream_t st) {
+    // the kernel's dynamic-LDS ceiling, set once per device (a cheap host call; not repeated inside a capture after the first eager step)
+    static std::atomic<uint64_t> lds_set{0};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(lds_set.load() & bit)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_train_grad<ROW>), hipFuncAttributeMaxDynamicSharedMemorySize, kTrLdsBytes));
+        lds_set.fetch_or(bit);
+    }
+    char *ws = static_cast<char *>(io->workspace);
+    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
+    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
+    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    TrainRing ring{io->states, io->next_states, io->actions, io->rewards, io->dones, io->imposters, io->max_size,
+                   (int32_t)env->layout.obs_raw_size, (int32_t)env->c.A, (int32_t)env->c.n_imp};
+    const int64_t N = io->n;
+    hipLaunchKernelGGL(k_train_select, dim3(1), dim3(kTrThreads), kTrThreads * 4, st, ring, io->indices, N, lists, counts, gacc[0], pl.net[0].P, gacc[1],
+                       pl.net[1].P, io->losses_out);
+    HIP_TRY(hipGetLastError());
+    if (N == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            const susnet_dqn_team &T = io->team[tm];
+            if (!T.enabled) continue;
+            hipLaunchKernelGGL(k_train_grad<ROW>, dim3((unsigned)pl.G), dim3(kTrThreads), kTrLdsBytes, st, ring, pl.net[tm], T.params, T.target_params, lists,
+                               counts, N, agent, tm, (float)io->gamma, partial, T.step);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm], counts, agent, tm, partial,
+                               (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
+            HIP_TRY(hipGetLastError());
+        }
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled || !T.packed) continue;
+        hipLaunchKernelGGL(k_train_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256)), dim3(256), 0, st, pl.net[tm], T.params, T.packed);
+        HIP_TRY(hipGetLastError());
+    }
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream) {
+    if (int rc = check_bound(env)) return rc;
+    DqnPlan pl;
+    if (int rc = dqn_plan(env, io, pl)) return rc;
+    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: workspace missing, smaller than susnet_dqn_workspace_bytes or not 256-byte aligned");
+    if (!io->states || !io->next_states || !io->actions || !io->rewards || !io->dones || !io->imposters || !io->losses_out || io->max_size < 1 ||
+        (io->n > 0 && !io->indices))
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null ring tensor / indices / losses_out");
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (T.enabled && (!T.params || !T.target_params || !T.exp_avg || !T.exp_avg_sq || !T.step))
+            return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: an enabled team needs params / target_params / exp_avg / exp_avg_sq / step");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (pl.feat) {
+    case FEAT_ONEHOT: return dqn_launch<QRow1>(env, io, pl, st);
+    case FEAT_COORD: return dqn_launch<QRowC>(env, io, pl, st);
+    default: return dqn_launch<QRow3>(env, io, pl, st);
+    }
 }

@@ -1,0 +1,314 @@
+"""The learner's half of the reference trainer on the device: ``DQNTeamTrainer.train_step`` (src/train.py:50-149) on a batch drawn
+from a ``DeviceReplayBuffer`` (``ReplayBuffer.sample``, src/replay_memory.py:75-94).
+
+* HIP path (``susnet_dqn_train_step``, csrc/susnet_train.h): reference ``MLP``s on a compiled-in feature layout (the layouts
+  ``susnet_qnet_forward`` serves), a window of one state, one imposter.  The ring is read in place at the sampled indices; per (agent,
+  team) update one gradient launch and one reduce + Adam launch, no host synchronisation, and the teams' packed images (what
+  ``PolicyRollout`` acts with) are rewritten on the device.
+* torch path (``torch_train_step``): the same algorithm in torch ops for anything else -- ``SpatialDQN``, other layer stacks, longer
+  windows, CPU tensors.
+
+The parameters of each trained team live in ONE flat float32 buffer in ``model.parameters()`` order, and the modules' parameters are
+views into it: after a step the ``nn.Module`` holds the new values (``dump_to_checkpoint`` works), whichever path ran.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import _lib as L
+from .policy import MLP, RandomEquiprobable, _weights_version
+
+BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults (train.py:35-37 passes only lr)
+
+
+def torch_train_step(models, targets, optimizers, gamma: float, state_feats, next_state_feats, actions, rewards, dones, imposters) -> List[float]:
+    """``DQNTeamTrainer.train_step`` (train.py:50-149) on featurized batches: ``state_feats`` / ``next_state_feats`` = one
+    ``(spatial, non_spatial)`` pair per agent (``generate_featurized_states()``), ``models`` / ``targets`` / ``optimizers`` = [imposter,
+    crew] (an optimizer of None: the team does not train).  Returns ``[imposter_loss, crew_loss]`` summed over agents, as floats."""
+    losses = [0.0, 0.0]
+    if all(o is None for o in optimizers):
+        return losses
+    for opt in optimizers:  # train.py:64-67: ONCE per call -- the gradients accumulate over the agents
+        if opt is not None:
+            opt.zero_grad()
+    if imposters.shape[1] != 1:
+        raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
+                         "(src/train.py:83) has n_imposters * N entries")
+    for agent_idx, (sf, nf) in enumerate(zip(state_feats, next_state_feats)):
+        imp_rows = (imposters == agent_idx).view(-1)
+        for team, rows in ((0, imp_rows), (1, ~imp_rows)):
+            opt, model, target = optimizers[team], models[team], targets[team]
+            if opt is None or int(rows.sum()) == 0:
+                continue
+            model.train()
+            q = model(sf[0][rows], sf[1][rows])
+            values = torch.gather(q, 1, actions[rows, agent_idx].view(-1, 1)).view(-1)
+            with torch.no_grad():
+                done_mask = dones[rows].view(-1)
+                r = rewards[rows, agent_idx].view(-1)
+                y = r + gamma * torch.max(target(nf[0][rows], nf[1][rows]), dim=1)[0]
+                y[done_mask] = r[done_mask]
+            loss = F.mse_loss(values, y)
+            loss.backward()
+            losses[team] += loss.item()
+            opt.step()
+    return losses
+
+
+def _flatten_into(module: nn.Module, device) -> torch.Tensor:
+    """One flat float32 buffer holding ``module``'s parameters in ``parameters()`` order; the parameters become views into it."""
+    params = list(module.parameters())
+    flat = torch.cat([p.detach().reshape(-1).to(device, torch.float32) for p in params]) if params else torch.zeros(0, device=device)
+    off = 0
+    for p in params:
+        n = p.numel()
+        p.data = flat[off:off + n].view_as(p)
+        off += n
+    return flat
+
+
+class DeviceDQNTeamTrainer:
+    """``DQNTeamTrainer`` (train.py:40-149) with its models, target models (train.py:306-307, 341-343) and Adam optimizers
+    (train.py:24-38), for a ``DeviceReplayBuffer`` of ``env``.  ``components``: the FlatFeaturizer components the networks read.
+    ``policy``: a ``PolicyRollout`` whose fused images should follow the trained weights without a host re-pack (it must read the same
+    ``components``).  ``featurizer``: what the torch path featurizes the ring's states with (``features.FlatFeaturizer`` over
+    ``components`` by default; a ``SpatialDQN`` needs a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of the same env)."""
+
+    def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module], components: Sequence[str], lr: float, gamma: float,
+                 train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None):
+        if env.n_imposters >= 2:
+            raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
+                             "(src/train.py:83) has n_imposters * N entries")
+        self.env, self.components, self.lr, self.gamma, self.policy = env, list(components), float(lr), float(gamma), policy
+        self.device = torch.device(env.device)
+        self.models = [imposter_model, crew_model]
+        # OptimizerType.build returns None for a random model (train.py:33-34)
+        self.trained = [bool(flag) and m is not None and not isinstance(m, RandomEquiprobable) and any(True for _ in m.parameters())
+                        for m, flag in ((imposter_model, train_imposter), (crew_model, train_crew))]
+        self.targets: List[Optional[nn.Module]] = [None, None]
+        self.flat: List[Optional[torch.Tensor]] = [None, None]
+        self.target_flat: List[Optional[torch.Tensor]] = [None, None]
+        self.exp_avg: List[Optional[torch.Tensor]] = [None, None]
+        self.exp_avg_sq: List[Optional[torch.Tensor]] = [None, None]
+        self.step_count: List[Optional[torch.Tensor]] = [None, None]
+        for t, m in enumerate(self.models):
+            if m is None:
+                continue
+            m.to(self.device)
+            target = m.create_copy().to(self.device) if hasattr(m, "create_copy") else None
+            self.targets[t] = target
+            if self.trained[t]:
+                self.flat[t] = _flatten_into(m, self.device)
+                self.target_flat[t] = _flatten_into(target, self.device)
+                self.exp_avg[t] = torch.zeros_like(self.flat[t])
+                self.exp_avg_sq[t] = torch.zeros_like(self.flat[t])
+                self.step_count[t] = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._dims = [self._mlp_dims(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self.hip = (self.device.type == "cuda" and any(self.trained) and all(d is not None for d, tr in zip(self._dims, self.trained) if tr)
+                    and self._hip_served())
+        if policy is not None and any(self._policy_image(t) is not None for t in range(2)) and list(policy.components) != self.components:
+            raise ValueError(f"policy reads components {list(policy.components)}, the trainer {self.components}: the rewritten images would "
+                             "belong to another feature layout")
+        self._featurizer = featurizer
+        self._optim: List[Optional[torch.optim.Adam]] = [None, None]
+        # where each team's Adam state currently lives: "flat" (the buffers the kernels update) or "optim" (the torch optimizer)
+        self._owner = ["flat", "flat"]
+        self._ws, self._losses = None, None
+
+    # ---- configuration ----
+    @staticmethod
+    def _mlp_dims(model):
+        if not isinstance(model, MLP):
+            return None
+        layers = list(model.model)
+        lin, act = layers[0::2], layers[1::2]
+        if len(lin) != 5 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in lin) or \
+                not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in act):
+            return None
+        return [lin[0].in_features] + [m.out_features for m in lin]
+
+    def _io(self, ring=None, idx=None) -> "L.DqnIO":
+        io = L.DqnIO()
+        io.n_components = len(self.components)
+        for i, c in enumerate(self.components):
+            io.components[i] = L.FLAT_COMPONENTS[c]
+        io.trajectory_size = ring.trajectory_size if ring is not None else 1
+        io.gamma = self.gamma
+        for t in range(2):
+            tm = io.team[t]
+            if not self.trained[t] or self._dims[t] is None:
+                continue
+            tm.enabled, tm.n_dims = 1, 6
+            for i, v in enumerate(self._dims[t]):
+                tm.dims[i] = v
+            tm.lr, tm.beta1, tm.beta2, tm.eps = self.lr, BETAS[0], BETAS[1], EPS
+            tm.params, tm.target_params = self.flat[t].data_ptr(), self.target_flat[t].data_ptr()
+            tm.exp_avg, tm.exp_avg_sq, tm.step = self.exp_avg[t].data_ptr(), self.exp_avg_sq[t].data_ptr(), self.step_count[t].data_ptr()
+            net = self._policy_image(t)
+            tm.packed = net.packed.data_ptr() if net is not None else None
+        if ring is not None:
+            io.states, io.next_states = ring.states.data_ptr(), ring.next_states.data_ptr()
+            io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
+            io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
+            io.max_size = ring.max_size
+        if idx is not None:
+            io.indices, io.n = idx.data_ptr(), idx.numel()
+        return io
+
+    def _hip_served(self) -> bool:
+        io = self._io()
+        io.max_size, io.n = 1, 1
+        nbytes = C.c_uint64()
+        return self.env.lib.susnet_dqn_workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
+
+    def _policy_image(self, team):
+        p = self.policy
+        if p is None:
+            return None
+        if team == 0 and p.imposter_model is self.models[0]:
+            return p.fused_imposter
+        if team == 1 and p.crew_model is self.models[1]:
+            return p.fused_crew
+        return None
+
+    def uses_hip(self, ring) -> bool:
+        """Whether ``ring`` is trained on by ``susnet_dqn_train_step`` (else: ``torch_train_step``)."""
+        return self.hip and ring.trajectory_size == 1 and ring.states.device == self.device
+
+    # ---- the train step ----
+    def train_step(self, ring, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Sample ``batch_size`` ring rows uniformly with replacement (replay_memory.py:89) and take one train step.  Returns the
+        device ``[2]`` losses ``[imposter, crew]`` (HIP path: without synchronising)."""
+        assert ring.size > 0, "Replay buffer is empty, can't sample"
+        idx = torch.randint(0, ring.size, (int(batch_size),), device=ring.states.device, generator=generator)
+        return self.train_step_on_indices(ring, idx)
+
+    def train_step_on_indices(self, ring, idx: torch.Tensor) -> torch.Tensor:
+        idx = idx.to(ring.states.device, torch.int64).contiguous()
+        if self.uses_hip(ring):
+            return self._hip_step(ring, idx)
+        return self._torch_step(ring, idx)
+
+    def _hip_step(self, ring, idx):
+        env = self.env
+        for t in range(2):
+            self._state_to_flat(t)
+        io = self._io(ring, idx)
+        nbytes = C.c_uint64()
+        L.check(env.lib.susnet_dqn_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)))
+        if self._ws is None or self._ws.numel() < nbytes.value:
+            self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        if self._losses is None:
+            self._losses = torch.zeros(2, dtype=torch.float32, device=self.device)
+        io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        io.losses_out = self._losses.data_ptr()
+        with torch.cuda.device(self.device):
+            L.check(env.lib.susnet_dqn_train_step(env._h, C.byref(io), env._stream()))
+        self._sync_policy_version()
+        return self._losses.clone()  # (a new tensor per step, as the torch path returns; enqueued, no host wait)
+
+    def _sync_policy_version(self):
+        p = self.policy
+        if p is not None and any(self._policy_image(t) is not None for t in range(2)):
+            # the images were rewritten on the device (in-place kernel writes leave the parameters' versions as they were)
+            p._packed_version = (_weights_version(p.imposter_model), _weights_version(p.crew_model))
+
+    def optimizers(self):
+        """torch.optim.Adam per team over the module parameters (the torch path), state mirrored from the flat buffers."""
+        for t in range(2):
+            if self.trained[t] and self._optim[t] is None:
+                self._optim[t] = torch.optim.Adam(self.models[t].parameters(), lr=self.lr)
+        return self._optim
+
+    def _torch_step(self, ring, idx):
+        from .features import FlatFeaturizer
+
+        opts = self.optimizers()
+        for t in range(2):
+            if self.trained[t] and self._owner[t] == "flat":
+                self._optim[t].load_state_dict(self._flat_state_dict(t))
+                self._owner[t] = "optim"
+        if self._featurizer is None:
+            self._featurizer = FlatFeaturizer(self.env, self.components)
+        fz = self._featurizer
+        fz.fit(ring.states[idx])
+        sf = fz.generate_featurized_states()
+        fz.fit(ring.next_states[idx])
+        nf = fz.generate_featurized_states()
+        losses = torch_train_step(self.models, self.targets, [o if tr else None for o, tr in zip(opts, self.trained)], self.gamma, sf, nf,
+                                  ring.actions[idx], ring.rewards[idx], ring.dones[idx], ring.imposters[idx])
+        if self.policy is not None:
+            self.policy.refresh_weights(force=True)
+        return torch.tensor(losses, dtype=torch.float32, device=self.device)
+
+    # ---- optimizer state, in torch.optim.Adam's format ----
+    def _state_to_flat(self, t):
+        if self.trained[t] and self._owner[t] == "optim":
+            self._set_state(t, self._optim[t].state_dict())
+            self._owner[t] = "flat"
+
+    def state_tensors(self, team: int):
+        """``(exp_avg, exp_avg_sq, step)`` of ``team`` as flat device tensors in ``parameters()`` order."""
+        self._state_to_flat(team)
+        return self.exp_avg[team], self.exp_avg_sq[team], self.step_count[team]
+
+    def optimizer_state_dict(self, team: int) -> dict:
+        """``torch.optim.Adam(model.parameters(), lr).state_dict()`` of ``team`` (0 imposter, 1 crew)."""
+        assert self.trained[team], "this team has no optimizer"
+        if self._owner[team] == "optim":
+            return self._optim[team].state_dict()
+        return self._flat_state_dict(team)
+
+    def _flat_state_dict(self, team: int) -> dict:
+        params = list(self.models[team].parameters())
+        state = {}
+        step = float(self.step_count[team].item())
+        if step > 0:
+            off = 0
+            for i, p in enumerate(params):
+                n = p.numel()
+                state[i] = {"step": torch.tensor(step), "exp_avg": self.exp_avg[team][off:off + n].view_as(p).clone(),
+                            "exp_avg_sq": self.exp_avg_sq[team][off:off + n].view_as(p).clone()}
+                off += n
+        group = {"lr": self.lr, "betas": BETAS, "eps": EPS, "weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, team: int, sd: dict) -> None:
+        assert self.trained[team], "this team has no optimizer"
+        self._set_state(team, sd)
+        self._owner[team] = "flat"
+
+    def _set_state(self, team, sd):
+        params = list(self.models[team].parameters())
+        st = sd["state"]
+        off, step = 0, 0.0
+        for i, p in enumerate(params):
+            n = p.numel()
+            s = st.get(i)
+            if s:
+                self.exp_avg[team][off:off + n].copy_(s["exp_avg"].reshape(-1))
+                self.exp_avg_sq[team][off:off + n].copy_(s["exp_avg_sq"].reshape(-1))
+                step = float(s["step"])
+            else:
+                self.exp_avg[team][off:off + n].zero_()
+                self.exp_avg_sq[team][off:off + n].zero_()
+            off += n
+        self.step_count[team].fill_(step)
+
+    # ---- target networks ----
+    @torch.no_grad()
+    def sync_targets(self) -> None:
+        """``target.load_state_dict(model.state_dict())`` for both teams (train.py:341-343)."""
+        for t in range(2):
+            if self.targets[t] is None:
+                continue
+            if self.target_flat[t] is not None:
+                self.target_flat[t].copy_(self.flat[t])
+            else:
+                self.targets[t].load_state_dict(self.models[t].state_dict())
