@@ -25,6 +25,7 @@
  *                          src/features/model_ready.py:41-57, 254-289, 338-354 (callers: src/train.py:345-347)
  *   susnet_scent           ImposterScentFeaturizer.extract_features   src/features/component.py:336-380
  *   susnet_dqn_train_step  DQNTeamTrainer.train_step on ReplayBuffer.sample's rows  src/train.py:50-149, src/replay_memory.py:75-94
+ *   susnet_episode_stats   train()'s episode bookkeeping: G = reward + gamma * G, the teams' mean returns, episode lengths  src/train.py:385-450
  *   susnet_seed / _tick    np.random.seed(seed)            src/environment/base.py:126,267 (production stream)
  *   susnet_device_tick     (new) step counter in device memory: captured launches replay as a hipGraph
  *   susnet_bind_tape       (numpy's own MT19937 words: decisions equal the reference's for that seed)
@@ -50,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SUSNET_ABI_VERSION 6
+#define SUSNET_ABI_VERSION 7
 
 #define SUSNET_MAX_AGENTS 16
 #define SUSNET_MAX_JOBS 16
@@ -517,6 +518,53 @@ typedef struct susnet_dqn_io {
 } susnet_dqn_io;
 int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out);
 int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream);
+
+/* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
+ * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.
+ * Per tick t and environment b, for every agent: G[a] = (double)rewards[t][b][a] + gamma * G[a] in float64, the product rounded before
+ * the add (no fused multiply-add: numpy makes a temporary).  Where done | truncated: one record is appended to the log with
+ * imposter_return = mean of G over the agents in roles[t][b], crew_return = mean over the others -- each in numpy's summation order
+ * (below 8 values left to right from 0.0; from 8 values ((x0+x1)+(x2+x3))+((x4+x5)+(x6+x7)), then x8, x9, ... one by one; divided by
+ * the count; an empty team gives NaN) --, length = t_episode + 1, tick = tick_base + t, env = b; then G = 0 and t_episode = 0 for that
+ * environment.  Otherwise t_episode += 1.  G and t_episode are carried between calls in `carry`.
+ * Log order is tick-major, env-minor -- what a host loop over ticks and environments appends -- on every run: positions come from
+ * per-(tick, wave) ballot counts and a scan in fixed order, never from an atomic.  When the log is full further episodes are counted in
+ * *dropped and not written; the carried state still advances.  Three launches per call whatever n_ticks and the batch are, no host
+ * synchronisation: a call can be captured in a hipGraph.  Served: 2 .. 12 agents, any batch, any n_ticks >= 1.  The handle supplies
+ * the configuration (agent count, batch) only; no environment state is read.
+ * susnet_episode_stats_bytes: the sizes of `carry` (float64 G[A][B], then int32 t_episode[B]; all zero = every environment at the start
+ * of an episode) and of `workspace` for blocks of up to n_ticks ticks. */
+#define SUSNET_EPISODE_DONE 1      /* ended_by bits */
+#define SUSNET_EPISODE_TRUNCATED 2
+typedef struct susnet_episode_record {
+    double imposter_return;   /* G[imposter_mask].mean() (train.py:421) */
+    double crew_return;       /* G[~imposter_mask].mean() (train.py:422) */
+    int64_t tick;             /* tick_base + t: the lockstep tick at which the episode ended */
+    int32_t env;              /* b */
+    int32_t length;           /* steps of the episode: the reference's t_episode + 1 (train.py:430) */
+    int32_t ended_by;         /* SUSNET_EPISODE_DONE | SUSNET_EPISODE_TRUNCATED */
+    int32_t reserved;         /* 0 */
+} susnet_episode_record;
+typedef struct susnet_episode_io {
+    int32_t n_ticks;          /* T >= 1 */
+    int32_t reserved;
+    const float *rewards;     /* [T][B][A] float32 */
+    const uint8_t *done;      /* [T][B] */
+    const uint8_t *truncated; /* [T][B] */
+    const uint16_t *roles;    /* [T][B] imposter bitmask of the episode that acted */
+    double gamma;
+    int64_t tick_base;        /* the lockstep tick index of slot 0 */
+    void *carry;              /* device, carry_bytes of susnet_episode_stats_bytes, 8-byte aligned; read and updated */
+    uint64_t carry_bytes;
+    susnet_episode_record *log; /* device [capacity], append-only */
+    int64_t capacity;
+    int64_t *count;           /* device [1]: records in the log; read and advanced on the device */
+    int64_t *dropped;         /* device [1]: episodes that found the log full */
+    void *workspace;          /* device scratch, workspace_bytes of susnet_episode_stats_bytes for >= n_ticks, 8-byte aligned */
+    uint64_t workspace_bytes;
+} susnet_episode_io;
+int susnet_episode_stats_bytes(const susnet_env *env, int32_t n_ticks, uint64_t *carry_bytes_out, uint64_t *workspace_bytes_out);
+int susnet_episode_stats(susnet_env *env, const susnet_episode_io *io, void *stream);
 
 /* Synchronises `stream`, reads and clears the device error word. Returns 0 or the most severe
  * SUSNET_E_ACTION_* / SUSNET_E_TAPE / SUSNET_E_ROW code; *bits_out receives the raw bits. */

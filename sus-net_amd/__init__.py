@@ -16,9 +16,12 @@ from .env import (  # noqa: F401,E402
     Action, BatchedFourRoomEnv, BatchedFourRoomEnvWithTagging, BatchedImposterTrainingGround, ObsConfig,
     StateFields, four_room_grid,
 )
-from . import _lib, build_hip, dist, features, policy, replay, trainer  # noqa: F401,E402
+from . import _lib, build_hip, dist, episodes, features, policy, replay, scheduler, train_loop, trainer  # noqa: F401,E402
 from .replay import Batch, DeviceReplayBuffer  # noqa: F401,E402
 from .trainer import DeviceDQNTeamTrainer, torch_train_step  # noqa: F401,E402
+from .episodes import EpisodeLog  # noqa: F401,E402
+from .scheduler import ExponentialSchedule  # noqa: F401,E402
+from .train_loop import plan_blocks, run_experiment, train  # noqa: F401,E402
 from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout  # noqa: F401,E402
 from .features import FlatFeaturizer, GlobalFeaturizer, PerspectiveFeaturizer  # noqa: F401,E402
 

@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libsusnet_hip.so"
 LIB_PATH = os.environ.get("SUSNET_LIB_PATH", os.path.join(PKG_DIR, LIB_NAME))  # override: A/B experiments only
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_AGENTS, MAX_JOBS, MAX_GRID, N_METRICS, N_LIFETIME = 16, 16, 16, 13, 12
 
 VARIANT_BASE, VARIANT_ITG, VARIANT_TAGGING = 0, 1, 2
@@ -23,6 +23,7 @@ OBS_NONE, OBS_RAW, OBS_FLAT, OBS_PLANES, OBS_PERSP = 0, 1, 2, 3, 4
 E_INVALID, E_HIP, E_STATE, E_ACTION_ASSERT, E_ACTION_INDEX, E_TAPE, E_ROW = -1, -2, -3, -4, -5, -6, -7
 
 RECORD_DEFAULT, RECORD_COMPACT = 0, 1
+EPISODE_DONE, EPISODE_TRUNCATED = 1, 2  # susnet_episode_record.ended_by bits
 FLAT_COMPONENTS = {"onehot_pos": 0, "coord_pos": 1, "alive_crew": 2, "l1_crew": 3, "closest_crew": 4,
                    "walls3x3": 5, "dist_to_imp": 6, "room_loc": 7}
 LIFETIME_NAMES = ["episodes", "crew_won", "imposter_won", "truncated", "imp_killed_crew", "completed_jobs",
@@ -34,7 +35,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -114,6 +115,18 @@ class DqnIO(C.Structure):
                 ("next_states", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("imposters", C.c_void_p),
                 ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double), ("team", DqnTeam * 2),
                 ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+class EpisodeRecord(C.Structure):
+    _fields_ = [("imposter_return", C.c_double), ("crew_return", C.c_double), ("tick", C.c_int64), ("env", C.c_int32), ("length", C.c_int32),
+                ("ended_by", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EpisodeIO(C.Structure):
+    _fields_ = [("n_ticks", C.c_int32), ("reserved", C.c_int32), ("rewards", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p),
+                ("roles", C.c_void_p), ("gamma", C.c_double), ("tick_base", C.c_int64), ("carry", C.c_void_p), ("carry_bytes", C.c_uint64),
+                ("log", C.c_void_p), ("capacity", C.c_int64), ("count", C.c_void_p), ("dropped", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_uint64)]
 
 
 class RecordLayout(C.Structure):
@@ -210,6 +223,8 @@ def lib():
     L.susnet_scent.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.susnet_dqn_workspace_bytes.argtypes = [C.c_void_p, P(DqnIO), P(C.c_uint64)]
     L.susnet_dqn_train_step.argtypes = [C.c_void_p, P(DqnIO), C.c_void_p]
+    L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]
+    L.susnet_episode_stats.argtypes = [C.c_void_p, P(EpisodeIO), C.c_void_p]
     for name in EXPORTS:
         if name not in ("susnet_last_error", "susnet_destroy"):
             getattr(L, name).restype = C.c_int

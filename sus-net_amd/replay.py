@@ -200,7 +200,17 @@ class DeviceReplayBuffer:
             self.idx = (self.idx + n * B) % self.max_size
             self.size = min(self.size + n * B, self.max_size)
             done_ticks += n
+            self._collect_feed_ticks = n
         return num_steps * B
+
+    @property
+    def last_feed(self):
+        """``(feed, n_ticks)``: the ``[T][B]`` block the last ``collect`` filled last (``env.alloc_feed``'s tensors; slots ``0 .. n_ticks - 1`` are
+        valid) -- what ``EpisodeLog.update`` reads.  The next ``collect`` overwrites it."""
+        feed = getattr(self, "_collect_feed", None)
+        if feed is None:
+            raise RuntimeError("last_feed: no collect() has run on this buffer")
+        return feed, self._collect_feed_ticks
 
     def reset_collection(self) -> None:
         """Forget the carried sequence window: the next ``collect`` starts from the current state.  (``collect`` does this by itself when the
