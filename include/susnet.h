@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SUSNET_ABI_VERSION 7
+#define SUSNET_ABI_VERSION 8
 
 #define SUSNET_MAX_AGENTS 16
 #define SUSNET_MAX_JOBS 16
@@ -189,6 +189,24 @@ typedef struct susnet_obs_spec {
     void *out2;                   /* PLANES: non_spatial [B][A(+A)+J]; PERSP: [B][A][A(+A)+J]; else NULL */
 } susnet_obs_spec;
 
+/* The info counters of ONE finished episode: what the reference's `info` dict holds on the terminal step (EnvMetricHandler,
+ * src/metrics.py:35-64) and metrics.step(info) appends to the run's per-episode lists (src/train.py:419-427).  16 bytes, 16-byte
+ * aligned: the stepping lane writes it with one vector store where the episode ends, before the in-launch reset clears the counters.
+ * Kills and votes are a byte each: an episode played from its reset kills at most n_crew <= 15 agents and votes out at most 16; only
+ * imported states (susnet_import_state) can count further, and imp_killed_crew then saturates at 255.  TOTAL_STALEMATES has no field:
+ * the reference never increments it. */
+#define SUSNET_OUTCOME_CREW_WON 1u     /* bits of susnet_episode_info.outcome: SusMetrics.CREW_WON / IMPOSTER_WON */
+#define SUSNET_OUTCOME_IMPOSTER_WON 2u
+typedef struct susnet_episode_info {
+    uint32_t time_steps;      /* TOTAL_TIME_STEPS: the steps of the episode */
+    uint32_t completed_jobs;  /* COMPLETED_JOBS */
+    uint32_t sabotaged_jobs;  /* SABOTAGED_JOBS */
+    uint8_t imp_killed_crew;  /* IMP_KILLED_CREW */
+    uint8_t imp_voted_out;    /* IMP_VOTED_OUT */
+    uint8_t crew_voted_out;   /* CREW_VOTED_OUT */
+    uint8_t outcome;          /* SUSNET_OUTCOME_* (0: truncated without a winner) */
+} susnet_episode_info;
+
 typedef struct susnet_step_io {
     const void *actions;  /* role-relative action indices (base.py:379-382) */
     int32_t actions_dtype;  /* SUSNET_U8 / I32 / I64 */
@@ -205,6 +223,8 @@ typedef struct susnet_step_io {
     uint8_t *term_obs;    /* out [B][obs_raw_size] u8, written ONLY where the episode ended at this step: its true terminal state
                            * (flatten_state order), before the auto-reset replaces it */
     uint16_t *roles;      /* out [B]: imposter bitmask (bit i = agent i) of the episode that acted at this step */
+    susnet_episode_info *ep_info; /* out [B] or NULL, 16-byte aligned: written ONLY where the episode ended at this step (done | truncated),
+                                   * next to term_obs: the episode's info counters, before the auto-reset clears them */
 } susnet_step_io;
 
 /* Fused random rollout: T lockstep ticks in one launch; per tick every env samples uniform role-valid
@@ -427,6 +447,7 @@ typedef struct susnet_feed_io {
     uint8_t *term_obs;   /* out [T][B][obs_raw_size] u8, written only where an episode ended: its terminal state */
     uint16_t *roles;     /* out [T][B]: imposter bitmask of the episode that acted */
     float *q;            /* out [T][B][n_actions_imposter] f32: the imposters' Q rows, or NULL */
+    susnet_episode_info *ep_info; /* out [T][B] or NULL, 16-byte aligned: written only where an episode ended: its info counters */
 } susnet_feed_io;
 int susnet_qnet_policy_rollout(susnet_env *env, const int32_t *components, int32_t n_components, const int32_t *dims, int32_t n_dims,
                                const float *packed, const susnet_policy_opts *opts, const susnet_feed_io *feed, int32_t n_ticks, void *stream);
@@ -562,6 +583,10 @@ typedef struct susnet_episode_io {
     int64_t *dropped;         /* device [1]: episodes that found the log full */
     void *workspace;          /* device scratch, workspace_bytes of susnet_episode_stats_bytes for >= n_ticks, 8-byte aligned */
     uint64_t workspace_bytes;
+    /* both or neither: the feed's info records and a second log parallel to `log` -- the record of every ended (tick, env) is copied to
+     * info_log[pos], pos = the position of the episode's record in `log`: same count, same dropped */
+    const susnet_episode_info *info; /* [T][B]: susnet_feed_io.ep_info (read where done | truncated), or NULL */
+    susnet_episode_info *info_log;   /* device [capacity], 16-byte aligned, or NULL */
 } susnet_episode_io;
 int susnet_episode_stats_bytes(const susnet_env *env, int32_t n_ticks, uint64_t *carry_bytes_out, uint64_t *workspace_bytes_out);
 int susnet_episode_stats(susnet_env *env, const susnet_episode_io *io, void *stream);

@@ -21,7 +21,7 @@ from .replay import Batch, DeviceReplayBuffer  # noqa: F401,E402
 from .trainer import DeviceDQNTeamTrainer, torch_train_step  # noqa: F401,E402
 from .episodes import EpisodeLog  # noqa: F401,E402
 from .scheduler import ExponentialSchedule  # noqa: F401,E402
-from .train_loop import plan_blocks, run_experiment, train  # noqa: F401,E402
+from .train_loop import evaluate, evaluate_checkpoints, plan_blocks, run_experiment, train  # noqa: F401,E402
 from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout  # noqa: F401,E402
 from .features import FlatFeaturizer, GlobalFeaturizer, PerspectiveFeaturizer  # noqa: F401,E402
 

@@ -12,7 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libsusnet_hip.so"
 LIB_PATH = os.environ.get("SUSNET_LIB_PATH", os.path.join(PKG_DIR, LIB_NAME))  # override: A/B experiments only
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_AGENTS, MAX_JOBS, MAX_GRID, N_METRICS, N_LIFETIME = 16, 16, 16, 13, 12
 
 VARIANT_BASE, VARIANT_ITG, VARIANT_TAGGING = 0, 1, 2
@@ -24,6 +24,7 @@ E_INVALID, E_HIP, E_STATE, E_ACTION_ASSERT, E_ACTION_INDEX, E_TAPE, E_ROW = -1, 
 
 RECORD_DEFAULT, RECORD_COMPACT = 0, 1
 EPISODE_DONE, EPISODE_TRUNCATED = 1, 2  # susnet_episode_record.ended_by bits
+OUTCOME_CREW_WON, OUTCOME_IMPOSTER_WON = 1, 2  # susnet_episode_info.outcome bits
 FLAT_COMPONENTS = {"onehot_pos": 0, "coord_pos": 1, "alive_crew": 2, "l1_crew": 3, "closest_crew": 4,
                    "walls3x3": 5, "dist_to_imp": 6, "room_loc": 7}
 LIFETIME_NAMES = ["episodes", "crew_won", "imposter_won", "truncated", "imp_killed_crew", "completed_jobs",
@@ -73,6 +74,7 @@ class StepIO(C.Structure):
         ("actions", C.c_void_p), ("actions_dtype", C.c_int32), ("actions_layout", C.c_int32),
         ("rewards", C.c_void_p), ("rewards_dtype", C.c_int32), ("rewards_layout", C.c_int32),
         ("done", C.c_void_p), ("truncated", C.c_void_p), ("obs", C.POINTER(ObsSpec)), ("term_obs", C.c_void_p), ("roles", C.c_void_p),
+        ("ep_info", C.c_void_p),
     ]
 
 
@@ -96,7 +98,7 @@ class RingIO(C.Structure):
 
 class FeedIO(C.Structure):
     _fields_ = [("actions", C.c_void_p), ("rewards", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p), ("obs", C.c_void_p),
-                ("term_obs", C.c_void_p), ("roles", C.c_void_p), ("q", C.c_void_p)]
+                ("term_obs", C.c_void_p), ("roles", C.c_void_p), ("q", C.c_void_p), ("ep_info", C.c_void_p)]
 
 
 class PolicyOpts(C.Structure):
@@ -126,7 +128,12 @@ class EpisodeIO(C.Structure):
     _fields_ = [("n_ticks", C.c_int32), ("reserved", C.c_int32), ("rewards", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p),
                 ("roles", C.c_void_p), ("gamma", C.c_double), ("tick_base", C.c_int64), ("carry", C.c_void_p), ("carry_bytes", C.c_uint64),
                 ("log", C.c_void_p), ("capacity", C.c_int64), ("count", C.c_void_p), ("dropped", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_uint64)]
+                ("workspace_bytes", C.c_uint64), ("info", C.c_void_p), ("info_log", C.c_void_p)]
+
+
+class EpisodeInfo(C.Structure):
+    _fields_ = [("time_steps", C.c_uint32), ("completed_jobs", C.c_uint32), ("sabotaged_jobs", C.c_uint32), ("imp_killed_crew", C.c_uint8),
+                ("imp_voted_out", C.c_uint8), ("crew_voted_out", C.c_uint8), ("outcome", C.c_uint8)]
 
 
 class RecordLayout(C.Structure):

@@ -1093,6 +1093,8 @@ static int step_impl(susnet_env *env, const susnet_step_io *io, const float *q_i
     a.term_obs = io->term_obs;
     a.roles = io->roles;
     a.raw_F = env->layout.obs_raw_size;
+    if (reinterpret_cast<uintptr_t>(io->ep_info) & 15u) return fail(SUSNET_E_INVALID, "ep_info must be 16-byte aligned (one vector store per record)");
+    a.ep_info = io->ep_info;
     a.tick = env->ticks;
     ObsArgs o;
     if (int rc = build_obs(env, io->obs, o, env->c.B)) return rc;
@@ -1212,6 +1214,7 @@ extern "C" int susnet_qnet_policy_rollout(susnet_env *env, const int32_t *compon
     io.obs = feed->obs ? &obs : nullptr;
     io.term_obs = feed->term_obs;
     io.roles = feed->roles;
+    io.ep_info = feed->ep_info;
     QnetFuse f = {qnet_feat(env, components, n_components), packed, feed->q, dims[5], nullptr, nullptr, 0};
     if (int rc = qnet_crew(env, components, n_components, opts, f)) return rc;
     const TickStrides ts = {B * A, B * A * 4, B, B, B * S, B * 2, B * (int64_t)dims[5] * 4, B * (int64_t)f.crew_n_out * 4};
@@ -2346,7 +2349,11 @@ extern "C" int susnet_episode_stats(susnet_env *env, const susnet_episode_io *io
         return fail(SUSNET_E_INVALID, "susnet_episode_stats: workspace missing, smaller than susnet_episode_stats_bytes or not 8-byte aligned");
     if ((reinterpret_cast<uintptr_t>(io->log) & 7u) || (reinterpret_cast<uintptr_t>(io->count) & 7u) || (reinterpret_cast<uintptr_t>(io->dropped) & 7u))
         return fail(SUSNET_E_INVALID, "susnet_episode_stats: log / count / dropped must be 8-byte aligned");
+    if ((io->info == nullptr) != (io->info_log == nullptr)) return fail(SUSNET_E_INVALID, "susnet_episode_stats: info and info_log go together (both or neither)");
+    if ((reinterpret_cast<uintptr_t>(io->info) & 15u) || (reinterpret_cast<uintptr_t>(io->info_log) & 15u))
+        return fail(SUSNET_E_INVALID, "susnet_episode_stats: info / info_log must be 16-byte aligned");
     EpisodeArgs p;
+    p.info = io->info; p.info_log = io->info_log;
     p.rewards = io->rewards; p.done = io->done; p.truncated = io->truncated; p.roles = io->roles;
     p.G = static_cast<double *>(io->carry);
     p.t_episode = reinterpret_cast<int32_t *>(static_cast<char *>(io->carry) + pl.off_t);

@@ -1349,6 +1349,20 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
 
+// the info counters of the episode that just ended (susnet_episode_info: EnvMetricHandler's dict on the terminal step) as ONE 16-byte store
+__device__ __forceinline__ void store_episode_info(susnet_episode_info *dst, const Env &e) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    static_assert(sizeof(susnet_episode_info) == 16 && alignof(susnet_episode_info) == 4, "one 16-byte record");
+    static_assert(FLAG_CREW_WON == 2u * SUSNET_OUTCOME_CREW_WON && FLAG_IMP_WON == 2u * SUSNET_OUTCOME_IMPOSTER_WON, "outcome = flags >> 1");
+    const uint32_t kills = e.m_kv & 0xffffu;
+    u32x4 v;
+    v.x = e.m_steps;
+    v.y = e.m_fix;
+    v.z = e.m_sab;
+    v.w = (kills < 255u ? kills : 255u) | ((e.m_kv >> 16) << 8) | (((e.flags >> 1) & 3u) << 24); // kills | imp_voted << 8 | crew_voted << 16 | outcome << 24
+    *reinterpret_cast<u32x4 *>(dst) = v;
+}
+
 struct LifeAcc {
     uint32_t v[10];
     __device__ __forceinline__ void clear() {

@@ -12,7 +12,8 @@
 //                     each (tick, wave)'s first record; advances count / dropped
 //   k_episode_write   lane = environment, G in registers, loop over the ticks: the update above; where the episode ends the lane's record
 //                     goes to position[tick][wave] + (ended lanes below it in the wave) -- tick-major, env-minor, the order a host loop
-//                     over ticks and envs appends in -- when that is inside the log; the carried G / t_episode go back to memory
+//                     over ticks and envs appends in -- when that is inside the log; the carried G / t_episode go back to memory.  With
+//                     an info log the feed's susnet_episode_info of that (tick, env) is copied to the same position of the parallel log
 #pragma once
 
 #include "susnet_device.h"
@@ -37,6 +38,8 @@ struct EpisodeArgs {
     double gamma;
     int64_t tick_base;
     int32_t T, B, W;
+    const susnet_episode_info *info; // [T][B] the feed's info records (valid where done | truncated), or NULL
+    susnet_episode_info *info_log;   // [capacity] parallel to log, or NULL
 };
 
 __global__ __launch_bounds__(kEpThreads) void k_episode_count(EpisodeArgs p) {
@@ -172,6 +175,10 @@ __global__ __launch_bounds__(kEpThreads) void k_episode_write(EpisodeArgs p) {
                 rec.ended_by = (dn ? SUSNET_EPISODE_DONE : 0) | (tr ? SUSNET_EPISODE_TRUNCATED : 0);
                 rec.reserved = 0;
                 p.log[pos] = rec;
+                if (p.info_log != nullptr) { // the episode's info counters, to the same position: one 16-byte load and store
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    reinterpret_cast<u32x4 *>(p.info_log)[pos] = reinterpret_cast<const u32x4 *>(p.info)[i];
+                }
             }
 #pragma unroll
             for (int a = 0; a < A; a++) G[a] = 0.0;

@@ -33,6 +33,7 @@ struct StepArgs {
     uint8_t *term_obs; // [B][F] or NULL
     uint16_t *roles;   // [B] or NULL
     int32_t raw_F;     // flattened_state_size
+    susnet_episode_info *ep_info; // [B] ([T][B] in the multi-tick policy kernel: slot obs_tick) or NULL: the info counters of the episode that ended
 };
 constexpr int kMaxPolicyActions = 16; // Q row lengths susnet_policy_step serves
 
@@ -326,7 +327,10 @@ __device__ __forceinline__ void step_wave(const Consts &c, const State &s, const
         if (a.done) a.done[b] = done ? 1 : 0;
         if (a.trunc) a.trunc[b] = trunc ? 1 : 0;
         if (a.roles) a.roles[b] = (uint16_t)S::imp(c, e.imp); // the episode that acted (before an auto-reset draws new roles)
-        if (__builtin_expect(a.term_obs != nullptr && (done || trunc), 0)) fill_raw<S>(c, st, e, a.term_obs + b * a.raw_F); // its true terminal state
+        if (__builtin_expect((a.term_obs != nullptr || a.ep_info != nullptr) && (done || trunc), 0)) {
+            if (a.term_obs != nullptr) fill_raw<S>(c, st, e, a.term_obs + b * a.raw_F); // its true terminal state
+            if (a.ep_info != nullptr) store_episode_info(a.ep_info + obs_tick * c.B + b, e); // its info counters, before the reset clears them
+        }
         bool jobs_changed = false;
         if (__builtin_expect(c.auto_reset && (done || trunc), 0)) {
             accumulate_lifetime(c, s, b, e, trunc);

@@ -663,14 +663,17 @@ class BatchedFourRoomEnv:
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=self.device)
         return {"n_ticks": T, "actions": z(T, B, A, dtype=torch.uint8), "rewards": z(T, B, A, dtype=torch.float32),
                 "done": z(T, B, dtype=torch.bool), "truncated": z(T, B, dtype=torch.bool), "obs": z(T, B, S, dtype=torch.uint8),
-                "term_obs": z(T, B, S, dtype=torch.uint8), "roles": z(T, B, dtype=torch.int16)}
+                "term_obs": z(T, B, S, dtype=torch.uint8), "roles": z(T, B, dtype=torch.int16),
+                # one susnet_episode_info (16 bytes = 4 int32 words) per slot, written only where an episode ended: its info counters
+                "ep_info": z(T, B, 4, dtype=torch.int32)}
 
     def policy_tick_into(self, feed: Dict[str, torch.Tensor], t: int, net_imposter: "PackedQNet" = None, net_crew: "PackedQNet" = None,
                          q_imposter: Optional[torch.Tensor] = None, q_crew: Optional[torch.Tensor] = None, epsilon: float = 0.0,
                          mask_dead: bool = True, q_out: Optional[torch.Tensor] = None) -> None:
         """ONE tick of the trainer's acting loop (train.py:345-399: act on the current state, step, keep what ``replay_buffer.add``
         needs) written into slot ``t`` of ``feed``: the actions taken, rewards, done / truncated, the raw uint8 state after the step (after
-        the auto-reset where the episode ended), the true terminal state there, and the acting episode's roles.  The teams' Q rows come
+        the auto-reset where the episode ended), the true terminal state and the episode's info counters (``ep_info``) there, and the acting
+        episode's roles.  The teams' Q rows come
         from packed reference MLPs (``net_*``: the Q-network kernel reads the state itself) or from the caller (``q_*``).  With
         ``net_imposter`` alone on a compiled-in game and the production stream the whole tick is ONE kernel
         (``susnet_qnet_policy_step``: network, argmax / exploration, the random crew's draws, step, feed); else the network launch(es) +
@@ -699,6 +702,7 @@ class BatchedFourRoomEnv:
         io.actions, io.rewards = feed["actions"][t].data_ptr(), feed["rewards"][t].data_ptr()
         io.done, io.truncated = feed["done"][t].data_ptr(), feed["truncated"][t].data_ptr()
         io.term_obs, io.roles = feed["term_obs"][t].data_ptr(), feed["roles"][t].data_ptr()
+        io.ep_info = feed["ep_info"][t].data_ptr() if "ep_info" in feed else None
         one_kernel = (net_imposter is not None and q_imposter is None and q_crew is None and
                       self.supports_qnet_policy_step(net_imposter, net_crew, epsilon))
         opts = self._policy_opts(epsilon, mask_dead, net_crew if one_kernel else None)
@@ -731,6 +735,7 @@ class BatchedFourRoomEnv:
         io.actions, io.rewards = feed["actions"].data_ptr(), feed["rewards"].data_ptr()
         io.done, io.truncated = feed["done"].data_ptr(), feed["truncated"].data_ptr()
         io.obs, io.term_obs, io.roles = feed["obs"].data_ptr(), feed["term_obs"].data_ptr(), feed["roles"].data_ptr()
+        io.ep_info = feed["ep_info"].data_ptr() if "ep_info" in feed else None
         if q_out is not None:
             assert q_out.dtype == torch.float32 and tuple(q_out.shape) == (n_ticks, self.batch, net_imposter.dims[-1]) and q_out.is_contiguous()
             io.q = q_out.data_ptr()

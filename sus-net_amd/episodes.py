@@ -7,6 +7,10 @@ computed from the ``[T][B]`` feed block a collection leaves on the device (``Dev
 * numpy path: CPU tensors / arrays; the same rule in float64 with the same summation order, one tick at a time.
 
 Log order is tick-major, env-minor on both paths: what a host loop over ticks and environments would append.
+
+A feed that carries ``ep_info`` (``env.alloc_feed``: one ``susnet_episode_info`` per slot, written by the stepping kernels where an episode
+ends) also fills a second log, parallel to the first: the ``info`` counters of every logged episode -- what the reference's
+``metrics.step(info)`` appends at every episode end (src/train.py:419-427).
 """
 from __future__ import annotations
 
@@ -22,6 +26,14 @@ RECORD_DTYPE = np.dtype([("imposter_return", "<f8"), ("crew_return", "<f8"), ("t
                          ("ended_by", "<i4"), ("reserved", "<i4")])
 assert RECORD_DTYPE.itemsize == C.sizeof(L.EpisodeRecord)
 FIELDS = ("imposter_return", "crew_return", "length", "tick", "env", "ended_by")
+# susnet_episode_info (include/susnet.h): 16 bytes, four int32 words in a feed tensor
+INFO_DTYPE = np.dtype([("time_steps", "<u4"), ("completed_jobs", "<u4"), ("sabotaged_jobs", "<u4"), ("imp_killed_crew", "u1"),
+                       ("imp_voted_out", "u1"), ("crew_voted_out", "u1"), ("outcome", "u1")])
+assert INFO_DTYPE.itemsize == C.sizeof(L.EpisodeInfo) == 16
+# records() name (the reference's SusMetrics value) <- record field; the two outcome flags come from `outcome`
+INFO_FIELDS = {"imp_killed_crew": "imp_killed_crew", "imp_voted_out": "imp_voted_out", "crew_voted_out": "crew_voted_out",
+               "sabotaged_jobs": "sabotaged_jobs", "completed_jobs": "completed_jobs", "total_time_steps": "time_steps"}
+INFO_NAMES = tuple(INFO_FIELDS) + ("imposter_won", "crew_won")
 MIN_AGENTS, MAX_AGENTS = 2, 12
 
 
@@ -44,6 +56,28 @@ def numpy_order_mean(values) -> float:
     return s / n
 
 
+def info_records(x) -> np.ndarray:
+    """A feed's ``ep_info`` (``[T][B][4]`` int32 tensor / array, or an ``INFO_DTYPE`` array) as a host ``[T][B]`` array of ``INFO_DTYPE``."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype == INFO_DTYPE:
+        return x
+    if x.dtype.itemsize != 4 or x.shape[-1] != 4:
+        raise ValueError(f"ep_info must be [T, B, 4] of 32-bit words or an array of INFO_DTYPE, got {x.dtype} {x.shape}")
+    return np.ascontiguousarray(x).view(INFO_DTYPE).reshape(x.shape[:-1])
+
+
+def pack_info(time_steps, completed_jobs, sabotaged_jobs, imp_killed_crew, imp_voted_out, crew_voted_out, imposter_won, crew_won) -> np.ndarray:
+    """``INFO_DTYPE`` records from the counters of the reference's ``info`` dict (arrays of one shape): what the stepping kernels write."""
+    out = np.zeros(np.shape(time_steps), dtype=INFO_DTYPE)
+    out["time_steps"], out["completed_jobs"], out["sabotaged_jobs"] = time_steps, completed_jobs, sabotaged_jobs
+    out["imp_killed_crew"] = np.minimum(imp_killed_crew, 255)
+    out["imp_voted_out"], out["crew_voted_out"] = imp_voted_out, crew_voted_out
+    out["outcome"] = (np.asarray(crew_won) != 0) * L.OUTCOME_CREW_WON + (np.asarray(imposter_won) != 0) * L.OUTCOME_IMPOSTER_WON
+    return out
+
+
 def _host(x, dtype) -> np.ndarray:
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
@@ -55,8 +89,10 @@ class EpisodeLog:
     ``dropped`` counters, for one batched env -- or, without an env (``n_agents=, batch=``), for CPU feed arrays.
 
     ``update(feed, n_ticks, tick_base)`` consumes the first ``n_ticks`` slots of a feed block (``rewards [T][B][A] float32``, ``done`` /
-    ``truncated [T][B] bool``, ``roles [T][B] int16``: the imposter bitmask of the episode that acted); ``records()`` returns the log as
-    host arrays in log order.  Episodes that find the log full are counted in ``dropped``."""
+    ``truncated [T][B] bool``, ``roles [T][B] int16``: the imposter bitmask of the episode that acted; optionally ``ep_info [T][B][4]
+    int32``: the ended episodes' ``susnet_episode_info``); ``records()`` returns the log as host arrays in log order -- with ``ep_info``
+    feeds also the episodes' info counters (``INFO_NAMES``).  Episodes that find the log full are counted in ``dropped``.  A log takes
+    feeds with ``ep_info`` or without, not a mixture."""
 
     def __init__(self, env=None, gamma: float = 0.99, capacity: int = 1 << 20, n_agents: Optional[int] = None, batch: Optional[int] = None,
                  device=None):
@@ -70,6 +106,8 @@ class EpisodeLog:
         if self.batch < 1 or self.capacity < 0:
             raise ValueError("EpisodeLog: batch must be positive, capacity non-negative")
         self.ticks = 0  # lockstep ticks consumed so far: the default tick_base of the next update
+        self.has_info = None  # whether the feeds carry ep_info: fixed by the first update
+        self._info_log = None  # the parallel log of susnet_episode_info records, allocated with the first ep_info feed
         if self.device.type == "cuda":
             if env is None:
                 raise ValueError("EpisodeLog on a CUDA device needs the env whose feed it reads (the kernel takes its handle)")
@@ -99,6 +137,7 @@ class EpisodeLog:
                 self._count = self._dropped = 0
         if not keep_log:
             self.ticks = 0
+            self.has_info = None
 
     # ---- one feed block ----
     def update(self, feed: Dict[str, torch.Tensor], n_ticks: Optional[int] = None, tick_base: Optional[int] = None) -> None:
@@ -108,6 +147,12 @@ class EpisodeLog:
             raise ValueError(f"EpisodeLog.update: n_ticks = {n} outside 1 .. {feed['rewards'].shape[0]}")
         if tuple(feed["rewards"].shape[1:]) != (self.batch, self.n_agents):
             raise ValueError(f"EpisodeLog.update: rewards {tuple(feed['rewards'].shape)} is not [T, {self.batch}, {self.n_agents}]")
+        has_info = feed.get("ep_info") is not None
+        if self.has_info is None:
+            self.has_info = has_info
+        elif self.has_info != has_info:
+            raise ValueError("EpisodeLog.update: this log was started " + ("with" if self.has_info else "without") + " ep_info feeds; the two logs "
+                             "must stay parallel")
         if self.device.type == "cuda":
             self._update_hip(feed, n, base)
         else:
@@ -135,6 +180,13 @@ class EpisodeLog:
         io.log, io.capacity = self._log.data_ptr(), self.capacity
         io.count, io.dropped = self._counters.data_ptr(), self._counters.data_ptr() + 8
         io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 8
+        if self.has_info:
+            info = feed["ep_info"]
+            if info.dtype != torch.int32 or not info.is_contiguous() or info.device != self.device or tuple(info.shape) != tuple(rew.shape[:2]) + (4,):
+                raise ValueError(f"EpisodeLog.update: ep_info must be a contiguous int32 tensor [T, {self.batch}, 4] on {self.device}")
+            if self._info_log is None:
+                self._info_log = torch.zeros(max(self.capacity, 1), 4, dtype=torch.int32, device=self.device)
+            io.info, io.info_log = info.data_ptr(), self._info_log.data_ptr()
         with torch.cuda.device(self.device):
             L.check(env.lib.susnet_episode_stats(env._h, C.byref(io), env._stream()))
 
@@ -145,6 +197,13 @@ class EpisodeLog:
         roles = _host(feed["roles"], np.int16).astype(np.int64) & 0xFFFF
         gamma = np.float64(self.gamma)
         A = self.n_agents
+        info = None
+        if self.has_info:
+            info = info_records(feed["ep_info"])
+            if info.shape[1:] != (self.batch,) or info.shape[0] < n:
+                raise ValueError(f"EpisodeLog.update: ep_info {info.shape} is not [T, {self.batch}] records")
+            if self._info_log is None:
+                self._info_log = np.zeros(self.capacity, dtype=INFO_DTYPE)
         for t in range(n):
             self._G = rew[t].astype(np.float64) + gamma * self._G  # train.py:386 (numpy rounds the product, then the sum)
             for b in np.flatnonzero(ended_by[t]):
@@ -154,6 +213,8 @@ class EpisodeLog:
                     rec["imposter_return"] = numpy_order_mean(g[a] for a in range(A) if (mask >> a) & 1)
                     rec["crew_return"] = numpy_order_mean(g[a] for a in range(A) if not (mask >> a) & 1)
                     rec["tick"], rec["env"], rec["length"], rec["ended_by"] = base + t, b, self._t_episode[b] + 1, ended_by[t, b]
+                    if info is not None:
+                        self._info_log[self._count] = info[t, b]
                     self._count += 1
                 else:
                     self._dropped += 1
@@ -164,14 +225,26 @@ class EpisodeLog:
     # ---- reading the log (host synchronisation) ----
     def records(self) -> Dict[str, np.ndarray]:
         """The log in log order as host arrays ``imposter_return``, ``crew_return`` (float64), ``length``, ``tick``, ``env``, ``ended_by``,
-        plus the scalars ``count`` and ``dropped``.  Copies the used part of the log to the host."""
+        plus the scalars ``count`` and ``dropped``; a log fed with ``ep_info`` also returns the episodes' info counters under the reference's
+        names (``INFO_NAMES``: ``imp_killed_crew``, ``imp_voted_out``, ``crew_voted_out``, ``sabotaged_jobs``, ``completed_jobs``,
+        ``total_time_steps``, ``imposter_won``, ``crew_won``; int64).  Copies the used part of the log(s) to the host."""
+        info = None
         if self.device.type == "cuda":
             count, dropped = (int(v) for v in self._counters.cpu())
             words = RECORD_DTYPE.itemsize // 8
             raw = self._log[:count * words].cpu().numpy().view(RECORD_DTYPE)
+            if self.has_info:
+                info = self._info_log[:count].cpu().numpy().view(INFO_DTYPE).reshape(count)
         else:
             count, dropped, raw = self._count, self._dropped, self._host_log[:self._count]
+            if self.has_info:
+                info = self._info_log[:count]
         out = {k: raw[k].copy() for k in FIELDS}
+        if info is not None:
+            for name, field in INFO_FIELDS.items():
+                out[name] = info[field].astype(np.int64)
+            out["imposter_won"] = ((info["outcome"] & L.OUTCOME_IMPOSTER_WON) != 0).astype(np.int64)
+            out["crew_won"] = ((info["outcome"] & L.OUTCOME_CREW_WON) != 0).astype(np.int64)
         out["count"], out["dropped"] = count, dropped
         return out
 

@@ -80,21 +80,38 @@ def _save(models, directory: pathlib.Path, progress) -> None:
             model.dump_to_checkpoint(directory / checkpoint_name(team, model, progress))
 
 
-# the info counters the reference's handler keeps per episode (metrics.py:22-32 + the two outcome flags) <- the env's lifetime accumulators
+# the info counters the reference's handler keeps per episode (metrics.py:22-32 + the two outcome flags) <- EpisodeLog.records() arrays
+# (None: total_stalemates, which the reference never increments -- a zero per episode)
+_RECORD_OF = {SusMetrics.IMP_KILLED_CREW: "imp_killed_crew", SusMetrics.IMP_VOTED_OUT: "imp_voted_out", SusMetrics.CREW_VOTED_OUT: "crew_voted_out",
+              SusMetrics.SABOTAGED_JOBS: "sabotaged_jobs", SusMetrics.COMPLETED_JOBS: "completed_jobs", SusMetrics.TOTAL_STALEMATES: None,
+              SusMetrics.TOTAL_TIME_STEPS: "total_time_steps", SusMetrics.IMPOSTER_WON: "imposter_won", SusMetrics.CREW_WON: "crew_won"}
+
+
+# ... and <- the env's lifetime accumulators (the one-mean-per-counter form)
 _LIFETIME_OF = {SusMetrics.IMP_KILLED_CREW: "imp_killed_crew", SusMetrics.IMP_VOTED_OUT: "imp_voted_out", SusMetrics.CREW_VOTED_OUT: "crew_voted_out",
                 SusMetrics.SABOTAGED_JOBS: "sabotaged_jobs", SusMetrics.COMPLETED_JOBS: "completed_jobs", SusMetrics.TOTAL_STALEMATES: None,
                 SusMetrics.TOTAL_TIME_STEPS: "episode_steps", SusMetrics.IMPOSTER_WON: "imposter_won", SusMetrics.CREW_WON: "crew_won"}
 
 
+def info_metric_lists(rec, first_record: int = 0):
+    """``{SusMetrics: [one value per episode]}`` for the nine info counters from ``EpisodeLog.records()`` (a log fed with ``ep_info``), in
+    episode order: what the reference's handler holds after ``metrics.step(info)`` at every episode end (train.py:419-427)."""
+    n = len(rec["tick"]) - first_record
+    return {m: (rec[name][first_record:].tolist() if name else [0] * n) for m, name in _RECORD_OF.items()}
+
+
 def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: DeviceReplayBuffer, policy: PolicyRollout,
           trainer: DeviceDQNTeamTrainer, scheduler: ExponentialSchedule, save_directory_path, train_step_interval: int = 5,
           batch_size: int = 32, num_saves: int = 5, target_update_interval: int = 10_000, generator: Optional[torch.Generator] = None,
-          episode_log: Optional[EpisodeLog] = None) -> EpisodeLog:
+          episode_log: Optional[EpisodeLog] = None, per_episode_info: bool = False) -> EpisodeLog:
     """``train()`` of src/train.py:284-471.  ``num_steps`` counts lockstep ticks: each adds ``env.batch`` transitions.  ``policy``: the
     ``PolicyRollout`` the teams act by (reference MLPs the Q-network kernel serves; a crew model of None = random crew); ``trainer``: the
     ``DeviceDQNTeamTrainer`` over the same models (built with ``policy=policy``, so that acting follows the trained weights);
-    ``generator``: draws the replay samples.  ``metrics`` receives what the reference's handler holds after its ``train()``; the
-    ``EpisodeLog`` (returned) keeps tick, env, length and cause of every episode as well."""
+    ``generator``: draws the replay samples.  ``metrics`` receives what the reference's handler holds after its ``train()``: the teams'
+    returns with one entry per episode, the loss per train step, and the nine info counters -- with ``per_episode_info=True`` one entry
+    per episode, in episode order (what ``metrics.step(info)`` appends at every episode end, train.py:419-427; ``run_experiment`` asks for
+    it); by default ONE entry each, the mean per finished episode over the run.  The ``EpisodeLog`` (returned) keeps tick, env, length, cause
+    and info counters of every episode as well."""
     if not env.auto_reset:
         raise ValueError("train: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
     if policy.env is not env or trainer.env is not env:
@@ -115,7 +132,7 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
     else:  # a log that is carried through several runs: this run's episodes start behind what it holds
         first_record = episode_log.records()["count"]
         episode_log.reset(keep_log=True)
-    life0 = env.lifetime_totals().clone()
+    life0 = None if per_episode_info else env.lifetime_totals().clone()
     k_train = 0
     for blk in blocks:
         if trains:
@@ -132,16 +149,18 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
             k_train += 1
     _save(trainer.models, save_dir, "100%")  # train.py:453-457 (written whether or not anything trained, as there)
 
-    # ---- the only read-back: the episode log, the loss history, the lifetime totals ----
+    # ---- the only read-back: the episode log (records and info counters) and the loss history ----
     rec = episode_log.records()
-    life = (env.lifetime_totals() - life0).cpu().tolist()
     loss_rows = losses.cpu().tolist()
     metrics.set({SusMetrics.AVG_IMPOSTER_RETURNS: rec["imposter_return"][first_record:].tolist(),
                  SusMetrics.AVG_CREW_RETURNS: rec["crew_return"][first_record:].tolist()})
     metrics.set({SusMetrics.IMPOSTER_LOSS: [r[0] for r in loss_rows], SusMetrics.CREW_LOSS: [r[1] for r in loss_rows]})
-    # one entry per counter: its mean per finished episode over the run (per-episode histories would need the stepping kernels to emit them)
-    episodes = life[L.LIFETIME_NAMES.index("episodes")]
-    metrics.set({m: [(life[L.LIFETIME_NAMES.index(name)] / max(episodes, 1)) if name else 0.0] for m, name in _LIFETIME_OF.items()})
+    if per_episode_info:  # the stepping kernels emit the counters where an episode ends (feed["ep_info"])
+        metrics.set(info_metric_lists(rec, first_record))
+    else:  # one entry per counter: its mean per finished episode over the run, from the env's lifetime accumulators
+        life = (env.lifetime_totals() - life0).cpu().tolist()
+        episodes = life[L.LIFETIME_NAMES.index("episodes")]
+        metrics.set({m: [(life[L.LIFETIME_NAMES.index(name)] / max(episodes, 1)) if name else 0.0] for m, name in _LIFETIME_OF.items()})
     return episode_log
 
 
@@ -152,8 +171,8 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
                    generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: writes ``config.json``, builds ring, policy, trainer
-    and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()``, writes ``metrics.json`` and the
-    checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions."""
+    and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
+    entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions."""
     components = list(components)
     if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
         raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
@@ -186,6 +205,79 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
         ring.populate_fused(env, replay_prepopulate_steps)
     train(env, metrics, num_steps, ring, policy, trainer, scheduler, experiment_dir, train_step_interval=train_step_interval,
           batch_size=batch_size, num_saves=num_checkpoint_saves, target_update_interval=target_update_interval, generator=generator,
-          episode_log=episode_log)
+          episode_log=episode_log, per_episode_info=True)
     metrics.save_metrics(save_file_path=experiment_dir / "metrics.json")
     return metrics
+
+
+@torch.no_grad()
+def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, block_ticks: int = 64,
+             mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None) -> dict:
+    """How a pair of models plays: ``env.reset()``, then the acting loop for ``n_ticks`` lockstep ticks in blocks of ``block_ticks`` (one
+    policy rollout launch into a feed + one ``EpisodeLog.update`` per block; no ring, no trainer), and ONE read-back at the end.
+    ``crew_model=None``: a random crew.  Returns ``episodes``, ``imposter_win_rate``, ``crew_win_rate``, ``truncation_rate``,
+    ``mean_imposter_return``, ``mean_crew_return`` (``gamma``-discounted; 1.0 = plain sums), ``mean_length`` and the mean of every info
+    counter per finished episode (``mean_<counter>``), plus ``dropped`` (episodes beyond ``capacity``, not in the means) and ``ticks``.
+    Rates and means of zero episodes are NaN."""
+    if not env.auto_reset:
+        raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
+    components = list(components)
+    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead)
+    if policy.fused_imposter is None or (crew_model is not None and policy.fused_crew is None):
+        raise ValueError("evaluate: served are reference MLPs on a compiled-in feature layout; a crew model of None acts randomly")
+    if not env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon):
+        raise ValueError("evaluate: this env / model pair / epsilon is not served by the one-kernel policy tick (susnet_qnet_policy_step)")
+    n_ticks = int(n_ticks)
+    n_block = max(1, min(int(block_ticks), n_ticks))
+    fused = n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0
+    env.reset()
+    if capacity is None:  # an episode takes at least one tick
+        capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
+    log = EpisodeLog(env, gamma=gamma, capacity=capacity)
+    feed = env.alloc_feed(n_block)
+    t = 0
+    while t < n_ticks:
+        n = min(n_block, n_ticks - t)
+        if fused:
+            env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
+        else:
+            for k in range(n):
+                env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
+        log.update(feed, n, tick_base=t)
+        t += n
+    rec = log.records()
+    return summarize_episodes(rec, ticks=n_ticks)
+
+
+def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:
+    """The evaluation summary of ``EpisodeLog.records()`` (a log fed with ``ep_info``): see ``evaluate``."""
+    n = int(rec["count"])
+    mean = lambda x: float(np.mean(x)) if n else float("nan")
+    out = {"episodes": n, "dropped": int(rec["dropped"]), "imposter_win_rate": mean(rec["imposter_won"]), "crew_win_rate": mean(rec["crew_won"]),
+           "truncation_rate": mean((rec["ended_by"] & L.EPISODE_TRUNCATED) != 0), "mean_imposter_return": mean(rec["imposter_return"]),
+           "mean_crew_return": mean(rec["crew_return"]), "mean_length": mean(rec["length"])}
+    for m, name in _RECORD_OF.items():
+        if name and name not in ("imposter_won", "crew_won"):
+            out[f"mean_{m.value}"] = mean(rec[name])
+    if ticks is not None:
+        out["ticks"] = int(ticks)
+    return out
+
+
+def evaluate_checkpoints(experiment_dir, env, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, **kw) -> dict:
+    """``evaluate`` for every checkpoint pair ``imposter_mlp_<p>.pt`` / ``crew_mlp_<p>.pt`` that ``run_experiment`` wrote into
+    ``experiment_dir`` (a run without a crew model: the imposters against a random crew), as a table ``{<p>: summary}`` in the order of
+    training progress (``"0"``, ..., ``"100%"``)."""
+    d = pathlib.Path(experiment_dir)
+    found = {}
+    for path in d.glob("imposter_mlp_*.pt"):
+        found[path.stem[len("imposter_mlp_"):]] = path
+    if not found:
+        raise FileNotFoundError(f"evaluate_checkpoints: no imposter_mlp_<p>.pt under {d}")
+    table = {}
+    for p in sorted(found, key=lambda s: float(s.rstrip("%"))):
+        imp = MLP.load_from_checkpoint(found[p], map_location="cpu").to(env.device)
+        crew_path = d / f"crew_mlp_{p}.pt"
+        crew = MLP.load_from_checkpoint(crew_path, map_location="cpu").to(env.device) if crew_path.exists() else None
+        table[p] = evaluate(env, imp, crew, components, n_ticks, epsilon=epsilon, **kw)
+    return table
