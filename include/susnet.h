@@ -25,6 +25,8 @@
  *                          src/features/model_ready.py:41-57, 254-289, 338-354 (callers: src/train.py:345-347)
  *   susnet_scent           ImposterScentFeaturizer.extract_features   src/features/component.py:336-380
  *   susnet_dqn_train_step  DQNTeamTrainer.train_step on ReplayBuffer.sample's rows  src/train.py:50-149, src/replay_memory.py:75-94
+ *   susnet_dqn_train_sweep the same for several learners at once: the sweeps over run_experiment(**config) of
+ *                          notebooks/experiment_1v1.ipynb and notebooks/experiment_mlp.ipynb
  *   susnet_episode_stats   train()'s episode bookkeeping: G = reward + gamma * G, the teams' mean returns, episode lengths  src/train.py:385-450
  *   susnet_seed / _tick    np.random.seed(seed)            src/environment/base.py:126,267 (production stream)
  *   susnet_device_tick     (new) step counter in device memory: captured launches replay as a hipGraph
@@ -539,6 +541,25 @@ typedef struct susnet_dqn_io {
 } susnet_dqn_io;
 int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out);
 int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream);
+
+/* A sweep's train step.  The reference's users run sweeps: notebooks/experiment_1v1.ipynb and notebooks/experiment_mlp.ipynb build a
+ * list of configurations that differ in gamma ([0.99, 0.9, 0.8]) and call run_experiment(**config) for each -- the same game, the same
+ * MLP, sequence_length 1 -- and every one of them runs DQNTeamTrainer.train_step (src/train.py:50-149) on its own.  At the batch sizes
+ * they use one learner's step is a chain of launches of ONE workgroup each; this call runs the steps of n_learners independent
+ * learners of one shape in the SAME launches (the learner is the grid's second dimension): 1 launch to split the batches, 2 per
+ * (agent, enabled team) update and 1 per enabled team for the packed images, whatever n_learners is, all on `stream`, no host
+ * synchronisation, no parallel branches: a call can be captured in a hipGraph.
+ * ios[k] is a complete susnet_dqn_io as susnet_dqn_train_step takes it -- its own ring, indices, gamma, Adam constants, parameters,
+ * losses_out and its own workspace of susnet_dqn_workspace_bytes(envs[k], &ios[k]) bytes -- and passes that call's checks; the handles
+ * supply configuration only.  All learners agree on what the step's shape depends on: agent and imposter count, raw row size, grid and
+ * feature layout, `components`, `n`, and both teams' `enabled` and `dims`.  gamma, the Adam constants, every pointer and max_size may
+ * differ.  No two learners share `params` (of either team), `workspace` or `losses_out`.  Anything else returns SUSNET_E_INVALID
+ * with a message naming the first offending learner and field, before anything is launched.
+ * After the call every learner's params, exp_avg, exp_avg_sq, step, losses_out and packed hold BIT FOR BIT what
+ * susnet_dqn_train_step(envs[k], &ios[k], stream) would have left: workgroup (g, k) does what workgroup g of that call does, and every
+ * sum runs in the same order.  A learner whose (agent, team) list is empty skips that update (train.py:101) whatever the others do. */
+#define SUSNET_DQN_MAX_LEARNERS 16
+int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream);
 
 /* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
  * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.

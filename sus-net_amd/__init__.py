@@ -18,10 +18,10 @@ from .env import (  # noqa: F401,E402
 )
 from . import _lib, build_hip, dist, episodes, features, policy, replay, scheduler, train_loop, trainer  # noqa: F401,E402
 from .replay import Batch, DeviceReplayBuffer  # noqa: F401,E402
-from .trainer import DeviceDQNTeamTrainer, torch_train_step  # noqa: F401,E402
+from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer, torch_train_step  # noqa: F401,E402
 from .episodes import EpisodeLog  # noqa: F401,E402
 from .scheduler import ExponentialSchedule  # noqa: F401,E402
-from .train_loop import evaluate, evaluate_checkpoints, plan_blocks, run_experiment, train  # noqa: F401,E402
+from .train_loop import evaluate, evaluate_checkpoints, plan_blocks, run_experiment, run_sweep, train, train_sweep  # noqa: F401,E402
 from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout  # noqa: F401,E402
 from .features import FlatFeaturizer, GlobalFeaturizer, PerspectiveFeaturizer  # noqa: F401,E402
 

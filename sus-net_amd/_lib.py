@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("SUSNET_LIB_PATH", os.path.join(PKG_DIR, LIB_NAME))  #
 
 ABI_VERSION = 8
 MAX_AGENTS, MAX_JOBS, MAX_GRID, N_METRICS, N_LIFETIME = 16, 16, 16, 13, 12
+DQN_MAX_LEARNERS = 16  # SUSNET_DQN_MAX_LEARNERS
 
 VARIANT_BASE, VARIANT_ITG, VARIANT_TAGGING = 0, 1, 2
 RNG_TAPE, RNG_PHILOX = 1, 2
@@ -36,7 +37,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -230,6 +231,7 @@ def lib():
     L.susnet_scent.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     L.susnet_dqn_workspace_bytes.argtypes = [C.c_void_p, P(DqnIO), P(C.c_uint64)]
     L.susnet_dqn_train_step.argtypes = [C.c_void_p, P(DqnIO), C.c_void_p]
+    L.susnet_dqn_train_sweep.argtypes = [P(C.c_void_p), P(DqnIO), C.c_int32, C.c_void_p]
     L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]
     L.susnet_episode_stats.argtypes = [C.c_void_p, P(EpisodeIO), C.c_void_p]
     for name in EXPORTS:

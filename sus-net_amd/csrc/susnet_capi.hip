@@ -2275,10 +2275,8 @@ static int dqn_launch(const susnet_env *env, const susnet_dqn_io *io, const DqnP
     return SUSNET_OK;
 }
 
-extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream) {
-    if (int rc = check_bound(env)) return rc;
-    DqnPlan pl;
-    if (int rc = dqn_plan(env, io, pl)) return rc;
+// what susnet_dqn_train_step requires of one io beyond dqn_plan (the sweep asks the same of every learner)
+static int dqn_check_io(const susnet_dqn_io *io, const DqnPlan &pl) {
     if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
         return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: workspace missing, smaller than susnet_dqn_workspace_bytes or not 256-byte aligned");
     if (!io->states || !io->next_states || !io->actions || !io->rewards || !io->dones || !io->imposters || !io->losses_out || io->max_size < 1 ||
@@ -2289,11 +2287,127 @@ extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, v
         if (T.enabled && (!T.params || !T.target_params || !T.exp_avg || !T.exp_avg_sq || !T.step))
             return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: an enabled team needs params / target_params / exp_avg / exp_avg_sq / step");
     }
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream) {
+    if (int rc = check_bound(env)) return rc;
+    DqnPlan pl;
+    if (int rc = dqn_plan(env, io, pl)) return rc;
+    if (int rc = dqn_check_io(io, pl)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (pl.feat) {
     case FEAT_ONEHOT: return dqn_launch<QRow1>(env, io, pl, st);
     case FEAT_COORD: return dqn_launch<QRowC>(env, io, pl, st);
     default: return dqn_launch<QRow3>(env, io, pl, st);
+    }
+}
+
+// ---- a sweep's train step: K learners in the launches of one (susnet_train.h, k_train_sweep_*) ----
+template <class ROW>
+static int dqn_sweep_launch(susnet_env *const *envs, const susnet_dqn_io *ios, int K, const DqnPlan *pls, hipStream_t st) {
+    static std::atomic<uint64_t> lds_set{0}; // (as dqn_launch: the dynamic-LDS ceiling of this instantiation, once per device)
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(lds_set.load() & bit)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_train_sweep_grad<ROW>), hipFuncAttributeMaxDynamicSharedMemorySize, kTrLdsBytes));
+        lds_set.fetch_or(bit);
+    }
+    const susnet_env *env = envs[0];
+    const DqnPlan &pl = pls[0]; // dims, n and the agent count agree: every learner has this grid and these nets
+    const int64_t N = ios[0].n;
+    TrainSelTable sel{};
+    TrainTable tab[2] = {};
+    bool packs[2] = {false, false};
+    for (int k = 0; k < K; k++) {
+        const susnet_dqn_io &io = ios[k];
+        char *ws = static_cast<char *>(io.workspace);
+        int32_t *lists = reinterpret_cast<int32_t *>(ws + pls[k].off_lists), *counts = reinterpret_cast<int32_t *>(ws + pls[k].off_counts);
+        float *gacc[2] = {reinterpret_cast<float *>(ws + pls[k].off_gacc[0]), reinterpret_cast<float *>(ws + pls[k].off_gacc[1])};
+        const TrainRing ring{io.states, io.next_states, io.actions, io.rewards, io.dones, io.imposters, io.max_size,
+                             (int32_t)envs[k]->layout.obs_raw_size, (int32_t)envs[k]->c.A, (int32_t)envs[k]->c.n_imp};
+        sel.l[k] = TrainSelLearner{ring, io.indices, lists, counts, gacc[0], gacc[1], io.losses_out};
+        for (int tm = 0; tm < 2; tm++) {
+            const susnet_dqn_team &T = io.team[tm];
+            if (!T.enabled) continue;
+            tab[tm].l[k] = TrainLearner{ring, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, lists, counts, gacc[tm],
+                                        reinterpret_cast<float *>(ws + pls[k].off_partial), io.losses_out, T.packed,
+                                        T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
+            packs[tm] = packs[tm] || T.packed != nullptr;
+        }
+    }
+    const unsigned Ku = (unsigned)K;
+    hipLaunchKernelGGL(k_train_sweep_select, dim3(1, Ku), dim3(kTrThreads), kTrThreads * 4, st, sel, N, pl.net[0].P, pl.net[1].P);
+    HIP_TRY(hipGetLastError());
+    if (N == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            if (!ios[0].team[tm].enabled) continue;
+            hipLaunchKernelGGL(k_train_sweep_grad<ROW>, dim3((unsigned)pl.G, Ku), dim3(kTrThreads), kTrLdsBytes, st, tab[tm], pl.net[tm], N, agent, tm);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_train_sweep_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm], agent, tm,
+                               (int)pl.G);
+            HIP_TRY(hipGetLastError());
+        }
+    for (int tm = 0; tm < 2; tm++) {
+        if (!ios[0].team[tm].enabled || !packs[tm]) continue;
+        hipLaunchKernelGGL(k_train_sweep_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm]);
+        HIP_TRY(hipGetLastError());
+    }
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream) {
+    if (!envs || !ios) return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: null envs / ios");
+    if (n_learners < 1 || n_learners > SUSNET_DQN_MAX_LEARNERS)
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
+                                          std::to_string(SUSNET_DQN_MAX_LEARNERS));
+    const int K = n_learners;
+    auto who = [](int k, const std::string &what) { return "susnet_dqn_train_sweep: learner " + std::to_string(k) + ": " + what; };
+    DqnPlan pls[SUSNET_DQN_MAX_LEARNERS];
+    for (int k = 0; k < K; k++) { // each learner passes susnet_dqn_train_step's checks ...
+        int rc = check_bound(envs[k]);
+        if (!rc) rc = dqn_plan(envs[k], &ios[k], pls[k]);
+        if (!rc) rc = dqn_check_io(&ios[k], pls[k]);
+        if (rc) return fail(rc, who(k, g_err));
+    }
+    const susnet_env *e0 = envs[0];
+    const susnet_dqn_io &i0 = ios[0];
+    for (int k = 1; k < K; k++) { // ... and all agree on what shapes the step
+        const susnet_env *e = envs[k];
+        const susnet_dqn_io &io = ios[k];
+        const char *field = nullptr;
+        if (e->c.A != e0->c.A || e->c.n_imp != e0->c.n_imp) field = "agent count";
+        else if (e->layout.obs_raw_size != e0->layout.obs_raw_size) field = "raw row size";
+        else if (e->c.N != e0->c.N || memcmp(e->c.grid_rows, e0->c.grid_rows, sizeof(e0->c.grid_rows)) != 0) field = "grid";
+        else if (io.n_components != i0.n_components || memcmp(io.components, i0.components, sizeof(int32_t) * (size_t)i0.n_components) != 0)
+            field = "components";
+        else if (pls[k].feat != pls[0].feat) field = "feature layout";
+        else if (io.n != i0.n) field = "n";
+        for (int tm = 0; tm < 2 && !field; tm++) {
+            if ((io.team[tm].enabled != 0) != (i0.team[tm].enabled != 0)) field = tm ? "team[1].enabled" : "team[0].enabled";
+            else if (io.team[tm].enabled && (io.team[tm].n_dims != i0.team[tm].n_dims || memcmp(io.team[tm].dims, i0.team[tm].dims, sizeof(int32_t) * 6) != 0))
+                field = tm ? "team[1].dims" : "team[0].dims";
+        }
+        if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " differs from learner 0's (a sweep runs learners of one shape)"));
+    }
+    for (int k = 1; k < K; k++) // no two learners write the same memory
+        for (int j = 0; j < k; j++) {
+            const char *field = nullptr;
+            if (ios[k].workspace == ios[j].workspace) field = "workspace";
+            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
+            for (int a = 0; a < 2 && !field; a++)
+                for (int b = 0; b < 2 && !field; b++)
+                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
+                        field = a ? "team[1].params" : "team[0].params";
+            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
+        }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (pls[0].feat) {
+    case FEAT_ONEHOT: return dqn_sweep_launch<QRow1>(envs, ios, K, pls, st);
+    case FEAT_COORD: return dqn_sweep_launch<QRowC>(envs, ios, K, pls, st);
+    default: return dqn_sweep_launch<QRow3>(envs, ios, K, pls, st);
     }
 }
 

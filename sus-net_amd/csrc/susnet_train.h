@@ -23,6 +23,14 @@
 //   per team and step, one launch:
 //   k_train_pack     the team's packed image (susnet_qnet_pack's layout, susnet_capi.hip) from the updated parameters, element for element
 //                    the host's arithmetic (tail rows summed in its order): bitwise what the host packer makes.
+//
+// A sweep (susnet_dqn_train_sweep; the notebooks' loops over run_experiment(**config), notebooks/experiment_1v1.ipynb and
+// experiment_mlp.ipynb) trains K learners of one shape in the SAME launches: k_train_sweep_select / _grad / _adam / _pack take a table of
+// per-learner arguments by value (TrainTable, TrainSelTable) and the learner is blockIdx.y.  Each kernel body is ONE __device__ function
+// (tr_select / tr_grad / tr_adam / tr_pack) that both forms call, the single-learner kernel with its own arguments and the sweep kernel
+// with table.l[blockIdx.y]: workgroup (g, k) of a sweep does exactly what workgroup g of learner k's own call does -- same tiles, same
+// partial layout, same order of every sum -- so a learner's results are bitwise those of susnet_dqn_train_step.  Learners never touch
+// one another's memory: no waits between workgroups, no atomics.
 #pragma once
 
 #include "susnet_flat.h"
@@ -35,6 +43,7 @@ constexpr int kTrThreads = 512, kTrWaves = kTrThreads / 64, kTrTS = 32, kTrSP = 
 constexpr int kTrMaxF = 96;        // input width cap (the compiled-in layouts: 36, 4, 88)
 constexpr int kTrMaxTiles = 9;     // weight-gradient tiles per wave: (3 x 8 + 8 x 4 + 4 x 2 + 2 + 1 = 67) / 8 waves, rounded up
 constexpr int kTrMaxGrid = 256;    // workgroups of k_train_grad (one per CU)
+constexpr int kTrMaxLearners = SUSNET_DQN_MAX_LEARNERS; // learners of one sweep call (the tables travel as kernel arguments)
 
 // one team's network in torch's parameter order (MLP.parameters(): model.0.weight, model.0.bias, model.1.weight (PReLU), model.2.weight ...)
 struct TrainNet {
@@ -53,6 +62,32 @@ struct TrainRing {
     int64_t max_size;
     int32_t S, A, n_imp;
 };
+
+// ---- the sweep's tables: one entry per learner, passed by value ----
+struct TrainSelLearner { // k_train_sweep_select
+    TrainRing ring;
+    const int64_t *idx;
+    int32_t *lists, *counts;
+    float *gacc0, *gacc1, *losses;
+};
+struct TrainSelTable {
+    TrainSelLearner l[kTrMaxLearners];
+};
+struct TrainLearner { // one team of one learner: k_train_sweep_grad / _adam / _pack
+    TrainRing ring;
+    float *prm;
+    const float *tgt;
+    float *m1, *m2, *step;
+    const int32_t *lists, *counts;
+    float *gacc, *partial, *losses, *packed;
+    double lr, beta1, beta2, eps;
+    float gamma;
+    int32_t pad_;
+};
+struct TrainTable {
+    TrainLearner l[kTrMaxLearners];
+};
+static_assert(sizeof(TrainTable) + sizeof(TrainNet) + 64 <= 4096 && sizeof(TrainSelTable) + 64 <= 4096, "the tables are kernel arguments: 4 KB");
 
 // LDS (floats): activations transposed [unit][sample] with row stride kTrSP
 constexpr int kTrOX = 0, kTrOZ1 = kTrOX + kTrMaxF * kTrSP, kTrOZ2 = kTrOZ1 + 256 * kTrSP, kTrOZ3 = kTrOZ2 + 128 * kTrSP,
@@ -114,10 +149,9 @@ __device__ __forceinline__ void tr_backward_layer(const float *__restrict__ W, i
 // the team's rows of one agent: ring row ids, stable order
 __device__ __forceinline__ int32_t *tr_list(int32_t *lists, int64_t N, int agent, int team) { return lists + ((int64_t)agent * 2 + team) * N; }
 
-// ---- k_train_select: ONE workgroup of kTrThreads ----
-__global__ __launch_bounds__(kTrThreads) void k_train_select(TrainRing ring, const int64_t *__restrict__ idx, int64_t N, int32_t *lists, int32_t *counts,
-                                                             float *gacc0, int P0, float *gacc1, int P1, float *losses) {
-    extern __shared__ int32_t tr_scan[];
+// ---- k_train_select: ONE workgroup of kTrThreads (per learner) ----
+__device__ __forceinline__ void tr_select(const TrainRing &ring, const int64_t *__restrict__ idx, int64_t N, int32_t *lists, int32_t *counts, float *gacc0,
+                                          int P0, float *gacc1, int P1, float *losses, int32_t *tr_scan) {
     const int t = threadIdx.x;
     for (int p = t; p < P0; p += kTrThreads) gacc0[p] = 0.0f;
     for (int p = t; p < P1; p += kTrThreads) gacc1[p] = 0.0f;
@@ -154,6 +188,16 @@ __global__ __launch_bounds__(kTrThreads) void k_train_select(TrainRing ring, con
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(kTrThreads) void k_train_select(TrainRing ring, const int64_t *__restrict__ idx, int64_t N, int32_t *lists, int32_t *counts,
+                                                             float *gacc0, int P0, float *gacc1, int P1, float *losses) {
+    extern __shared__ int32_t tr_scan[];
+    tr_select(ring, idx, N, lists, counts, gacc0, P0, gacc1, P1, losses, tr_scan);
+}
+__global__ __launch_bounds__(kTrThreads) void k_train_sweep_select(TrainSelTable tab, int64_t N, int P0, int P1) {
+    extern __shared__ int32_t tr_scan[];
+    const TrainSelLearner &a = tab.l[blockIdx.y];
+    tr_select(a.ring, a.idx, N, a.lists, a.counts, a.gacc0, P0, a.gacc1, P1, a.losses, tr_scan);
 }
 
 // the tile's feature rows X[k][s] (k < F) from flattened states (base.py:234-235: positions, then alive flags)
@@ -209,12 +253,11 @@ __device__ __forceinline__ void tr_forward(const TrainNet &net, const float *__r
     }
 }
 
-// ---- k_train_grad: one (agent, team) update's gradient partials ----
+// ---- k_train_grad: one (agent, team) update's gradient partials; workgroup blockIdx.x of gridDim.x ----
 template <class ROW>
-__global__ __launch_bounds__(kTrThreads) void k_train_grad(TrainRing ring, TrainNet net, const float *__restrict__ prm, const float *__restrict__ tgt,
-                                                           const int32_t *__restrict__ lists, const int32_t *__restrict__ counts, int64_t N, int agent,
-                                                           int team, float gamma, float *__restrict__ partial, float *step) {
-    extern __shared__ float lds[];
+__device__ __forceinline__ void tr_grad(const TrainRing &ring, const TrainNet &net, const float *__restrict__ prm, const float *__restrict__ tgt,
+                                        const int32_t *__restrict__ lists, const int32_t *__restrict__ counts, int64_t N, int agent, int team, float gamma,
+                                        float *__restrict__ partial, float *step, float *lds) {
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int count = counts[2 * agent + team];
@@ -352,11 +395,24 @@ __global__ __launch_bounds__(kTrThreads) void k_train_grad(TrainRing ring, Train
         __syncthreads();
     }
 }
+template <class ROW>
+__global__ __launch_bounds__(kTrThreads) void k_train_grad(TrainRing ring, TrainNet net, const float *__restrict__ prm, const float *__restrict__ tgt,
+                                                           const int32_t *__restrict__ lists, const int32_t *__restrict__ counts, int64_t N, int agent,
+                                                           int team, float gamma, float *__restrict__ partial, float *step) {
+    extern __shared__ float lds[];
+    tr_grad<ROW>(ring, net, prm, tgt, lists, counts, N, agent, team, gamma, partial, step, lds);
+}
+template <class ROW>
+__global__ __launch_bounds__(kTrThreads) void k_train_sweep_grad(TrainTable tab, TrainNet net, int64_t N, int agent, int team) {
+    extern __shared__ float lds[];
+    const TrainLearner &a = tab.l[blockIdx.y];
+    tr_grad<ROW>(a.ring, net, a.prm, a.tgt, a.lists, a.counts, N, agent, team, a.gamma, a.partial, a.step, lds);
+}
 
 // ---- k_train_adam: thread per parameter ----
-__global__ __launch_bounds__(256) void k_train_adam(TrainNet net, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial,
-                                                    int G, float *__restrict__ gacc, float *__restrict__ prm, float *__restrict__ m1, float *__restrict__ m2,
-                                                    const float *__restrict__ step, double lr, double beta1, double beta2, double eps, float *losses) {
+__device__ __forceinline__ void tr_adam(const TrainNet &net, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial, int G,
+                                        float *__restrict__ gacc, float *__restrict__ prm, float *__restrict__ m1, float *__restrict__ m2,
+                                        const float *__restrict__ step, double lr, double beta1, double beta2, double eps, float *losses) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const int count = counts[2 * agent + team];
     if (count == 0 || p > net.P) return; // an empty team takes no step (train.py:101)
@@ -382,10 +438,19 @@ __global__ __launch_bounds__(256) void k_train_adam(TrainNet net, const int32_t 
     const float denom = sqrtf(v) / bc2s + (float)eps;
     prm[p] = prm[p] + (-step_size) * (m / denom);
 }
+__global__ __launch_bounds__(256) void k_train_adam(TrainNet net, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial,
+                                                    int G, float *__restrict__ gacc, float *__restrict__ prm, float *__restrict__ m1, float *__restrict__ m2,
+                                                    const float *__restrict__ step, double lr, double beta1, double beta2, double eps, float *losses) {
+    tr_adam(net, counts, agent, team, partial, G, gacc, prm, m1, m2, step, lr, beta1, beta2, eps, losses);
+}
+__global__ __launch_bounds__(256) void k_train_sweep_adam(TrainTable tab, TrainNet net, int agent, int team, int G) {
+    const TrainLearner &a = tab.l[blockIdx.y];
+    tr_adam(net, a.counts, agent, team, a.partial, G, a.gacc, a.prm, a.m1, a.m2, a.step, a.lr, a.beta1, a.beta2, a.eps, a.losses);
+}
 
 // ---- k_train_pack: the team's packed image from torch-layout parameters (susnet_capi.hip qnet_pack, element for element) ----
 template <class ROW>
-__global__ __launch_bounds__(256) void k_train_pack(TrainNet net, const float *__restrict__ prm, float *__restrict__ out) {
+__device__ __forceinline__ void tr_pack(const TrainNet &net, const float *__restrict__ prm, float *__restrict__ out) {
     using Q = QNet<ROW>;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Q::kPacked) return;
@@ -428,6 +493,15 @@ __global__ __launch_bounds__(256) void k_train_pack(TrainNet net, const float *_
         v = prm[net.oA[i - Q::oSlope]];
     }
     out[i] = v;
+}
+template <class ROW>
+__global__ __launch_bounds__(256) void k_train_pack(TrainNet net, const float *__restrict__ prm, float *__restrict__ out) {
+    tr_pack<ROW>(net, prm, out);
+}
+template <class ROW>
+__global__ __launch_bounds__(256) void k_train_sweep_pack(TrainTable tab, TrainNet net) { // (a learner without a packed image: nothing to write)
+    const TrainLearner &a = tab.l[blockIdx.y];
+    if (a.packed) tr_pack<ROW>(net, a.prm, a.packed);
 }
 
 } // namespace susnet

@@ -30,7 +30,7 @@ from .metrics import EpisodicMetricHandler, SusMetrics
 from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN
 from .replay import DeviceReplayBuffer
 from .scheduler import ExponentialSchedule
-from .trainer import DeviceDQNTeamTrainer
+from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer
 
 Block = namedtuple("Block", ("t0", "n_ticks", "sync_ticks", "save_ticks", "trains"))
 Block.__doc__ = """Ticks ``t0 .. t0 + n_ticks - 1``; ``sync_ticks`` / ``save_ticks``: the ticks inside the block at which the reference syncs the
@@ -100,6 +100,78 @@ def info_metric_lists(rec, first_record: int = 0):
     return {m: (rec[name][first_record:].tolist() if name else [0] * n) for m, name in _RECORD_OF.items()}
 
 
+class _Run:
+    """One learner's side of the block loop: what ``train()`` does around the train step.  ``train()`` drives one of these,
+    ``train_sweep()`` several in lockstep -- the same methods in the same order per member."""
+
+    def __init__(self, who, env, metrics, num_steps, replay_buffer, policy, trainer, scheduler, save_directory_path, blocks, generator=None,
+                 episode_log=None, per_episode_info=False):
+        if not env.auto_reset:
+            raise ValueError(f"{who}: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
+        if policy.env is not env or trainer.env is not env:
+            raise ValueError(f"{who}: policy and trainer must be built over the env that is trained on")
+        if policy.fused_imposter is None or (policy.crew_model is not None and policy.fused_crew is None):
+            raise ValueError(f"{who}: served are reference MLPs on a compiled-in feature layout (PolicyRollout.fused_imposter / fused_crew); "
+                             "a crew model of None acts randomly")
+        self.env, self.metrics, self.num_steps, self.ring, self.policy, self.trainer = env, metrics, num_steps, replay_buffer, policy, trainer
+        self.scheduler, self.generator, self.per_episode_info = scheduler, generator, per_episode_info
+        self.save_dir = pathlib.Path(save_directory_path)
+        self.trains = any(trainer.trained)
+        self.losses = torch.zeros(sum(b.trains for b in blocks), 2, dtype=torch.float32, device=env.device)
+        self.save_dir.mkdir(parents=True, exist_ok=True)
+
+        env.reset()  # train.py:316
+        self.first_record = 0
+        if episode_log is None:
+            episode_log = EpisodeLog(env, gamma=trainer.gamma)
+        else:  # a log that is carried through several runs: this run's episodes start behind what it holds
+            self.first_record = episode_log.records()["count"]
+            episode_log.reset(keep_log=True)
+        self.episode_log = episode_log
+        self.life0 = None if per_episode_info else env.lifetime_totals().clone()
+
+    def before_train_step(self, blk: Block) -> None:
+        """The block up to its train step: checkpoints and target sync due inside it, the collect, the episode bookkeeping."""
+        if self.trains:
+            for t in blk.save_ticks:  # train.py:331-338
+                _save(self.trainer.models, self.save_dir, int(t * 100 / self.num_steps))
+        if blk.sync_ticks:  # train.py:341-343
+            self.trainer.sync_targets()
+        self.ring.collect(self.env, self.policy, blk.n_ticks, epsilon=float(self.scheduler.value(blk.t0)), ticks_per_append=blk.n_ticks)
+        feed, n = self.ring.last_feed
+        self.episode_log.update(feed, n, tick_base=blk.t0)  # (`tick` counts from this run's first tick, also in a log carried over)
+
+    def finish(self) -> EpisodeLog:
+        env, metrics, first_record = self.env, self.metrics, self.first_record
+        _save(self.trainer.models, self.save_dir, "100%")  # train.py:453-457 (written whether or not anything trained, as there)
+        # ---- the only read-back: the episode log (records and info counters) and the loss history ----
+        rec = self.episode_log.records()
+        loss_rows = self.losses.cpu().tolist()
+        metrics.set({SusMetrics.AVG_IMPOSTER_RETURNS: rec["imposter_return"][first_record:].tolist(),
+                     SusMetrics.AVG_CREW_RETURNS: rec["crew_return"][first_record:].tolist()})
+        metrics.set({SusMetrics.IMPOSTER_LOSS: [r[0] for r in loss_rows], SusMetrics.CREW_LOSS: [r[1] for r in loss_rows]})
+        if self.per_episode_info:  # the stepping kernels emit the counters where an episode ends (feed["ep_info"])
+            metrics.set(info_metric_lists(rec, first_record))
+        else:  # one entry per counter: its mean per finished episode over the run, from the env's lifetime accumulators
+            life = (env.lifetime_totals() - self.life0).cpu().tolist()
+            episodes = life[L.LIFETIME_NAMES.index("episodes")]
+            metrics.set({m: [(life[L.LIFETIME_NAMES.index(name)] / max(episodes, 1)) if name else 0.0] for m, name in _LIFETIME_OF.items()})
+        return self.episode_log
+
+
+def _run_blocks(runs: List[_Run], blocks: List[Block], train_step) -> List[EpisodeLog]:
+    """THE block loop: per block every run's ``before_train_step``, then -- where the block ends on a train tick -- ``train_step(k)``, which
+    writes row ``k`` of the training runs' loss histories."""
+    k_train = 0
+    for blk in blocks:
+        for run in runs:
+            run.before_train_step(blk)
+        if blk.trains:  # train.py:402-416
+            train_step(k_train)
+            k_train += 1
+    return [run.finish() for run in runs]
+
+
 def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: DeviceReplayBuffer, policy: PolicyRollout,
           trainer: DeviceDQNTeamTrainer, scheduler: ExponentialSchedule, save_directory_path, train_step_interval: int = 5,
           batch_size: int = 32, num_saves: int = 5, target_update_interval: int = 10_000, generator: Optional[torch.Generator] = None,
@@ -112,56 +184,62 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
     per episode, in episode order (what ``metrics.step(info)`` appends at every episode end, train.py:419-427; ``run_experiment`` asks for
     it); by default ONE entry each, the mean per finished episode over the run.  The ``EpisodeLog`` (returned) keeps tick, env, length, cause
     and info counters of every episode as well."""
-    if not env.auto_reset:
-        raise ValueError("train: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
-    if policy.env is not env or trainer.env is not env:
-        raise ValueError("train: policy and trainer must be built over the env that is trained on")
-    if policy.fused_imposter is None or (policy.crew_model is not None and policy.fused_crew is None):
-        raise ValueError("train: served are reference MLPs on a compiled-in feature layout (PolicyRollout.fused_imposter / fused_crew); "
-                         "a crew model of None acts randomly")
-    save_dir = pathlib.Path(save_directory_path)
-    trains = any(trainer.trained)
     blocks = plan_blocks(num_steps, train_step_interval, target_update_interval, num_saves)
-    losses = torch.zeros(sum(b.trains for b in blocks), 2, dtype=torch.float32, device=env.device)
-    save_dir.mkdir(parents=True, exist_ok=True)
+    run = _Run("train", env, metrics, num_steps, replay_buffer, policy, trainer, scheduler, save_directory_path, blocks, generator, episode_log,
+               per_episode_info)
 
-    env.reset()  # train.py:316
-    first_record = 0
-    if episode_log is None:
-        episode_log = EpisodeLog(env, gamma=trainer.gamma)
-    else:  # a log that is carried through several runs: this run's episodes start behind what it holds
-        first_record = episode_log.records()["count"]
-        episode_log.reset(keep_log=True)
-    life0 = None if per_episode_info else env.lifetime_totals().clone()
-    k_train = 0
-    for blk in blocks:
-        if trains:
-            for t in blk.save_ticks:  # train.py:331-338
-                _save(trainer.models, save_dir, int(t * 100 / num_steps))
-        if blk.sync_ticks:  # train.py:341-343
-            trainer.sync_targets()
-        replay_buffer.collect(env, policy, blk.n_ticks, epsilon=float(scheduler.value(blk.t0)), ticks_per_append=blk.n_ticks)
-        feed, n = replay_buffer.last_feed
-        episode_log.update(feed, n, tick_base=blk.t0)  # (`tick` counts from this run's first tick, also in a log carried over)
-        if blk.trains:  # train.py:402-416
-            if trains:
-                losses[k_train].copy_(trainer.train_step(replay_buffer, batch_size, generator))
-            k_train += 1
-    _save(trainer.models, save_dir, "100%")  # train.py:453-457 (written whether or not anything trained, as there)
+    def train_step(k):
+        if run.trains:
+            run.losses[k].copy_(trainer.train_step(replay_buffer, batch_size, generator))
 
-    # ---- the only read-back: the episode log (records and info counters) and the loss history ----
-    rec = episode_log.records()
-    loss_rows = losses.cpu().tolist()
-    metrics.set({SusMetrics.AVG_IMPOSTER_RETURNS: rec["imposter_return"][first_record:].tolist(),
-                 SusMetrics.AVG_CREW_RETURNS: rec["crew_return"][first_record:].tolist()})
-    metrics.set({SusMetrics.IMPOSTER_LOSS: [r[0] for r in loss_rows], SusMetrics.CREW_LOSS: [r[1] for r in loss_rows]})
-    if per_episode_info:  # the stepping kernels emit the counters where an episode ends (feed["ep_info"])
-        metrics.set(info_metric_lists(rec, first_record))
-    else:  # one entry per counter: its mean per finished episode over the run, from the env's lifetime accumulators
-        life = (env.lifetime_totals() - life0).cpu().tolist()
-        episodes = life[L.LIFETIME_NAMES.index("episodes")]
-        metrics.set({m: [(life[L.LIFETIME_NAMES.index(name)] / max(episodes, 1)) if name else 0.0] for m, name in _LIFETIME_OF.items()})
-    return episode_log
+    return _run_blocks([run], blocks, train_step)[0]
+
+
+def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_size: int = 32, num_saves: int = 5,
+                target_update_interval: int = 10_000, per_episode_info: bool = False) -> List[EpisodeLog]:
+    """``train()`` for the members of a sweep in lockstep -- the reference's loop over ``run_experiment(**config)``
+    (notebooks/experiment_1v1.ipynb, notebooks/experiment_mlp.ipynb) with the runs side by side.  ``members``: one
+    ``(env, metrics, replay_buffer, policy, trainer, scheduler, save_directory_path, generator)`` per run, each with its own env, ring,
+    models and generator.  Per block every member first does what ``train()`` does before the train step -- its saves, its target sync,
+    its ``collect`` at its own epsilon, its ``EpisodeLog.update`` -- then ONE ``DeviceDQNSweepTrainer.train_step`` steps all members
+    (``susnet_dqn_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
+    ``batch_size``, ``num_saves``, ``target_update_interval``) is shared.  Each member's metrics, losses, checkpoints and ``EpisodeLog``
+    (returned, in member order) are what ``train()`` alone produces for it: its step is bitwise its own, and its random streams are
+    its own (give every member a generator: without one the draws come from the device's global generator, in member order)."""
+    members = [tuple(m) for m in members]
+    if not members:
+        raise ValueError("train_sweep: no members")
+    if len(set(id(m[0]) for m in members)) != len(members) or len(set(id(m[2]) for m in members)) != len(members):
+        raise ValueError("train_sweep: every member needs its own env and its own replay buffer")
+    blocks = plan_blocks(num_steps, train_step_interval, target_update_interval, num_saves)
+    runs = [_Run(f"train_sweep: member {k}", env, metrics, num_steps, ring, policy, trainer, scheduler, save_dir, blocks, generator, None,
+                 per_episode_info)
+            for k, (env, metrics, ring, policy, trainer, scheduler, save_dir, generator) in enumerate(members)]
+    training = [run for run in runs if run.trains]  # (a member with no trained team takes no step and draws no sample, as in train())
+    sweep = DeviceDQNSweepTrainer([run.trainer for run in training]) if training else None
+
+    def train_step(k):
+        if sweep is not None:
+            out = sweep.train_step([run.ring for run in training], batch_size, [run.generator for run in training])
+            for j, run in enumerate(training):
+                run.losses[k].copy_(out[j])
+
+    return _run_blocks(runs, blocks, train_step)
+
+
+def _experiment_config(env, imposter_model, crew_model, components, base, *, num_steps, sequence_length, replay_buffer_size,
+                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter,
+                       train_crew, learning_rate, train_step_interval, target_update_interval) -> dict:
+    """What ``run_experiment`` writes into ``config.json`` (train.py:185-211), in its key order."""
+    return {
+        "num_steps": num_steps, "batch": env.batch, "imposter_model_args": getattr(imposter_model, "config", None),
+        "crew_model_args": getattr(crew_model, "config", None), "imposter_model_type": model_type(imposter_model),
+        "crew_model_type": model_type(crew_model), "featurizer_type": "flat:" + "+".join(components), "sequence_length": sequence_length,
+        "replay_buffer_size": replay_buffer_size, "replay_prepopulate_steps": replay_prepopulate_steps, "batch_size": batch_size, "gamma": gamma,
+        "scheduler_start_eps": scheduler_start_eps, "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps,
+        "train_imposter": train_imposter, "train_crew": train_crew, "experiment_base_dir": str(base), "optimizer_type": "adam",
+        "learning_rate": learning_rate, "train_step_interval": train_step_interval, "target_update_interval": target_update_interval,
+    }
 
 
 def run_experiment(env, num_steps: int, imposter_model, crew_model, components: Sequence[str], sequence_length: int = 1,
@@ -184,15 +262,11 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
     experiment_dir = base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     experiment_dir.mkdir(parents=True, exist_ok=True)
-    config = {
-        "num_steps": num_steps, "batch": env.batch, "imposter_model_args": getattr(imposter_model, "config", None),
-        "crew_model_args": getattr(crew_model, "config", None), "imposter_model_type": model_type(imposter_model),
-        "crew_model_type": model_type(crew_model), "featurizer_type": "flat:" + "+".join(components), "sequence_length": sequence_length,
-        "replay_buffer_size": replay_buffer_size, "replay_prepopulate_steps": replay_prepopulate_steps, "batch_size": batch_size, "gamma": gamma,
-        "scheduler_start_eps": scheduler_start_eps, "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps,
-        "train_imposter": train_imposter, "train_crew": train_crew, "experiment_base_dir": str(base), "optimizer_type": "adam",
-        "learning_rate": learning_rate, "train_step_interval": train_step_interval, "target_update_interval": target_update_interval,
-    }
+    config = _experiment_config(env, imposter_model, crew_model, components, base, num_steps=num_steps, sequence_length=sequence_length,
+                                replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
+                                gamma=gamma, scheduler_start_eps=scheduler_start_eps, scheduler_end_eps=scheduler_end_eps,
+                                scheduler_time_steps=scheduler_time_steps, train_imposter=train_imposter, train_crew=train_crew,
+                                learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval)
     (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
 
     policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True)
@@ -208,6 +282,93 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
           episode_log=episode_log, per_episode_info=True)
     metrics.save_metrics(save_file_path=experiment_dir / "metrics.json")
     return metrics
+
+
+SWEEP_VARIANT_KEYS = ("gamma", "learning_rate", "seed", "scheduler_start_eps", "scheduler_end_eps", "scheduler_time_steps", "name")
+
+
+def check_variants(variants) -> List[dict]:
+    """The variants of ``run_sweep`` as a list of dicts; ``ValueError`` for an empty list or a key outside ``SWEEP_VARIANT_KEYS`` (every
+    other setting is shared by the members by construction)."""
+    variants = [dict(v) for v in variants]
+    if not variants:
+        raise ValueError("run_sweep: no variants")
+    for k, v in enumerate(variants):
+        unknown = sorted(set(v) - set(SWEEP_VARIANT_KEYS))
+        if unknown:
+            raise ValueError(f"run_sweep: variant {k} has {unknown}; a variant may set {list(SWEEP_VARIANT_KEYS)}, everything else is shared")
+    return variants
+
+
+def sweep_member_dirs(base, variants, timestamp: str) -> List[pathlib.Path]:
+    """``base/<name or index>/<timestamp>/`` per variant: one reference-shaped experiment directory each (train.py:181-182)."""
+    names = [str(v.get("name", k)) for k, v in enumerate(variants)]
+    if len(set(names)) != len(names):
+        raise ValueError(f"run_sweep: member directory names repeat: {names}")
+    return [pathlib.Path(base) / n / timestamp for n in names]
+
+
+def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, crew_model_factory, components: Sequence[str],
+              sequence_length: int = 1, replay_buffer_size: int = 100_000, replay_prepopulate_steps: int = 1000, batch_size: int = 32,
+              gamma: float = 0.99, scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
+              train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
+              train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
+              seed: int = 0) -> List[EpisodicMetricHandler]:
+    """The reference's sweeps -- ``for config in configs: run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
+    notebooks/experiment_mlp.ipynb: gamma 0.99 / 0.9 / 0.8 on one game and one MLP) -- as ONE run: the members collect one after another
+    and take their train steps together (``train_sweep``).  The shared arguments are ``run_experiment``'s.  ``variants``: one dict per
+    member with any of ``gamma``, ``learning_rate``, ``seed``, ``scheduler_start_eps``, ``scheduler_end_eps``, ``scheduler_time_steps``,
+    ``name`` (anything else: ``ValueError``); a key left out takes the shared value.  ``env_factory(seed)`` builds a member's env
+    (``obs=ObsConfig('flat', components), auto_reset=True``); ``imposter_model_factory(env)`` / ``crew_model_factory(env)`` its MLPs
+    (``crew_model_factory=None``: random crews) under ``torch.manual_seed(seed)``; the member's sample generator is seeded with ``seed``
+    too.  Each member gets ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values),
+    the checkpoints and ``metrics.json`` exactly as ``run_experiment`` writes them, so plotting over one directory per gamma keeps
+    working.  Returns the members' metric handlers."""
+    components = list(components)
+    variants = check_variants(variants)
+    if sequence_length != 1:
+        raise ValueError("run_sweep: a window of one state is served (sequence_length=1): the Q-network kernel and "
+                         "susnet_dqn_train_sweep read one state")
+    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
+    dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+    shared = {"gamma": gamma, "learning_rate": learning_rate, "seed": seed, "scheduler_start_eps": scheduler_start_eps,
+              "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps}
+    members, handlers = [], []
+    for k, (variant, experiment_dir) in enumerate(zip(variants, dirs)):
+        v = {**shared, **{key: val for key, val in variant.items() if key != "name"}}
+        env = env_factory(int(v["seed"]))
+        if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
+            raise ValueError("run_sweep: env_factory must build the env with obs=ObsConfig('flat', components), auto_reset=True")
+        torch.manual_seed(int(v["seed"]))
+        imposter_model = imposter_model_factory(env)
+        crew_model = crew_model_factory(env) if crew_model_factory is not None else None
+        if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
+            raise ValueError("run_sweep: served are reference MLPs (a crew model of None acts randomly)")
+        experiment_dir.mkdir(parents=True, exist_ok=True)
+        config = _experiment_config(env, imposter_model, crew_model, components, base, num_steps=num_steps, sequence_length=sequence_length,
+                                    replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
+                                    gamma=v["gamma"], scheduler_start_eps=v["scheduler_start_eps"], scheduler_end_eps=v["scheduler_end_eps"],
+                                    scheduler_time_steps=v["scheduler_time_steps"], train_imposter=train_imposter, train_crew=train_crew,
+                                    learning_rate=v["learning_rate"], train_step_interval=train_step_interval,
+                                    target_update_interval=target_update_interval)
+        config["seed"] = v["seed"]
+        (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
+        policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True)
+        trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=v["learning_rate"], gamma=v["gamma"],
+                                       train_imposter=train_imposter, train_crew=train_crew, policy=policy)
+        scheduler = ExponentialSchedule(v["scheduler_start_eps"], v["scheduler_end_eps"], v["scheduler_time_steps"])
+        ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
+        if replay_prepopulate_steps > 0:
+            ring.populate_fused(env, replay_prepopulate_steps)
+        generator = torch.Generator(device=env.device)
+        generator.manual_seed(int(v["seed"]))
+        handlers.append(EpisodicMetricHandler())
+        members.append((env, handlers[-1], ring, policy, trainer, scheduler, experiment_dir, generator))
+    train_sweep(members, num_steps, train_step_interval=train_step_interval, batch_size=batch_size, num_saves=num_checkpoint_saves,
+                target_update_interval=target_update_interval, per_episode_info=True)
+    for handler, experiment_dir in zip(handlers, dirs):
+        handler.save_metrics(save_file_path=experiment_dir / "metrics.json")
+    return handlers
 
 
 @torch.no_grad()

@@ -194,7 +194,8 @@ class DeviceDQNTeamTrainer:
             return self._hip_step(ring, idx)
         return self._torch_step(ring, idx)
 
-    def _hip_step(self, ring, idx):
+    def _hip_io(self, ring, idx) -> "L.DqnIO":
+        """The complete ``susnet_dqn_io`` of one step on ``ring`` at ``idx``: Adam state in the flat buffers, workspace and losses allocated."""
         env = self.env
         for t in range(2):
             self._state_to_flat(t)
@@ -207,6 +208,11 @@ class DeviceDQNTeamTrainer:
             self._losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
         io.losses_out = self._losses.data_ptr()
+        return io
+
+    def _hip_step(self, ring, idx):
+        env = self.env
+        io = self._hip_io(ring, idx)
         with torch.cuda.device(self.device):
             L.check(env.lib.susnet_dqn_train_step(env._h, C.byref(io), env._stream()))
         self._sync_policy_version()
@@ -312,3 +318,87 @@ class DeviceDQNTeamTrainer:
                 self.target_flat[t].copy_(self.flat[t])
             else:
                 self.targets[t].load_state_dict(self.models[t].state_dict())
+
+
+def sweep_chunks(n_members: int, limit: int = L.DQN_MAX_LEARNERS):
+    """``[(lo, hi), ...]``: the members of a sweep in order, in calls of at most ``limit`` (``SUSNET_DQN_MAX_LEARNERS``) learners."""
+    return [(lo, min(lo + limit, n_members)) for lo in range(0, n_members, limit)]
+
+
+class DeviceDQNSweepTrainer:
+    """The train steps of a sweep -- the reference's loops over ``run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
+    notebooks/experiment_mlp.ipynb: one game, one MLP shape, gamma 0.99 / 0.9 / 0.8) -- taken in lockstep: ``trainers`` are independent
+    ``DeviceDQNTeamTrainer`` objects, each over its own env, models and policy, and one ``train_step`` steps every one of them.
+
+    When every member is served by the HIP path and the members have one shape (``compatible()``), the step is ONE
+    ``susnet_dqn_train_sweep`` call per chunk of at most 16 members: the launches of one learner's step with the learner as the grid's
+    second dimension, each member's result bitwise what its own ``train_step_on_indices`` leaves.  Otherwise the members' own
+    ``train_step_on_indices`` run one after another (the torch path for CPU tensors, ``SpatialDQN`` and anything else unserved)."""
+
+    def __init__(self, trainers: Sequence[DeviceDQNTeamTrainer]):
+        self.trainers = list(trainers)
+        if not self.trainers:
+            raise ValueError("a sweep needs at least one trainer")
+        if len(set(id(t) for t in self.trainers)) != len(self.trainers):
+            raise ValueError("a trainer appears twice in the sweep: two learners would update the same parameters")
+        self._losses = None
+
+    def __len__(self):
+        return len(self.trainers)
+
+    def compatible(self) -> bool:
+        """Whether the members agree on what shapes the step (what ``susnet_dqn_train_sweep`` requires): device, agent and imposter
+        count, raw row size, grid, components, which teams train and their layer dims.  gamma, learning rate and weights may differ."""
+        a = self.trainers[0]
+        for b in self.trainers[1:]:
+            ea, eb = a.env, b.env
+            if (b.device != a.device or eb.n_agents != ea.n_agents or eb.n_imposters != ea.n_imposters
+                    or eb.flattened_state_size != ea.flattened_state_size or eb.grid.shape != ea.grid.shape or not (eb.grid == ea.grid).all()
+                    or b.components != a.components or b.trained != a.trained or b._dims != a._dims):
+                return False
+        return True
+
+    def uses_hip(self, rings) -> bool:
+        """Whether a step on ``rings`` (one per member) is served by ``susnet_dqn_train_sweep`` for ALL members (else: the per-member loop)."""
+        return len(rings) == len(self.trainers) and all(t.uses_hip(r) for t, r in zip(self.trainers, rings)) and self.compatible()
+
+    def train_step(self, rings, batch_size: int, generators=None) -> torch.Tensor:
+        """Draw each member's ``batch_size`` ring rows with its own generator -- the draw the member's ``train_step`` makes -- and take
+        one sweep step.  Returns the device ``[K, 2]`` losses."""
+        generators = list(generators) if generators is not None else [None] * len(self.trainers)
+        idxs = []
+        for ring, g in zip(rings, generators):
+            assert ring.size > 0, "Replay buffer is empty, can't sample"
+            idxs.append(torch.randint(0, ring.size, (int(batch_size),), device=ring.states.device, generator=g))
+        return self.train_step_on_indices(rings, idxs)
+
+    def train_step_on_indices(self, rings, idxs) -> torch.Tensor:
+        """One train step of every member on its own ring at its own indices.  Returns the device ``[K, 2]`` losses ``[imposter, crew]``
+        per member (HIP path: without synchronising)."""
+        K = len(self.trainers)
+        if len(rings) != K or len(idxs) != K:
+            raise ValueError(f"a sweep of {K} members needs {K} rings and {K} index tensors")
+        idxs = [i.to(r.states.device, torch.int64).contiguous() for r, i in zip(rings, idxs)]
+        if not (self.uses_hip(rings) and len(set(int(i.numel()) for i in idxs)) == 1):
+            return torch.stack([t.train_step_on_indices(r, i) for t, r, i in zip(self.trainers, rings, idxs)])
+        first = self.trainers[0]
+        if self._losses is None or self._losses.shape[0] != K:
+            self._losses = torch.zeros(K, 2, dtype=torch.float32, device=first.device)
+        row_bytes = self._losses.stride(0) * self._losses.element_size()
+        for lo, hi in sweep_chunks(K):
+            n = hi - lo
+            ios, envs = (L.DqnIO * n)(), (C.c_void_p * n)()
+            for j, k in enumerate(range(lo, hi)):
+                io = self.trainers[k]._hip_io(rings[k], idxs[k])
+                io.losses_out = self._losses.data_ptr() + k * row_bytes
+                ios[j], envs[j] = io, self.trainers[k].env._h
+            with torch.cuda.device(first.device):
+                L.check(first.env.lib.susnet_dqn_train_sweep(envs, ios, n, first.env._stream()))
+        for t in self.trainers:
+            t._sync_policy_version()
+        return self._losses.clone()
+
+    @torch.no_grad()
+    def sync_targets(self) -> None:
+        for t in self.trainers:
+            t.sync_targets()
