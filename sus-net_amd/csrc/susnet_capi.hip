@@ -1342,8 +1342,10 @@ extern "C" int susnet_rollout(susnet_env *env, const susnet_rollout_io *io, void
     const uint64_t obs_tick_bytes = (uint64_t)o.tick_stride * (o.dtype == SUSNET_F32 ? 4u : 1u);
     const uint64_t tick_bytes = a.record ? (uint64_t)env->c.B * (uint64_t)a.record_bytes : std::max<uint64_t>(4u * AB, traj_flat ? obs_tick_bytes : (uint64_t)o.tick_stride);
     // (susnet_set_launch_limit; tests exercise the chunking on small batches).  Records are addressed slab by slab (record_slab): unless a limit
-    // was set, a record launch takes any number of ticks
-    const uint64_t limit = (a.record && env->launch_limit == env->launch_limit_default && !(env->layout.test_overrides & SUSNET_OVERRIDE_TRAJ_MAX_BYTES))
+    // was set, a record launch takes any number of ticks -- except on the 1v1 kernel (k_rollout_duel), which addresses the records of a whole
+    // launch through ONE descriptor and a 32-bit offset: its record launches stay within the launch limit like the trajectory modes
+    const bool duel_rec = a.record && spec == 2 && (env->c.duel_fast || env->c.duel_walls);
+    const uint64_t limit = (a.record && !duel_rec && env->launch_limit == env->launch_limit_default && !(env->layout.test_overrides & SUSNET_OVERRIDE_TRAJ_MAX_BYTES))
                                ? ~0ull : env->launch_limit;
     const uint64_t fit = limit / tick_bytes;
     if (a.record && (fit < 1 || tick_bytes > (1ull << 31) - 1u)) return fail(env, SUSNET_E_INVALID, "susnet_rollout: one tick of records exceeds 2 GiB");

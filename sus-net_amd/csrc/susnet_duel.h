@@ -137,7 +137,7 @@ __device__ __forceinline__ void duel_core(const DuelConsts &k, Duel &d, uint32_t
 
 // One step.  Out: rewards, done, truncated.  e: t, flags, info counters; cur: the env's event-stream cursor (production protocol: a
 // landed kill takes one word -- its value is never needed with a single candidate; numpy draws nothing there, base.py:497).
-// hit_out: the caller advances the cursor itself (k_rollout_duel: inside its episode-end branch).
+// hit_out: the caller advances the cursor itself.  (The fused rollout steps through duel_tick below.)
 template <bool NUMPY, bool WALLS = false>
 __device__ __forceinline__ void duel_step(const DuelConsts &k, Duel &d, Env &e, uint64_t &cur, uint32_t a0, uint32_t a1, float &r0, float &r1,
                                           uint32_t &done, uint32_t &trunc, uint32_t *hit_out = nullptr) {
@@ -151,6 +151,17 @@ __device__ __forceinline__ void duel_step(const DuelConsts &k, Duel &d, Env &e, 
     // base.py:392-395: t saturates at max_time_steps - 1
     trunc = e.t == k.max_t_m1 ? 1u : 0u;
     e.t += trunc ^ 1u;
+}
+
+// The fused rollout's step (k_rollout_duel): duel_core and the episode clock.  What an episode merely counts -- steps, kills, the won flag, the
+// kill's word of the event stream -- is settled where the episode ends, from `hit` and `done`, instead of on every tick.
+template <bool WALLS = false>
+__device__ __forceinline__ void duel_tick(const DuelConsts &k, Duel &d, uint32_t &t, uint32_t a0, uint32_t a1, float &r0, float &r1, uint32_t &done,
+                                          uint32_t &trunc, uint32_t &hit) {
+    duel_core<WALLS>(k, d, a0, a1, r0, r1, done, hit);
+    // base.py:392-395: t saturates at max_time_steps - 1
+    trunc = t == k.max_t_m1 ? 1u : 0u;
+    t += trunc ^ 1u;
 }
 
 } // namespace susnet

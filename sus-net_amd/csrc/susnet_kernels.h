@@ -1371,7 +1371,17 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
     constexpr uint32_t kRecBytes = kRec16 ? 16u : 20u;
     const uint64_t nt = (uint64_t)(a.n_ticks > 0 ? a.n_ticks : 0);
     const uint64_t B = (uint64_t)c.B;
+    // the records of the WHOLE launch behind one descriptor, built once: a tick's slab is reached by advancing the per-lane offset by one slab
+    // (rec_slab) after its stores.  32 bits hold it: susnet_rollout cuts a record request of this kernel into launches of at most the handle's
+    // launch limit (2^31 - 1 bytes unless the caller set a smaller one), so nt * kRecBytes * B < 2^31.  Lanes without an environment (ragged
+    // last wave, fewer than 64 environments per wave) have left above: the range check sees the per-lane offset and the whole launch's size
+    // only, so it would not drop a stray lane's store into the next tick's slab.
     BufDst drec = make_buf_dst(a.record, nt * kRecBytes * B, (uint32_t)bl * kRecBytes);
+    const uint32_t rec_slab = kRecBytes * (uint32_t)c.B;
+    // the terminal states (replay feed): bound or not is a fact of the launch -- without the tensor the descriptor spans 0 bytes and the range
+    // check drops the two stores, so the episode-end block carries no test of the pointer
+    constexpr bool kTerm = kFeed(OUT) || kRec || kRec16;
+    BufDst dterm = make_buf_dst(a.term_obs, a.term_obs != nullptr ? nt * 6u * B : 0ull, (uint32_t)bl * 6u);
     BufDst da = make_buf_dst(a.actions, nt * 2u * B, (uint32_t)bl * 2u + ghost);
     BufDst dr = make_buf_dst(a.rewards, nt * 8u * B, (uint32_t)bl * 8u + ghost);
     BufDst dd = make_buf_dst(a.done, nt * B, (uint32_t)bl + ghost);
@@ -1388,13 +1398,21 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
     // the next episode's spawn cells, drawn ahead (production stream; see draw_episode): one register
     uint32_t pqn = d.pq;
     bool have_next = false;
-    auto tick_body = [&](int tick, auto par) __attribute__((always_inline)) {
+    // What an episode merely COUNTS stays off the tick.  Steps: ep0 = the tick index at which the running episode's count is 0 (negative for
+    // an episode that entered the launch with steps on it), so its count after tick k is k + 1 - ep0, and the steps of all episodes finished
+    // before the launch's last tick add up to ep0's total advance.  Kills, the won flag and the kill's word of the event stream: a landed
+    // kill ends the episode on its own tick (the crew has one member), so `hit` and `done` are settled in the episode-end block.
+    const uint32_t ep_init = 0u - e.m_steps;
+    uint32_t ep0 = ep_init;
+    // LAST: the launch's last tick (always the single-tick copy, see the loop below).  Only it keeps the info counters of an episode that
+    // ends readable (FLAG_FRESH) and leaves the cursor unaligned; every other copy resets, zeroes and aligns unconditionally.
+    auto tick_body = [&](int tick, auto par, auto last) __attribute__((always_inline)) {
         constexpr int POS = decltype(par)::value;
+        constexpr bool LAST = decltype(last)::value;
         if (kTraj) { // this tick's slabs: scalar offsets derived from the (wave-uniform) tick index, nothing loop-carried
             const uint32_t t32 = (uint32_t)tick;
             da.so = t32 * (2u * slab_d); dr.so = t32 * (8u * slab_d); dd.so = t32 * slab_d; dt.so = t32 * slab_d; dobs.so = t32 * slab_o;
         }
-        if (kRec || kRec16) drec = record_slab(a.record, kRecBytes * slab_d, tick, (uint32_t)bl * kRecBytes);
         uint32_t a0, a1;
         if constexpr (RNG::kNumpy) { // base.py:326-330 with numpy's own words
             a0 = rng.bounded(6u);
@@ -1422,14 +1440,18 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
         if (kTraj) da.st16(0u, a0 | (a1 << 8));
         float r0, r1;
         uint32_t done, trunc, hit;
-        duel_step<RNG::kNumpy, WALLS>(k, d, e, rng.cur, a0, a1, r0, r1, done, trunc, &hit);
+        duel_tick<WALLS>(k, d, e.t, a0, a1, r0, r1, done, trunc, hit);
         if (kTraj) {
             dr.st64(0u, __float_as_uint(r0), __float_as_uint(r1));
             dd.st8(0u, done);
             dt.st8(0u, trunc);
         }
         if (kFeed(OUT) && a.roles != nullptr) a.roles[(int64_t)tick * c.B + b] = (uint16_t)1u; // the imposter is agent 0 (pred_prey.py:52-66, shuffle off)
+#ifdef SUSNET_EXP_DUEL_NO_FIN // diagnostic builds only (tools/build_variant_tu.sh): no episode ends inside the launch -- WRONG results
+        const bool fin = false;
+#else
         const bool fin = (done | trunc) != 0u;
+#endif
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(fin) != 0ull, 0)) {
             if constexpr (!RNG::kNumpy) {
                 // a finishing lane without drawn spawn cells: draw now -- for every lane of the wave that has none (see draw_episode)
@@ -1445,14 +1467,18 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
                     }
                 }
             }
-            if (fin) {
-                if (!RNG::kNumpy) rng.cur += (uint64_t)hit; // the landed kill's word of the event stream: a hit ends the episode (the crew has
-                                                            // one member), so it is counted here instead of by a 64-bit add on every tick
-                life.add_episode(e, trunc != 0u);
-                if ((kFeed(OUT) || kRec || kRec16) && a.term_obs != nullptr) { // the terminal state, before the in-launch reset replaces it
-                    PtrDst tp{a.term_obs + ((int64_t)tick * c.B + b) * 6};
-                    tp.st32(0u, d.pq - k01);
-                    tp.st16(4u, duel_alive_bytes(d));
+            if (fin) { // ONE region for the finishing lanes, straight-line inside
+                if (!RNG::kNumpy) rng.cur += (uint64_t)hit; // the landed kill's word of the event stream
+                // lifetime sums: the counters a 1v1 game without jobs or votes can move (LifeAcc::add_episode; the other slots stay 0 and are
+                // flushed as such)
+                life.v[SUSNET_L_EPISODES] += 1u;
+                life.v[SUSNET_L_IMPOSTER_WON] += ((e.flags >> 2) | done) & 1u; static_assert(FLAG_IMP_WON == 4u, "done << 2");
+                life.v[SUSNET_L_TRUNCATED] += trunc;
+                life.v[SUSNET_L_KILLS] += (e.m_kv & 0xffffu) + hit;
+                if constexpr (kTerm) { // the terminal state, before the in-launch reset replaces it
+                    dterm.so = (uint32_t)tick * (6u * slab_d);
+                    dterm.st32(0u, d.pq - k01);
+                    dterm.st16(4u, duel_alive_bytes(d));
                 }
                 if constexpr (RNG::kNumpy) {
                     reset_env<S>(c, T, st, tid, e, rng);
@@ -1464,12 +1490,18 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
                     e.ep += 1u;
                     have_next = false;
                 }
-                if constexpr (WALLS) DuelWallTable::lookup(d); // the spawn cells' bits (rare path: the wait sits in here)
-                // info counters of a terminal step stay readable until the next step: only the launch's last tick can be observed.
-                // The next step will align the event cursor: done right here unless this was the launch's last tick (then the
-                // stored cursor is the one the last step left)
-                if (tick == a.n_ticks - 1) e.flags |= FLAG_FRESH;
-                else { zero_metrics(e); rng.align(); }
+                if constexpr (LAST) {
+                    // info counters of a terminal step stay readable until the next step, and the stored cursor is the one this step left
+                    life.v[SUSNET_L_EPISODE_STEPS] += (uint32_t)tick + 1u - ep0;
+                    e.m_kv += hit;
+                    e.flags |= (done << 2) | FLAG_FRESH;
+                } else {
+                    if constexpr (WALLS) DuelWallTable::lookup(d); // the spawn cells' bits (rare path: the wait sits in here)
+                    ep0 = (uint32_t)tick + 1u;
+                    e.m_kv = 0u;
+                    e.flags &= ~(FLAG_FRESH | FLAG_CREW_WON | FLAG_IMP_WON);
+                    rng.align(); // the next step would align the event cursor: done right here
+                }
             }
         }
         if (OUT == OUT_TRAJ_RAW8) { // flatten_state: x0 y0 x1 y1 alive0 alive1
@@ -1489,18 +1521,27 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
             frow.build(fx, fy, fal);
             flat_store_wave(frow, T.stage, tid, nrows, dflat.r, dflat.vo + (uint32_t)tick * (slab_o * 4u));
         }
+        if (kRec || kRec16) drec.vo += rec_slab; // the next tick's slab
     };
     constexpr int kGroup = RNG::kNumpy ? 0 : 4 * kDuelTicksPerWord;
+    // the unrolled groups are taken only while a tick remains after them: the launch's last tick always runs through the single-tick copy
+    using NotLast = std::integral_constant<bool, false>;
+    const int last_tick = a.n_ticks - 1;
     int tick = 0;
-    while (tick < a.n_ticks) {
-        if (kGroup > 0 && tick + kGroup <= a.n_ticks && ((tick_base + (uint64_t)tick) % (uint64_t)(kGroup > 0 ? kGroup : 1)) == 0ull) {
-            static_for<0, (kGroup > 0 ? kGroup : 1)>([&](auto pos) __attribute__((always_inline)) { tick_body(tick + decltype(pos)::value, pos); });
+    while (tick < last_tick) {
+        if (kGroup > 0 && tick + kGroup <= last_tick && ((tick_base + (uint64_t)tick) % (uint64_t)(kGroup > 0 ? kGroup : 1)) == 0ull) {
+            static_for<0, (kGroup > 0 ? kGroup : 1)>([&](auto pos) __attribute__((always_inline)) { tick_body(tick + decltype(pos)::value, pos, NotLast{}); });
             tick += kGroup;
         } else {
-            tick_body(tick, std::integral_constant<int, -1>{});
+            tick_body(tick, std::integral_constant<int, -1>{}, NotLast{});
             tick++;
         }
     }
+    if (a.n_ticks > 0) tick_body(last_tick, std::integral_constant<int, -1>{}, std::integral_constant<bool, true>{});
+    // the counters kept off the tick, as stepping one tick at a time leaves them
+    life.v[SUSNET_L_EPISODE_STEPS] += ep0 - ep_init;
+    if (ep0 != ep_init) e.m_fix = e.m_sab = 0u; // (zero_metrics of an episode end before the last tick)
+    e.m_steps = (uint32_t)nt - ep0;
     if (kFlat && !active) return;
     const State se = kernarg_reload<State>(kStateArgOffset); // (not `s`: see kernarg_reload)
     from_duel(d, st, e);
