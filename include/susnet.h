@@ -13,6 +13,7 @@
  *   susnet_sample_actions  FourRoomEnv.sample_actions      src/environment/base.py:326-330
  *   susnet_policy_actions  run_game's acting step          src/visualize.py:547-562 (train.py:355-381, epsilon = 0)
  *   susnet_qnet_*          MLP.forward on the flat features src/models/dqn.py:72-108, 322-329
+ *   susnet_mlp_forward     MLP.forward of any served layer stack on caller-supplied feature rows  src/models/dqn.py:72-108, 322-329
  *   susnet_policy_step     argmax per team + env.step        src/visualize.py:547-582
  *   susnet_step            FourRoomEnv.step                src/environment/base.py:332-407 (tagging.py:120-235)
  *                          + _agent_step 462-533, check_win_condition 409-460 (pred_prey.py:78-99),
@@ -418,6 +419,37 @@ int susnet_qnet_pack(const susnet_env *env, const int32_t *components, int32_t n
                      const float *const *weights, const float *const *biases, const float *slopes, float *packed);
 int susnet_qnet_forward(susnet_env *env, const int32_t *components, int32_t n_components, const int32_t *dims, int32_t n_dims,
                         const float *packed, float *q_out, void *stream);
+
+/* The same network -- the reference's MLP.forward (src/models/dqn.py:72-108; make_mlp 322-329: Linear + nn.PReLU() with ONE slope per
+ * layer, no activation after the last Linear) -- of ANY served layer stack on CALLER-SUPPLIED feature rows: every game, component set and
+ * layer stack the compiled-in family above does not know.  rows: [n][F] float32 contiguous -- env.obs of a FLAT observation, the output of
+ * susnet_observe / susnet_featurize in FLAT mode, or anything else; q_out: [n][n_out].
+ *   Weights are read where torch keeps them: weight[l] is the module's parameter tensor ([dims[l+1]][dims[l]] row-major; only 4-byte
+ * alignment is assumed), bias[l] its bias, slope[l] the one-element PReLU weight behind layer l.  There is no packed image and no host step:
+ * after an in-place optimizer step (torch's, or susnet_dqn_train_step on a flat parameter buffer) the next launch reads the new values.
+ *   Served: 1 .. 7 Linear layers (n_dims 2 .. 8), F = dims[0] in 1 .. SUSNET_MLP_MAX_F (every flat layout of a 16-agent 16x16 game is
+ * below it), hidden widths 1 .. 256, n_out = dims[n_dims-1] in 1 .. 32, n >= 1; rows / q_out / the parameter pointers non-NULL and 4-byte
+ * aligned.  Anything else: SUSNET_E_INVALID, with a message that names the field, before anything is launched.
+ *   Arithmetic: float32 throughout on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32); as in susnet_qnet_forward every output is
+ * ONE chain over k in ascending order whose accumulator starts as the bias, so values agree with torch's to float32 summation-order
+ * differences.  No activation goes through global memory; the weights are streamed from global memory / L2 by every workgroup.
+ *   One launch of at most SUSNET_MLP_MAX_GRID workgroups, each walking tiles of SUSNET_MLP_ROW_TILE rows.  The handle supplies the stream
+ * and error conventions only: no environment state is read, and the handle need not have its state bound. */
+#define SUSNET_MLP_MAX_F 1024
+#define SUSNET_MLP_ROW_TILE 64
+#define SUSNET_MLP_MAX_GRID 512
+typedef struct susnet_mlp_io {
+    int32_t n_dims;            /* 2 .. 8: 1 .. 7 Linear layers */
+    int32_t dims[8];           /* [F, h1, .., n_out] */
+    const float *weight[7];    /* device, torch layout [dims[l+1]][dims[l]] row-major, 4-byte aligned only */
+    const float *bias[7];      /* device [dims[l+1]] */
+    const float *slope[6];     /* device [1] each: the PReLU weight behind layer l (n_dims - 2 of them) */
+    const float *rows;         /* device [n][F] float32, contiguous (env.obs / susnet_observe / susnet_featurize FLAT output) */
+    int64_t n;
+    float *q_out;              /* device [n][n_out] float32 */
+} susnet_mlp_io;
+int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream);
+
 int susnet_step(susnet_env *env, const susnet_step_io *io, void *stream);
 /* susnet_policy_actions and susnet_step in ONE launch -- a tick of the acting loop (visualize.py:547-582: argmax per team, env.step):
  * the stepping lane takes the teams' greedy actions from the Q rows itself (q_imposter / q_crew as for susnet_policy_actions; at most
@@ -428,17 +460,19 @@ int susnet_policy_step(susnet_env *env, const float *q_imposter, const float *q_
 /* susnet_qnet_forward and susnet_policy_step (imposters by the network; the crew random, or by ITS network: opts->crew_packed) as ONE
  * kernel -- a whole tick of the acting loop in one launch: the wave that computed its 64 environments' Q rows takes their argmax in
  * registers and steps them (with a crew network the workgroup swaps the LDS image between the two passes).  Arguments as for
- * the two calls; q_out may be NULL (Q rows not kept).  Served: the two compiled-in games the network kernel knows the feature layout of
- * (2-agent 9x9 ImposterTrainingGround; 1v2 14x14 FourRoomEnv with 4 jobs), PHILOX handles; otherwise SUSNET_E_INVALID and the caller
- * uses the two calls. */
+ * the two calls; q_out may be NULL (Q rows not kept).  Served: the two compiled-in games on the three feature layouts the network kernel
+ * knows (2-agent 9x9 ImposterTrainingGround, either map, with {ONEHOT_POS} or {COORD_POS}; 1v2 14x14 FourRoomEnv with 4 jobs with
+ * {ONEHOT_POS, ALIVE_CREW, CLOSEST_CREW}).  PHILOX handles with a random crew or the crew's network and any epsilon; TAPE handles with
+ * both networks and epsilon = 0 (nothing is drawn then).  Otherwise SUSNET_E_INVALID and the caller uses the two calls. */
 int susnet_qnet_policy_step(susnet_env *env, const int32_t *components, int32_t n_components, const int32_t *dims, int32_t n_dims,
                             const float *packed, float *q_out, const susnet_policy_opts *opts /* or NULL */, const susnet_step_io *io, void *stream);
 
 /* The policy tick (susnet_qnet_policy_step) repeated n_ticks times inside ONE launch: the acting loop of the trainer over a block of
  * ticks with fixed weights (train.py:345-399 between two optimizer steps) -- the network image is loaded once, a launch is paid once,
  * and what replay_buffer.add needs of every tick lands in slot t of [T][B] arrays, ready for susnet_ring_append.  Every pointer is
- * optional.  Served where susnet_qnet_policy_step is (the two compiled-in games, PHILOX handles, a random crew); the handle must
- * auto-reset.  Advances the handle by n_ticks steps. */
+ * optional.  Served where susnet_qnet_policy_step is (the two compiled-in games on their three feature layouts; PHILOX handles with a random
+ * crew or the crew's network through opts->crew_*, TAPE handles with both networks at epsilon = 0); the handle must auto-reset.  Advances
+ * the handle by n_ticks steps. */
 typedef struct susnet_feed_io {
     uint8_t *actions;    /* out [T][B][A] u8: the actions taken */
     float *rewards;      /* out [T][B][A] f32 */

@@ -17,6 +17,7 @@
 #include "susnet_kernels.h"
 #include "susnet_family.h"
 #include "susnet_qnet.h"
+#include "susnet_dense.h"
 #include "susnet_train.h"
 #include "susnet_episodes.h"
 
@@ -1016,6 +1017,44 @@ extern "C" int susnet_qnet_forward(susnet_env *env, const int32_t *components, i
     case FEAT_COORD: return qnet_launch<QRowC>(env, packed, q_out, dims[5], static_cast<hipStream_t>(stream));
     default: return qnet_launch<QRow3>(env, packed, q_out, dims[5], static_cast<hipStream_t>(stream));
     }
+}
+
+// susnet_mlp_forward: any served layer stack on caller-supplied rows (the kernel: inst_qnet_dense.hip).  Everything is checked here, before
+// the launch; the handle gives the error conventions only (no state is read: it need not be bound).
+extern "C" int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_forward: null env / io");
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_forward: " + what); };
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (io->n_dims < 2 || io->n_dims > 8) return bad("n_dims = " + std::to_string(io->n_dims) + " (served: 2 .. 8, i.e. 1 .. 7 Linear layers)");
+    const int nl = io->n_dims - 1;
+    if (io->dims[0] < 1 || io->dims[0] > SUSNET_MLP_MAX_F)
+        return bad("dims[0] = " + std::to_string(io->dims[0]) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
+    for (int l = 1; l < nl; l++)
+        if (io->dims[l] < 1 || io->dims[l] > kDnMaxHidden)
+            return bad("dims[" + std::to_string(l) + "] = " + std::to_string(io->dims[l]) + " (hidden widths: 1 .. " + std::to_string(kDnMaxHidden) + ")");
+    if (io->dims[nl] < 1 || io->dims[nl] > kDnMaxOut)
+        return bad("dims[" + std::to_string(nl) + "] = " + std::to_string(io->dims[nl]) + " (n_out: 1 .. " + std::to_string(kDnMaxOut) + ")");
+    if (io->n < 1) return bad("n = " + std::to_string((long long)io->n) + " (at least one row)");
+    for (int l = 0; l < nl; l++) {
+        if (!io->weight[l] || misaligned(io->weight[l])) return bad("weight[" + std::to_string(l) + "] is NULL or not 4-byte aligned");
+        if (!io->bias[l] || misaligned(io->bias[l])) return bad("bias[" + std::to_string(l) + "] is NULL or not 4-byte aligned");
+        if (l < nl - 1 && (!io->slope[l] || misaligned(io->slope[l]))) return bad("slope[" + std::to_string(l) + "] is NULL or not 4-byte aligned");
+    }
+    if (!io->rows || misaligned(io->rows)) return bad("rows is NULL or not 4-byte aligned");
+    if (!io->q_out || misaligned(io->q_out)) return bad("q_out is NULL or not 4-byte aligned");
+    DenseArgs a{};
+    a.n_dims = io->n_dims;
+    for (int l = 0; l <= nl; l++) a.d[l] = io->dims[l];
+    for (int l = 0; l < nl; l++) {
+        a.W[l] = io->weight[l];
+        a.B[l] = io->bias[l];
+        if (l < nl - 1) a.A[l] = io->slope[l];
+    }
+    a.rows = io->rows;
+    a.n = io->n;
+    a.q = io->q_out;
+    HIP_TRY(qnet_dense_launch(a, static_cast<hipStream_t>(stream)));
+    return SUSNET_OK;
 }
 
 // susnet_qnet_policy_step: the network whose kernel also steps (nullptr: a plain / policy step through k_step)

@@ -934,6 +934,15 @@ class BatchedFourRoomEnv:
             torch.cuda.current_stream(self.device).synchronize()
         return (o1, o2) if o2 is not None else o1
 
+    def refresh_obs(self) -> torch.Tensor:
+        """Rewrite ``env.obs`` from the CURRENT state (``susnet_observe`` into the fused observation's own buffer; asynchronous).  ``step`` /
+        ``policy_step`` / ``reset`` do this inside their kernel; calls that write another observation (``policy_tick_into``: the raw uint8
+        state into a feed) leave ``env.obs`` behind -- this brings it up to date."""
+        assert self._obs_spec is not None, "the env was built without a fused observation (obs=ObsConfig(...))"
+        with self._on_device():
+            L.check(self.lib.susnet_observe(self._h, C.byref(self._obs_spec), self._stream()))
+        return self.obs
+
     _ROW_DTYPES = {torch.uint8: L.U8, torch.int32: L.I32, torch.int64: L.I64, torch.float32: L.F32, torch.float64: L.F64}
 
     def featurize(self, states: torch.Tensor, obs: ObsConfig):

@@ -5,8 +5,12 @@ The loop around the HIP environment -- fused flat observation -> model -> argmax
 as torch modules (so that its checkpoints load); a reference ``MLP`` on one of the compiled-in feature layouts does not RUN through
 torch, though: ``PolicyRollout`` hands its weights to the library once (``pack_mlp`` -> ``susnet_qnet_pack``) and a tick is then
 one kernel (``susnet_qnet_policy_step``: network on the f32-input MFMA, argmax, the crew's draws, the env step), or two
-(``susnet_qnet_forward`` + ``susnet_policy_step``) when the crew has a network too.  Everything else (``SpatialDQN``, other layer
-stacks) runs through stock PyTorch-ROCm and hands its Q rows to ``susnet_policy_step`` / ``susnet_policy_actions``.
+(``susnet_qnet_forward`` + ``susnet_policy_step``) when the crew has a network too.  A reference ``MLP`` on any OTHER game, component
+set or layer stack can run through the dense kernel (``PolicyRollout(..., dense=True)``: ``DenseQNet`` -> ``susnet_mlp_forward`` on
+``env.obs``, weights read in place) and hand its Q rows to ``susnet_policy_step``: that is what ``collect`` / ``train`` / ``evaluate`` use
+on those games.  By default, and for everything else (``SpatialDQN``, stacks wider than the dense kernel serves), the network runs
+through stock PyTorch-ROCm -- which is the faster of the two at large batches -- and hands its Q rows to ``susnet_policy_step`` /
+``susnet_policy_actions``.
 
 * ``MLP`` mirrors reference src/models/dqn.py:72-108 (`make_mlp` 322-329: Linear + PReLU, last activation
   dropped) INCLUDING the module names, so a reference checkpoint `{"state_dict", "config"}`
@@ -187,9 +191,100 @@ def pack_mlp(env, model, components: Sequence[str], into=None):
     return env.qnet_pack(components, [cpu(m.weight) for m in linears], [cpu(m.bias) for m in linears], [float(m.weight.detach()) for m in acts], into=into)
 
 
+def _mlp_stack(model):
+    """``(linears, activations)`` of a reference ``MLP`` (Linear with bias / single-slope nn.PReLU alternating, dqn.py:322-329), or None."""
+    if not isinstance(model, MLP):
+        return None
+    layers = list(model.model)
+    linears, acts = layers[0::2], layers[1::2]
+    if not linears or len(acts) != len(linears) - 1 or \
+            not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
+            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or \
+            any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:])):
+        return None
+    return linears, acts
+
+
+class DenseQNet:
+    """A reference ``MLP`` served by ``susnet_mlp_forward``: ``MLP.forward`` (dqn.py:72-108) as one HIP kernel on feature rows in device
+    memory -- any game, component set and layer stack within the kernel's widths (1..7 ``Linear(bias=True)`` layers with single-slope
+    ``PReLU``s between them, input width up to ``_lib.MLP_MAX_F``, hidden widths up to 256, at most 32 outputs).  ``DenseQNet(env, model)``
+    is None for anything else (callers then run the torch module).
+
+    Nothing is packed and nothing is cached: every ``forward`` takes the parameter tensors' ``data_ptr()``s afresh, so in-place updates
+    (``optimizer.step``, ``load_state_dict``, ``susnet_dqn_train_step`` on a flat buffer) AND re-pointed parameters (the trainer moves
+    ``p.data`` into its flat buffer) are followed without a refresh.  The one limit: a captured graph freezes the pointers it was captured
+    with -- a replay follows in-place updates, not re-pointing (capture after the trainer is built)."""
+
+    def __new__(cls, env, model):
+        from . import _lib as L
+
+        stack = _mlp_stack(model)
+        if stack is None:
+            return None
+        linears, acts = stack
+        dims = [linears[0].in_features] + [m.out_features for m in linears]
+        if len(linears) > 7 or not 1 <= dims[0] <= L.MLP_MAX_F or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or \
+                not 1 <= dims[-1] <= L.MLP_MAX_OUT:
+            return None
+        self = super().__new__(cls)
+        self.env, self.model, self.dims = env, model, dims
+        self._linears, self._acts = linears, acts
+        self._q = None  # the [rows][n_out] output buffer this object owns: the one of the most recent row count
+        return self
+
+    def _ptr(self, p, device):
+        if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError(f"DenseQNet: the model's parameters must be contiguous float32 tensors on {device} (got {p.dtype} on {p.device})")
+        return p.data_ptr()
+
+    @torch.no_grad()
+    def forward(self, rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Q rows ``[n, n_out]`` of ``rows`` (``[n, F]`` float32 contiguous on the env's device; default: ``env.obs``, the fused flat
+        observation).  ``out``: where they go (default: the buffer this object keeps, re-made when ``n`` changes: a result is valid until
+        the next call).  One launch, asynchronous."""
+        import ctypes as C
+
+        from . import _lib as L
+
+        env = self.env
+        if rows is None:
+            rows = env.obs
+        F, n_out = self.dims[0], self.dims[-1]
+        assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == F and rows.is_contiguous() and rows.device == env.device, (
+            f"DenseQNet: rows must be a contiguous float32 [n, {F}] tensor on {env.device}")
+        n = rows.shape[0]
+        if out is None:
+            out = self._q
+            if out is None or out.shape[0] != n:
+                out = self._q = torch.empty(n, n_out, dtype=torch.float32, device=env.device)
+        assert out.dtype == torch.float32 and tuple(out.shape) == (n, n_out) and out.is_contiguous() and out.device == env.device
+        io = L.MlpIO()
+        io.n_dims = len(self.dims)
+        for k, d in enumerate(self.dims):
+            io.dims[k] = d
+        for l, m in enumerate(self._linears):
+            io.weight[l], io.bias[l] = self._ptr(m.weight, env.device), self._ptr(m.bias, env.device)
+        for l, m in enumerate(self._acts):
+            io.slope[l] = self._ptr(m.weight, env.device)
+        io.rows, io.n, io.q_out = rows.data_ptr(), n, out.data_ptr()
+        with env._on_device():
+            L.check(env.lib.susnet_mlp_forward(env._h, C.byref(io), env._stream()))
+        return out
+
+
 def _weights_version(model) -> int:
     """Changes whenever a parameter of ``model`` is written in place (optimizer.step, load_state_dict, target sync) or replaced."""
     return 0 if model is None else sum(p._version + id(p) for p in model.parameters())
+
+
+def served_by_kernels(policy):
+    """``(imposters served, crew served, any dense)`` of a policy object: whether each team's Q rows come from one of the library's network
+    kernels (``fused_*``: the compiled-in layouts; ``dense_*``: ``susnet_mlp_forward``) -- a crew without a model is random, which is served."""
+    dense_imp, dense_crew = getattr(policy, "dense_imposter", None), getattr(policy, "dense_crew", None)
+    imp = policy.fused_imposter is not None or dense_imp is not None
+    crew = policy.crew_model is None or policy.fused_crew is not None or dense_crew is not None
+    return imp, crew, dense_imp is not None or dense_crew is not None
 
 
 class PolicyRollout:
@@ -202,7 +297,8 @@ class PolicyRollout:
     """
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module] = None,
-                 components: Sequence[str] = ("onehot_pos",), fused: bool = True, epsilon: float = 0.0, mask_dead: bool = False):
+                 components: Sequence[str] = ("onehot_pos",), fused: bool = True, epsilon: float = 0.0, mask_dead: bool = False,
+                 dense: bool = False):
         assert env.obs_config.mode == "flat" and list(env.obs_config.components) == list(components), (
             "construct the env with obs=ObsConfig('flat', components) so that step() fuses the observation")
         self.env, self.imposter_model, self.crew_model = env, imposter_model, crew_model
@@ -210,10 +306,16 @@ class PolicyRollout:
         # habit of giving dead agents index 0; both are applied by the kernels that choose the actions (PHILOX handles)
         self.epsilon, self.mask_dead = float(epsilon), bool(mask_dead)
         # reference MLPs on a compiled-in feature layout run as ONE kernel from the state words to the Q row (susnet_qnet_forward);
-        # anything else (SpatialDQN, other layer stacks / layouts) goes through the torch module on env.obs
+        # with `dense=True` every other reference MLP within the dense kernel's widths -- any game, component set, layer stack -- runs
+        # as one kernel on env.obs (susnet_mlp_forward: dense_imposter / dense_crew): what collect / train / evaluate need on those
+        # games.  It is OFF by default: measured at 65 536 rows the kernel takes 2.2 - 3.3 x the torch modules' time
+        # (profiles/dense_qnet_bench.json), so plain acting keeps the torch module on env.obs, as does anything else (SpatialDQN, wider
+        # stacks)
         self.components = list(components)
         self.fused_imposter = pack_mlp(env, imposter_model, components) if fused else None
         self.fused_crew = pack_mlp(env, crew_model, components) if fused and crew_model is not None else None
+        self.dense_imposter = self._dense(imposter_model, env.n_imposter_actions) if fused and dense and self.fused_imposter is None else None
+        self.dense_crew = self._dense(crew_model, env.n_crew_actions) if fused and dense and crew_model is not None and self.fused_crew is None else None
         self._packed_version = (_weights_version(imposter_model), _weights_version(crew_model))
         # ... and with a random crew on one of the compiled-in games the whole tick -- network, argmax, the crew's draws, the step -- is
         # ONE kernel (susnet_qnet_policy_step); so it is with both teams' networks (round 5: the LDS image is swapped between the two passes)
@@ -222,6 +324,19 @@ class PolicyRollout:
         B = env.batch
         self._spatial = torch.zeros(B, 1, 1, device=env.device)  # FlatFeaturizer's dummy spatial input
         self._actions = torch.zeros(B, env.n_agents, dtype=torch.int64, device=env.device)
+
+    def _dense(self, model, n_actions):
+        net = DenseQNet(self.env, model)
+        if net is None or net.dims[0] != self.env.obs.shape[-1] or net.dims[-1] != n_actions:
+            return None
+        return net
+
+    def _team_q(self, fused, dense, model, feats):
+        if fused is not None:
+            return self.env.qnet_forward(fused)
+        if dense is not None:
+            return dense.forward(feats)
+        return model(self._spatial, feats)
 
     def refresh_weights(self, force: bool = True) -> bool:
         """Re-pack the models' CURRENT weights into the device images the fused kernels read (in place: a captured graph keeps
@@ -245,10 +360,10 @@ class PolicyRollout:
         env = self.env
         self.refresh_weights(force=False)
         feats = env.obs  # [B, F] float32, refreshed by reset()/step()
-        q_imp = env.qnet_forward(self.fused_imposter) if self.fused_imposter is not None else self.imposter_model(self._spatial, feats)
+        q_imp = self._team_q(self.fused_imposter, self.dense_imposter, self.imposter_model, feats)
         q_crew = None
         if self.crew_model is not None:
-            q_crew = env.qnet_forward(self.fused_crew) if self.fused_crew is not None else self.crew_model(self._spatial, feats)
+            q_crew = self._team_q(self.fused_crew, self.dense_crew, self.crew_model, feats)
         return q_imp.contiguous(), (q_crew.contiguous() if q_crew is not None else None)
 
     @torch.no_grad()

@@ -150,11 +150,14 @@ class DeviceReplayBuffer:
         their Q-networks on the current state -- epsilon-greedy, dead agents get index 0 (train.py:351-381) --, the env steps, and the
         transition ``(window, actions, rewards, next window, done, imposters)`` goes to the ring with ``ReplayBuffer.add``'s semantics
         (replay_memory.py:50-73; windows as train.py:318-322, 388-389, 441-445).  ``policy``: a ``PolicyRollout`` over ``env`` whose
-        models are reference MLPs the Q-network kernel serves (``policy.fused_imposter``; the crew by ``policy.fused_crew``, or random
-        when it has no model).  Per tick ONE kernel where the env serves the whole tick (``susnet_qnet_policy_step``), else the network
-        launch(es) + ``susnet_policy_step``; every ``ticks_per_append`` ticks ONE ``susnet_ring_append``.  ``one_launch_per_block``: the block's
-        ticks in ONE launch where the env serves it (``susnet_qnet_policy_rollout``: the weights are fixed within a block anyway).  The sequence window carries
-        over between calls (``reset_collection`` after an ``env.reset()``).  Row order = tick-major, env-minor; with ``batch=1``,
+        models are reference MLPs a network kernel serves (``policy.fused_imposter`` / ``fused_crew`` on the compiled-in layouts, else
+        ``dense_imposter`` / ``dense_crew``: any game with at most 16 actions per team; a crew without a model is random).  With a dense
+        network, per tick: ``susnet_observe`` (the flat observation of the current state), the dense forward(s) on ``env.obs``, then
+        ``susnet_policy_step``.  On the compiled-in layouts, per tick ONE kernel where the env serves the whole tick
+        (``susnet_qnet_policy_step``), else the network launch(es) + ``susnet_policy_step``.  Either way every ``ticks_per_append`` ticks
+        end with ONE ``susnet_ring_append``.  ``one_launch_per_block``: the block's ticks in ONE launch where the env serves it
+        (``susnet_qnet_policy_rollout``: the weights are fixed within a block anyway).  The sequence window carries over between calls
+        (``reset_collection`` after an ``env.reset()``).  Row order = tick-major, env-minor; with ``batch=1``,
         ``rng='numpy'`` and two networks the ring equals the reference's for the same numpy seed and weights
         (tests/golden/collect_*.npz).  Returns the number of transitions added."""
         import ctypes as C
@@ -162,8 +165,18 @@ class DeviceReplayBuffer:
         from . import _lib as L
         from .env import ObsConfig
 
-        assert policy.env is env and policy.fused_imposter is not None, "collect: the imposters' model must be a reference MLP on a compiled-in feature layout"
-        assert policy.crew_model is None or policy.fused_crew is not None, "collect: the crew's model must be a reference MLP on a compiled-in feature layout (or None: random crew)"
+        from .policy import served_by_kernels
+
+        imp_served, crew_served, dense = served_by_kernels(policy)
+        assert policy.env is env and imp_served, ("collect: the imposters' model must be a reference MLP one of the network kernels "
+                                                              "serves (PolicyRollout.fused_imposter, or dense_imposter: dense=True)")
+        assert crew_served, ("collect: the crew's model must be a reference MLP one of the network kernels serves "
+                                    "(PolicyRollout.fused_crew / dense_crew), or None: random crew")
+        if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
+            raise ValueError(f"collect: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
+                             f"{env.n_crew_actions}: only the compiled-in games are collected from at that size")
+        if dense and policy.crew_model is None and env.rng_kind != "philox":
+            raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
         assert env.flattened_state_size == self.state_size and env.n_agents == self.n_agents and env.n_imposters == self.n_imposters
         T, B = self.trajectory_size, env.batch
         # the carried window and the feed block belong to ONE env (identity, device) between two of its resets: another env of the same
@@ -183,7 +196,7 @@ class DeviceReplayBuffer:
             feed = self._collect_feed = env.alloc_feed(n_block)
         io = self._ring_io(env, feed, self._collect_window)
         # one launch per BLOCK where the env serves the whole tick in one kernel and the block's observation slots are 16-byte aligned
-        fused_block = (one_launch_per_block and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
+        fused_block = (one_launch_per_block and not dense and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
                        and (n_block == 1 or (B * self.state_size) % 16 == 0))
         done_ticks = 0
         while done_ticks < num_steps:
@@ -191,6 +204,11 @@ class DeviceReplayBuffer:
             policy.refresh_weights(force=False)  # (the optimizer may have stepped since the last block)
             if fused_block:  # the whole block in ONE launch (susnet_qnet_policy_rollout)
                 env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
+            elif dense:  # a game / layer stack without a fused path: the dense forward(s) on the current flat observation, then the tick
+                for t in range(n):
+                    env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
+                    q_imp, q_crew = policy.q_rows()
+                    env.policy_tick_into(feed, t, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
             else:
                 for t in range(n):
                     env.policy_tick_into(feed, t, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
@@ -201,6 +219,8 @@ class DeviceReplayBuffer:
             self.size = min(self.size + n * B, self.max_size)
             done_ticks += n
             self._collect_feed_ticks = n
+        if dense:
+            env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
         return num_steps * B
 
     @property

@@ -27,7 +27,7 @@ import torch
 from . import _lib as L
 from .episodes import EpisodeLog
 from .metrics import EpisodicMetricHandler, SusMetrics
-from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN
+from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, served_by_kernels
 from .replay import DeviceReplayBuffer
 from .scheduler import ExponentialSchedule
 from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer
@@ -110,9 +110,14 @@ class _Run:
             raise ValueError(f"{who}: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
         if policy.env is not env or trainer.env is not env:
             raise ValueError(f"{who}: policy and trainer must be built over the env that is trained on")
-        if policy.fused_imposter is None or (policy.crew_model is not None and policy.fused_crew is None):
-            raise ValueError(f"{who}: served are reference MLPs on a compiled-in feature layout (PolicyRollout.fused_imposter / fused_crew); "
-                             "a crew model of None acts randomly")
+        imp_served, crew_served, dense = served_by_kernels(policy)
+        if not imp_served or not crew_served:
+            raise ValueError(f"{who}: served are reference MLPs a network kernel runs (PolicyRollout.fused_imposter / fused_crew on the compiled-in "
+                             "feature layouts, dense_imposter / dense_crew elsewhere: PolicyRollout(..., dense=True)); a crew model of None acts "
+                             "randomly")
+        if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
+            raise ValueError(f"{who}: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
+                             f"{env.n_crew_actions}")
         self.env, self.metrics, self.num_steps, self.ring, self.policy, self.trainer = env, metrics, num_steps, replay_buffer, policy, trainer
         self.scheduler, self.generator, self.per_episode_info = scheduler, generator, per_episode_info
         self.save_dir = pathlib.Path(save_directory_path)
@@ -177,7 +182,8 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
           batch_size: int = 32, num_saves: int = 5, target_update_interval: int = 10_000, generator: Optional[torch.Generator] = None,
           episode_log: Optional[EpisodeLog] = None, per_episode_info: bool = False) -> EpisodeLog:
     """``train()`` of src/train.py:284-471.  ``num_steps`` counts lockstep ticks: each adds ``env.batch`` transitions.  ``policy``: the
-    ``PolicyRollout`` the teams act by (reference MLPs the Q-network kernel serves; a crew model of None = random crew); ``trainer``: the
+    ``PolicyRollout`` the teams act by (reference MLPs a network kernel serves -- the fused kernels on the compiled-in layouts, the dense
+    kernel on every other game / component set / layer stack, where the learner is ``torch_train_step``; a crew model of None = random crew); ``trainer``: the
     ``DeviceDQNTeamTrainer`` over the same models (built with ``policy=policy``, so that acting follows the trained weights);
     ``generator``: draws the replay samples.  ``metrics`` receives what the reference's handler holds after its ``train()``: the teams'
     returns with one entry per episode, the loss per train step, and the nine info counters -- with ``per_episode_info=True`` one entry
@@ -269,7 +275,7 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                                 learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval)
     (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
 
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True)
+    policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True)
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
                                    train_crew=train_crew, policy=policy)
     scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
@@ -383,14 +389,22 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
     components = list(components)
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead)
-    if policy.fused_imposter is None or (crew_model is not None and policy.fused_crew is None):
-        raise ValueError("evaluate: served are reference MLPs on a compiled-in feature layout; a crew model of None acts randomly")
-    if not env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon):
+    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead, dense=True)
+    imp_served, crew_served, dense = served_by_kernels(policy)
+    if not imp_served or not crew_served:
+        raise ValueError("evaluate: served are reference MLPs a network kernel runs (the compiled-in feature layouts, or the dense kernel); "
+                         "a crew model of None acts randomly")
+    if dense:
+        if max(env.n_imposter_actions, env.n_crew_actions) > 16:
+            raise ValueError(f"evaluate: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
+                             f"{env.n_crew_actions}")
+        if crew_model is None and env.rng_kind != "philox":
+            raise ValueError("evaluate: a random crew draws from the production stream: build the env with rng='philox'")
+    elif not env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon):
         raise ValueError("evaluate: this env / model pair / epsilon is not served by the one-kernel policy tick (susnet_qnet_policy_step)")
     n_ticks = int(n_ticks)
     n_block = max(1, min(int(block_ticks), n_ticks))
-    fused = n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0
+    fused = not dense and (n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0)
     env.reset()
     if capacity is None:  # an episode takes at least one tick
         capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
@@ -401,11 +415,18 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
         n = min(n_block, n_ticks - t)
         if fused:
             env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
+        elif dense:  # the dense forward(s) on the current flat observation, then susnet_policy_step into the feed
+            for k in range(n):
+                env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
+                q_imp, q_crew = policy.q_rows()
+                env.policy_tick_into(feed, k, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
         else:
             for k in range(n):
                 env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
         log.update(feed, n, tick_base=t)
         t += n
+    if dense:
+        env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
     rec = log.records()
     return summarize_episodes(rec, ticks=n_ticks)
 
