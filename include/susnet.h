@@ -595,6 +595,43 @@ int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream
 #define SUSNET_DQN_MAX_LEARNERS 16
 int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream);
 
+/* The same train step -- DQNTeamTrainer.train_step (src/train.py:50-149), with exactly the semantics of susnet_dqn_train_step above:
+ * agents in order, imposter team then crew team, gradients accumulating over the agents (one zero_grad per call), targets from
+ * target_params with y = r on done rows, mean MSE, torch's single-tensor Adam with the step count on the device, no step for an empty
+ * (agent, team) list -- for ANY served MLP stack on CALLER-SUPPLIED feature rows: every game, component set and layer stack the
+ * compiled-in layouts do not know.  feat / next_feat are the FlatFeaturizer rows (susnet_featurize, FLAT mode) of the batch's states and
+ * next states IN BATCH ORDER: row s belongs to indices[s]; actions, rewards, dones and imposters are read in place from the ring at
+ * clamp(indices[s]).  `params` (and target_params, exp_avg, exp_avg_sq) is flat in MLP.parameters() order for 1 .. 7 Linear layers:
+ * W0, b0, a0, W1, b1, a1, ..., W_last, b_last (a_l: the one-element PReLU weight behind layer l); 4-byte alignment is all that is assumed.
+ *   Served: the layer stacks of susnet_mlp_forward (n_dims 2 .. 8, F = dims[0] in 1 .. SUSNET_MLP_MAX_F, hidden widths 1 .. 256,
+ * n_actions = dims[n_dims-1] in 1 .. 32), one imposter, 2 .. 16 agents, n in 0 .. 2^30, both enabled teams with the same dims[0],
+ * lr >= 0, 0 <= beta < 1, team[].packed == NULL (there is no image: susnet_mlp_forward reads params in place, so the next forward sees
+ * the step).  Anything else: SUSNET_E_INVALID with a message that names the field, before anything is launched.  Out-of-range indices and
+ * actions are clamped, as in susnet_dqn_train_step.  The handle supplies the configuration (agents, imposters) and the error conventions
+ * only: it need not have its state bound.
+ *   Launches: one to split the batch, then two per (agent, enabled team) update (gradient partials; sum + Adam), all on `stream`, no host
+ * synchronisation, no parallel branches, no atomics: a call can be captured as a hipGraph, and every sum runs in a fixed order, so two
+ * runs from equal state leave identical bytes.  float32 on v_mfma_f32_32x32x2_f32.  The gradient kernel runs at most 256 workgroups, and
+ * fewer where the workgroups' partial gradients together would exceed 64 MiB. */
+typedef struct susnet_mlp_train_io {
+    const float *feat;        /* device [n][F] float32, contiguous, BATCH order: row s belongs to indices[s] (FlatFeaturizer rows of states) */
+    const float *next_feat;   /* device [n][F]: the same of next_states */
+    const int64_t *actions;   /* ring [max_size][A] int64   -- read in place at indices, as susnet_dqn_io */
+    const float *rewards;     /* ring [max_size][A] float32 */
+    const uint8_t *dones;     /* ring [max_size][1] bool */
+    const int16_t *imposters; /* ring [max_size][n_imposters] int16 */
+    int64_t max_size;
+    const int64_t *indices;   /* [n] device: the sampled ring rows */
+    int64_t n;
+    double gamma;
+    susnet_dqn_team team[2];  /* [0] imposters, [1] crew; n_dims 2 .. 8, dims = [F, h.., n_actions]; `packed` must be NULL */
+    float *losses_out;        /* [2] float32 device: the accumulated losses [imposter, crew] */
+    void *workspace;          /* device scratch of susnet_mlp_train_workspace_bytes bytes, 256-byte aligned */
+    uint64_t workspace_bytes;
+} susnet_mlp_train_io;
+int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out);
+int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream);
+
 /* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
  * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.
  * Per tick t and environment b, for every agent: G[a] = (double)rewards[t][b][a] + gamma * G[a] in float64, the product rounded before

@@ -39,7 +39,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_episode_stats_bytes", "susnet_episode_stats",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -125,6 +125,12 @@ class DqnIO(C.Structure):
                 ("next_states", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p), ("imposters", C.c_void_p),
                 ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double), ("team", DqnTeam * 2),
                 ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+class MlpTrainIO(C.Structure):
+    _fields_ = [("feat", C.c_void_p), ("next_feat", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+                ("imposters", C.c_void_p), ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double),
+                ("team", DqnTeam * 2), ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
 
 
 class EpisodeRecord(C.Structure):
@@ -240,6 +246,8 @@ def lib():
     L.susnet_dqn_workspace_bytes.argtypes = [C.c_void_p, P(DqnIO), P(C.c_uint64)]
     L.susnet_dqn_train_step.argtypes = [C.c_void_p, P(DqnIO), C.c_void_p]
     L.susnet_dqn_train_sweep.argtypes = [P(C.c_void_p), P(DqnIO), C.c_int32, C.c_void_p]
+    L.susnet_mlp_train_workspace_bytes.argtypes = [C.c_void_p, P(MlpTrainIO), P(C.c_uint64)]
+    L.susnet_mlp_train_step.argtypes = [C.c_void_p, P(MlpTrainIO), C.c_void_p]
     L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]
     L.susnet_episode_stats.argtypes = [C.c_void_p, P(EpisodeIO), C.c_void_p]
     for name in EXPORTS:

@@ -19,6 +19,7 @@
 #include "susnet_qnet.h"
 #include "susnet_dense.h"
 #include "susnet_train.h"
+#include "susnet_mlp_train.h"
 #include "susnet_episodes.h"
 
 namespace susnet {
@@ -2450,6 +2451,148 @@ extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_
     case FEAT_COORD: return dqn_sweep_launch<QRowC>(envs, ios, K, pls, st);
     default: return dqn_sweep_launch<QRow3>(envs, ios, K, pls, st);
     }
+}
+
+// ---- the dense learner's train step (susnet_mlp_train.h; the kernels: inst_mlp_train.hip) ----
+struct MlpTrainPlan {
+    MlpTrainNet net[2];
+    TrainNet adam[2]; // what k_train_adam reads: P and Pp
+    int64_t G = 1;
+    uint64_t off_lists = 0, off_counts = 0, off_gacc[2] = {0, 0}, off_partial = 0, off_z = 0, bytes = 0;
+};
+static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, MlpTrainPlan &pl) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_train_step: null env / io");
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
+    if (env->c.n_imp != 1)
+        return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
+                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + std::to_string(env->c.A) + " (served: 2 .. 16)");
+    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + std::to_string((long long)io->n) + " (served: 0 .. 2^30)");
+    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
+    int64_t pmax = 4, zmax = 0;
+    int F = 0;
+    for (int tm = 0; tm < 2; tm++) {
+        pl.net[tm] = MlpTrainNet{};
+        pl.adam[tm] = TrainNet{};
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (T.n_dims < 2 || T.n_dims > 8) return bad(who + "n_dims = " + std::to_string(T.n_dims) + " (served: 2 .. 8, i.e. 1 .. 7 Linear layers)");
+        const int nl = T.n_dims - 1;
+        if (T.dims[0] < 1 || T.dims[0] > SUSNET_MLP_MAX_F)
+            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
+        for (int l = 1; l < nl; l++)
+            if (T.dims[l] < 1 || T.dims[l] > kMtMaxHidden)
+                return bad(who + "dims[" + std::to_string(l) + "] = " + std::to_string(T.dims[l]) + " (hidden widths: 1 .. " + std::to_string(kMtMaxHidden) + ")");
+        if (T.dims[nl] < 1 || T.dims[nl] > kMtMaxOut)
+            return bad(who + "dims[" + std::to_string(nl) + "] = " + std::to_string(T.dims[nl]) + " (n_out: 1 .. " + std::to_string(kMtMaxOut) + ")");
+        if (F && T.dims[0] != F)
+            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " but team[0].dims[0] = " + std::to_string(F) + ": both teams read the same feature rows");
+        F = T.dims[0];
+        if (T.packed) return bad(who + "packed must be NULL (the dense forward reads params in place: there is no image to rewrite)");
+        if (!(T.lr >= 0.0) || !(T.beta1 >= 0.0 && T.beta1 < 1.0) || !(T.beta2 >= 0.0 && T.beta2 < 1.0) || !(T.eps >= 0.0))
+            return bad(who + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
+        MlpTrainNet &net = pl.net[tm];
+        net.nl = nl;
+        int off = 0, z = 0;
+        for (int l = 0; l <= nl; l++) net.d[l] = T.dims[l];
+        for (int l = 0; l < nl; l++) { // MLP.parameters(): Linear weight, Linear bias, PReLU weight, ... (dqn.py:322-329)
+            net.oW[l] = off;
+            off += net.d[l + 1] * net.d[l];
+            net.oB[l] = off;
+            off += net.d[l + 1];
+            if (l < nl - 1) {
+                net.oA[l] = off++;
+                net.zo[l] = z;
+                z += net.d[l + 1] * kTrTS;
+            }
+        }
+        net.P = off;
+        net.Pp = (off + 1 + 3) / 4 * 4;
+        net.Z = z;
+        pl.adam[tm].P = net.P;
+        pl.adam[tm].Pp = net.Pp;
+        pmax = std::max<int64_t>(pmax, net.Pp);
+        zmax = std::max<int64_t>(zmax, z);
+    }
+    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
+    pl.G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMtMaxGrid, tiles), (int64_t)(kMtMaxPartialBytes / (4ull * (uint64_t)pmax))));
+    const int A = env->c.A;
+    uint64_t o = 0;
+    pl.off_lists = o;
+    o = up(o + 4ull * 2 * A * (uint64_t)std::max<int64_t>(io->n, 1), 256);
+    pl.off_counts = o;
+    o = up(o + 4ull * 2 * A, 256);
+    for (int tm = 0; tm < 2; tm++) {
+        pl.off_gacc[tm] = o;
+        o = up(o + 4ull * (uint64_t)std::max(pl.net[tm].Pp, 4), 256);
+    }
+    pl.off_partial = o;
+    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)pmax, 256);
+    pl.off_z = o;
+    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)std::max<int64_t>(zmax, 4), 256);
+    pl.bytes = o;
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out) {
+    MlpTrainPlan pl;
+    if (int rc = mlp_train_plan(env, io, pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_mlp_train_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
+extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
+    MlpTrainPlan pl;
+    if (int rc = mlp_train_plan(env, io, pl)) return rc;
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
+        return bad("workspace missing, smaller than susnet_mlp_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
+                   " bytes) or not 256-byte aligned");
+    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
+    if (!io->actions) return bad("actions is NULL");
+    if (!io->rewards) return bad("rewards is NULL");
+    if (!io->dones) return bad("dones is NULL");
+    if (!io->imposters) return bad("imposters is NULL");
+    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
+    if (io->n > 0) {
+        if (!io->indices) return bad("indices is NULL");
+        if (!io->feat || misaligned(io->feat)) return bad("feat is NULL or not 4-byte aligned");
+        if (!io->next_feat || misaligned(io->next_feat)) return bad("next_feat is NULL or not 4-byte aligned");
+    }
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
+        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
+        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
+        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
+        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(io->workspace);
+    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
+    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
+    float *partial = reinterpret_cast<float *>(ws + pl.off_partial), *zsave = reinterpret_cast<float *>(ws + pl.off_z);
+    const MlpTrainBatch b{io->feat, io->next_feat, io->actions, io->rewards, io->dones, io->imposters, io->indices, io->max_size, io->n,
+                          (int32_t)env->c.A, (int32_t)env->c.n_imp};
+    HIP_TRY(mlp_train_select_launch(b, lists, counts, gacc[0], pl.net[0].P, gacc[1], pl.net[1].P, io->losses_out, st));
+    if (io->n == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            const susnet_dqn_team &T = io->team[tm];
+            if (!T.enabled) continue;
+            HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, zsave, T.step,
+                                          (int)pl.G, st));
+            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.adam[tm], counts, agent, tm, partial,
+                               (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
+            HIP_TRY(hipGetLastError());
+        }
+    return SUSNET_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -253,10 +253,13 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
                    train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
-                   generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None) -> EpisodicMetricHandler:
+                   generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
+                   dense_train: bool = False) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: writes ``config.json``, builds ring, policy, trainer
     and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
-    entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions."""
+    entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
+    ``dense_train=True`` (opt-in): the trainer is built with ``dense=True`` -- off the compiled-in layouts the train step is
+    ``susnet_mlp_train_step`` instead of the torch loop."""
     components = list(components)
     if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
         raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
@@ -277,7 +280,7 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
 
     policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True)
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
-                                   train_crew=train_crew, policy=policy)
+                                   train_crew=train_crew, policy=policy, dense=dense_train)
     scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
     metrics = EpisodicMetricHandler()
     ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
@@ -319,7 +322,7 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
               gamma: float = 0.99, scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
               train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
               train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
-              seed: int = 0) -> List[EpisodicMetricHandler]:
+              seed: int = 0, dense_train: bool = False) -> List[EpisodicMetricHandler]:
     """The reference's sweeps -- ``for config in configs: run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
     notebooks/experiment_mlp.ipynb: gamma 0.99 / 0.9 / 0.8 on one game and one MLP) -- as ONE run: the members collect one after another
     and take their train steps together (``train_sweep``).  The shared arguments are ``run_experiment``'s.  ``variants``: one dict per
@@ -329,7 +332,8 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     (``crew_model_factory=None``: random crews) under ``torch.manual_seed(seed)``; the member's sample generator is seeded with ``seed``
     too.  Each member gets ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values),
     the checkpoints and ``metrics.json`` exactly as ``run_experiment`` writes them, so plotting over one directory per gamma keeps
-    working.  Returns the members' metric handlers."""
+    working.  ``dense_train`` is ``run_experiment``'s: members whose step the sweep call does not serve then take their dense steps one
+    after another.  Returns the members' metric handlers."""
     components = list(components)
     variants = check_variants(variants)
     if sequence_length != 1:
@@ -361,7 +365,7 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
         (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
         policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True)
         trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=v["learning_rate"], gamma=v["gamma"],
-                                       train_imposter=train_imposter, train_crew=train_crew, policy=policy)
+                                       train_imposter=train_imposter, train_crew=train_crew, policy=policy, dense=dense_train)
         scheduler = ExponentialSchedule(v["scheduler_start_eps"], v["scheduler_end_eps"], v["scheduler_time_steps"])
         ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
         if replay_prepopulate_steps > 0:

@@ -5,6 +5,10 @@ from a ``DeviceReplayBuffer`` (``ReplayBuffer.sample``, src/replay_memory.py:75-
   ``susnet_qnet_forward`` serves), a window of one state, one imposter.  The ring is read in place at the sampled indices; per (agent,
   team) update one gradient launch and one reduce + Adam launch, no host synchronisation, and the teams' packed images (what
   ``PolicyRollout`` acts with) are rewritten on the device.
+* dense HIP path (``susnet_mlp_train_step``, csrc/susnet_mlp_train.h; opt-in: ``DeviceDQNTeamTrainer(..., dense=True)``): reference
+  ``MLP``s of any served layer stack on ANY game and component set, a window of one state, one imposter.  The batch's states are gathered
+  and featurized (the FLAT featurizer kernel) into reused buffers, then one call: the same launches per update, no host synchronisation.
+  There is no packed image: a ``PolicyRollout(dense=True)`` reads the parameters in place and follows the step without a refresh.
 * torch path (``torch_train_step``): the same algorithm in torch ops for anything else -- ``SpatialDQN``, other layer stacks, longer
   windows, CPU tensors.
 
@@ -21,7 +25,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
-from .policy import MLP, RandomEquiprobable, _weights_version
+from .policy import MLP, RandomEquiprobable, _mlp_stack, _weights_version
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults (train.py:35-37 passes only lr)
 
@@ -77,10 +81,12 @@ class DeviceDQNTeamTrainer:
     (train.py:24-38), for a ``DeviceReplayBuffer`` of ``env``.  ``components``: the FlatFeaturizer components the networks read.
     ``policy``: a ``PolicyRollout`` whose fused images should follow the trained weights without a host re-pack (it must read the same
     ``components``).  ``featurizer``: what the torch path featurizes the ring's states with (``features.FlatFeaturizer`` over
-    ``components`` by default; a ``SpatialDQN`` needs a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of the same env)."""
+    ``components`` by default; a ``SpatialDQN`` needs a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of the same env).
+    ``dense=True`` (opt-in): what ``susnet_dqn_train_step`` does not serve goes to ``susnet_mlp_train_step`` where that serves it
+    (``uses_dense``), before the torch path."""
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module], components: Sequence[str], lr: float, gamma: float,
-                 train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None):
+                 train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None, dense: bool = False):
         if env.n_imposters >= 2:
             raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
                              "(src/train.py:83) has n_imposters * N entries")
@@ -119,6 +125,12 @@ class DeviceDQNTeamTrainer:
         # where each team's Adam state currently lives: "flat" (the buffers the kernels update) or "optim" (the torch optimizer)
         self._owner = ["flat", "flat"]
         self._ws, self._losses = None, None
+        # the dense step: each trained team's [F, h.., n_actions] where susnet_mlp_train_step serves it
+        self._dense_dims = [self._stack_dims(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self.dense = (bool(dense) and self.device.type == "cuda" and any(self.trained) and featurizer is None
+                      and all(c in L.FLAT_COMPONENTS for c in self.components)
+                      and all(d is not None for d, tr in zip(self._dense_dims, self.trained) if tr) and self._dense_served())
+        self._dense_bufs = None  # (n, gathered states, gathered next states, spec + rows of states, spec + rows of next states)
 
     # ---- configuration ----
     @staticmethod
@@ -131,6 +143,19 @@ class DeviceDQNTeamTrainer:
                 not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in act):
             return None
         return [lin[0].in_features] + [m.out_features for m in lin]
+
+    @staticmethod
+    def _stack_dims(model):
+        """``[F, h.., n_out]`` of a reference ``MLP`` stack within ``susnet_mlp_train_step``'s bounds (those of ``susnet_mlp_forward``), or None."""
+        stack = _mlp_stack(model)
+        if stack is None:
+            return None
+        linears, _ = stack
+        dims = [linears[0].in_features] + [m.out_features for m in linears]
+        if len(linears) > 7 or not 1 <= dims[0] <= L.MLP_MAX_F or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or \
+                not 1 <= dims[-1] <= L.MLP_MAX_OUT:
+            return None
+        return dims
 
     def _io(self, ring=None, idx=None) -> "L.DqnIO":
         io = L.DqnIO()
@@ -177,8 +202,39 @@ class DeviceDQNTeamTrainer:
         return None
 
     def uses_hip(self, ring) -> bool:
-        """Whether ``ring`` is trained on by ``susnet_dqn_train_step`` (else: ``torch_train_step``)."""
+        """Whether ``ring`` is trained on by ``susnet_dqn_train_step`` (else: the dense step where ``uses_dense``, else ``torch_train_step``)."""
         return self.hip and ring.trajectory_size == 1 and ring.states.device == self.device
+
+    def uses_dense(self, ring) -> bool:
+        """Whether ``ring`` is trained on by ``susnet_mlp_train_step``: a ``dense=True`` trainer of reference MLP stacks within the
+        kernel's bounds, cuda tensors, a window of one state -- and ``uses_hip`` does not hold (that path goes first)."""
+        return self.dense and not self.uses_hip(ring) and ring.trajectory_size == 1 and ring.states.device == self.device
+
+    def _dense_io(self) -> "L.MlpTrainIO":
+        io = L.MlpTrainIO()
+        io.gamma = self.gamma
+        for t in range(2):
+            tm = io.team[t]
+            if not self.trained[t] or self._dense_dims[t] is None:
+                continue
+            tm.enabled, tm.n_dims = 1, len(self._dense_dims[t])
+            for i, v in enumerate(self._dense_dims[t]):
+                tm.dims[i] = v
+            tm.lr, tm.beta1, tm.beta2, tm.eps = self.lr, BETAS[0], BETAS[1], EPS
+            tm.params, tm.target_params = self.flat[t].data_ptr(), self.target_flat[t].data_ptr()
+            tm.exp_avg, tm.exp_avg_sq, tm.step = self.exp_avg[t].data_ptr(), self.exp_avg_sq[t].data_ptr(), self.step_count[t].data_ptr()
+        return io
+
+    def _dense_served(self) -> bool:
+        from .env import ObsConfig
+
+        F = self.env._make_obs(ObsConfig("flat", self.components), 1, rows=1)[1].shape[-1]
+        if any(d[0] != F for d, tr in zip(self._dense_dims, self.trained) if tr):
+            return False  # the networks do not read this featurizer's rows
+        io = self._dense_io()
+        io.max_size, io.n = 1, 1
+        nbytes = C.c_uint64()
+        return self.env.lib.susnet_mlp_train_workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
 
     # ---- the train step ----
     def train_step(self, ring, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -192,6 +248,8 @@ class DeviceDQNTeamTrainer:
         idx = idx.to(ring.states.device, torch.int64).contiguous()
         if self.uses_hip(ring):
             return self._hip_step(ring, idx)
+        if self.uses_dense(ring):
+            return self._dense_step(ring, idx)
         return self._torch_step(ring, idx)
 
     def _hip_io(self, ring, idx) -> "L.DqnIO":
@@ -217,6 +275,48 @@ class DeviceDQNTeamTrainer:
             L.check(env.lib.susnet_dqn_train_step(env._h, C.byref(io), env._stream()))
         self._sync_policy_version()
         return self._losses.clone()  # (a new tensor per step, as the torch path returns; enqueued, no host wait)
+
+    def _dense_step(self, ring, idx):
+        """Gather + featurize the batch's states and next states into reused buffers, then ``susnet_mlp_train_step``: nothing waits on the
+        host (with ``env.check_errors`` the featurizer's row check is polled, as ``env.featurize`` does)."""
+        from .env import ObsConfig
+
+        env, n = self.env, int(idx.numel())
+        for t in range(2):
+            self._state_to_flat(t)
+        if self._losses is None:
+            self._losses = torch.zeros(2, dtype=torch.float32, device=self.device)
+        io = self._dense_io()
+        if n > 0:
+            if self._dense_bufs is None or self._dense_bufs[0] != n:
+                oc = ObsConfig("flat", self.components)
+                self._dense_bufs = (n, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
+                                    torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
+                                    env._make_obs(oc, 1, rows=n), env._make_obs(oc, 1, rows=n))
+            _, rows, next_rows, (spec, feat, _), (next_spec, next_feat, _) = self._dense_bufs
+            torch.index_select(ring.states, 0, idx, out=rows)
+            torch.index_select(ring.next_states, 0, idx, out=next_rows)
+            io.feat, io.next_feat = feat.data_ptr(), next_feat.data_ptr()
+        io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
+        io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
+        io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
+        nbytes = C.c_uint64()
+        L.check(env.lib.susnet_mlp_train_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)))
+        if self._ws is None or self._ws.numel() < nbytes.value:
+            self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        io.losses_out = self._losses.data_ptr()
+        with torch.cuda.device(self.device):
+            if n > 0:
+                dt = env._ROW_DTYPES[rows.dtype]
+                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), dt, n, C.byref(spec), env._stream()))
+                L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n, C.byref(next_spec), env._stream()))
+                if env.check_errors:
+                    env.poll_errors()
+            L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
+        if self.policy is not None and any(self._policy_image(t) is not None for t in range(2)):
+            self.policy.refresh_weights(force=True)  # (a fused image of these weights: only where the fused step was switched off by hand)
+        return self._losses.clone()
 
     def _sync_policy_version(self):
         p = self.policy
