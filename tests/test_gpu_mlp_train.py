@@ -2,7 +2,6 @@
 integer-valued networks, close to a float64 torch run on ragged and deep stacks, close to the torch path and to the fused learner on real
 rings, on the reference's own fixtures, bitwise reproducible and graph-capturable, and wired through train()."""
 import copy
-import ctypes as C
 import importlib
 import json
 import math
@@ -12,14 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from train_exact import BETAS, DEV, ExactSums, abi_step, exact_net, flatten, np_train_step, split
 from train_fixtures import GOLDEN, check_final, check_first_step, mlp_from, param_names, step_indices
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 COMPS3 = ["onehot_pos", "alive_crew", "closest_crew"]
-CANARY = 12345.0
-BETAS, EPS = (0.9, 0.999), 1e-8
 
 
 @pytest.fixture(scope="module")
@@ -33,242 +30,7 @@ def env4(pkg):
     return pkg.BatchedFourRoomEnv(1, 3, 5, batch=64, device=DEV, rng="philox", seed=3, auto_reset=True, grid_size=9)
 
 
-# ---- the C ABI by hand -------------------------------------------------------------------------------------------------------------------
-def n_params(dims):
-    return sum(a * b + b for a, b in zip(dims[:-1], dims[1:])) + len(dims) - 2
-
-
-def flatten(W, B, slopes):
-    """MLP.parameters() order: W0, b0, a0, W1, b1, a1, ..., W_last, b_last."""
-    parts = []
-    for l, (w, b) in enumerate(zip(W, B)):
-        parts += [np.asarray(w).reshape(-1), np.asarray(b).reshape(-1)]
-        if l < len(W) - 1:
-            parts.append(np.asarray([slopes[l]]))
-    return np.concatenate(parts)
-
-
-def split(dims, flat):
-    """-> [(name, array)] per tensor of a flat parameter-order buffer."""
-    out, off = [], 0
-    for l, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
-        out.append((f"W{l}", flat[off:off + a * b].reshape(b, a)))
-        off += a * b
-        out.append((f"b{l}", flat[off:off + b]))
-        off += b
-        if l < len(dims) - 2:
-            out.append((f"a{l}", flat[off:off + 1]))
-            off += 1
-    assert off == len(flat)
-    return out
-
-
-class Guarded:
-    """A float32 device buffer of `n` values at an ODD 4-byte offset of its allocation, with canaries in front and behind."""
-
-    def __init__(self, values=None, n=None):
-        n = len(values) if values is not None else n
-        self.n = n
-        self.buf = torch.full((n + 4,), CANARY, dtype=torch.float32, device=DEV)
-        self.view = self.buf[1:1 + n]
-        self.view.copy_(torch.as_tensor(np.asarray(values, dtype=np.float32)) if values is not None else torch.zeros(n))
-        assert self.view.data_ptr() % 8 == 4
-
-    def ptr(self):
-        return self.view.data_ptr()
-
-    def numpy(self):
-        return self.view.cpu().numpy().astype(np.float64)
-
-    def intact(self):
-        b = self.buf.cpu().numpy()
-        return b[0] == CANARY and bool((b[1 + self.n:] == CANARY).all())
-
-
-def abi_step(pkg, env, teams, batch, gamma):
-    """One susnet_mlp_train_step by hand.  teams: per team None or dict(dims, params, target, lr, betas); batch: dict of numpy arrays
-    feat, next_feat [n][F], idx [n], actions [M][A], rewards [M][A], dones [M], imposters [M].  -> (losses [2], per team dict of float64
-    numpy params / exp_avg / exp_avg_sq / step)."""
-    L = pkg._lib
-    io = L.MlpTrainIO()
-    dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(DEV)
-    n = len(batch["idx"])
-    feat, next_feat = dev(batch["feat"], torch.float32), dev(batch["next_feat"], torch.float32)
-    idx = dev(batch["idx"], torch.int64)
-    actions, rewards = dev(batch["actions"], torch.int64), dev(batch["rewards"], torch.float32)
-    dones, imposters = dev(batch["dones"], torch.uint8), dev(batch["imposters"].reshape(-1, 1), torch.int16)
-    io.feat, io.next_feat, io.indices, io.n = feat.data_ptr(), next_feat.data_ptr(), idx.data_ptr(), n
-    io.actions, io.rewards, io.dones, io.imposters = actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(), imposters.data_ptr()
-    io.max_size, io.gamma = actions.shape[0], gamma
-    bufs = [None, None]
-    for t, tm in enumerate(teams):
-        if tm is None:
-            continue
-        P = n_params(tm["dims"])
-        assert len(tm["params"]) == P == len(tm["target"])
-        g = dict(params=Guarded(tm["params"]), target=Guarded(tm["target"]), exp_avg=Guarded(n=P), exp_avg_sq=Guarded(n=P),
-                 step=torch.zeros(1, dtype=torch.float32, device=DEV))
-        bufs[t] = g
-        T = io.team[t]
-        T.enabled, T.n_dims = 1, len(tm["dims"])
-        for k, d in enumerate(tm["dims"]):
-            T.dims[k] = d
-        T.lr, T.beta1, T.beta2, T.eps = tm["lr"], tm["betas"][0], tm["betas"][1], EPS
-        T.params, T.target_params, T.exp_avg, T.exp_avg_sq = g["params"].ptr(), g["target"].ptr(), g["exp_avg"].ptr(), g["exp_avg_sq"].ptr()
-        T.step = g["step"].data_ptr()
-    losses = torch.full((4,), CANARY, dtype=torch.float32, device=DEV)  # [canary, imposter, crew, canary]
-    io.losses_out = losses.data_ptr() + 4
-    nbytes = C.c_uint64()
-    L.check(env.lib.susnet_mlp_train_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)))
-    ws = torch.empty(int(nbytes.value) + 256, dtype=torch.uint8, device=DEV)
-    ws[int(nbytes.value):] = 0x5A
-    io.workspace, io.workspace_bytes = ws.data_ptr(), int(nbytes.value)
-    with torch.cuda.device(DEV):
-        L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
-    torch.cuda.synchronize()
-    lo = losses.cpu().numpy()
-    assert lo[0] == CANARY and lo[3] == CANARY, "losses_out: a neighbour was written"
-    assert bool((ws[int(nbytes.value):] == 0x5A).all()), "the workspace was overrun"
-    out = [None, None]
-    for t, g in enumerate(bufs):
-        if g is None:
-            continue
-        for k in ("params", "target", "exp_avg", "exp_avg_sq"):
-            assert g[k].intact(), f"team {t} {k}: a canary was overwritten"
-        assert np.array_equal(g["target"].numpy(), np.asarray(teams[t]["target"], dtype=np.float32).astype(np.float64)), "the target network was written"
-        out[t] = dict(params=g["params"].numpy(), exp_avg=g["exp_avg"].numpy(), exp_avg_sq=g["exp_avg_sq"].numpy(), step=float(g["step"]))
-    return lo[1:3].astype(np.float64), out
-
-
-# ---- 1. exact ----------------------------------------------------------------------------------------------------------------------------
-class ExactSums:
-    """Collects, for every sum of the restatement, the condition under which EVERY summation order is exact in float32: all terms are
-    multiples of one power of two q and sum |term| / q < 2^24 (every partial sum is then a multiple of q below 2^24 q)."""
-
-    def __init__(self):
-        self.worst, self.ok = 0.0, True
-
-    @staticmethod
-    def quantum(x):
-        """The largest power of two that divides every entry of x (float64), or inf for all zeros."""
-        x = np.asarray(x, dtype=np.float64).reshape(-1)
-        x = x[x != 0]
-        if x.size == 0:
-            return math.inf
-        m, e = np.frexp(x)
-        mi = np.round(np.abs(m) * 2.0 ** 53).astype(np.int64)
-        low = mi & -mi  # lowest set bit of the 53-bit mantissa
-        return float(2.0 ** (np.min(e.astype(np.float64) + np.log2(low.astype(np.float64))) - 53))
-
-    @classmethod
-    def quantum_cols(cls, x):
-        """quantum() of every column of a matrix."""
-        return np.array([cls.quantum(x[:, j]) for j in range(x.shape[1])])
-
-    def check(self, q, abs_sums):
-        """One family of sums: the per-sum totals of |term| and the quantum of each sum's terms (one for the family, or one per sum)."""
-        abs_sums = np.asarray(abs_sums, dtype=np.float64)
-        q = np.broadcast_to(np.asarray(q, dtype=np.float64), abs_sums.shape)
-        live = np.isfinite(q) & (abs_sums > 0)  # (a sum of zeros is exact)
-        if not live.any():
-            return True
-        ratio = float(np.max(abs_sums[live] / q[live]))
-        self.worst = max(self.worst, ratio)
-        good = ratio < 2.0 ** 24
-        self.ok = self.ok and good
-        return good
-
-    def matmul(self, a, b, extra=None):
-        """sum_k a[i, k] b[k, j] (+ extra[j]): terms are multiples of q(a) q(b)."""
-        q = self.quantum(a) * self.quantum(b)
-        tot = np.abs(a) @ np.abs(b)
-        if extra is not None:
-            q = min(q, self.quantum(extra))
-            tot = tot + np.abs(extra)
-        return self.check(q, tot)
-
-
-def exact_net(rng, dims):
-    """Every unit: 4 nonzero +-1 inputs (all of them where the layer is narrower), bias in {-1, 0, 1}."""
-    W, B = [], []
-    for a, b in zip(dims[:-1], dims[1:]):
-        w = np.zeros((b, a))
-        for u in range(b):
-            cols = rng.choice(a, size=min(4, a), replace=False)
-            w[u, cols] = rng.choice([-1.0, 1.0], size=len(cols))
-        W.append(w)
-        B.append(rng.integers(-1, 2, b).astype(np.float64))
-    return W, B
-
-
-def np_forward(W, B, X, slope=0.5, ex=None):
-    Z, h = [], X
-    for l in range(len(W)):
-        if ex is not None:
-            ex.matmul(h, W[l].T, B[l])
-        z = h @ W[l].T + B[l]
-        Z.append(z)
-        h = np.where(z > 0, z, slope * z)
-    return Z
-
-
-def np_train_step(dims, online, target, batch, agents_rows, gamma, ex, slope=0.5):
-    """The float64 restatement of one team's updates with lr = 0 (the weights never move): the gradient accumulated over `agents_rows`
-    = [(agent, batch positions)], flat in parameter order, the summed losses, the number of non-empty updates, and whether the loss sums
-    met the exactness condition.  The gradient's sums are recorded in `ex` as the step defines them: within ONE update every word is
-    one sum over the list's rows (any order: tiles, workgroups, lanes), and the updates' gradients then accumulate in agent order
-    (zero_grad once per call) -- a second sum whose terms are the updates' totals."""
-    W, B = online
-    L_ = len(W)
-    gW, gB, gA = [np.zeros_like(w) for w in W], [np.zeros_like(b) for b in B], [0.0] * (L_ - 1)
-    aW, aB, aA = [np.zeros_like(w) for w in W], [np.zeros_like(b) for b in B], [0.0] * (L_ - 1)  # sums over updates of |update's total|
-    qW, qB, qA = [np.full(w.shape, math.inf) for w in W], [np.full(b.shape, math.inf) for b in B], [math.inf] * (L_ - 1)  # quanta of the totals
-    loss_total, steps, loss_exact = 0.0, 0, True
-    for agent, rows in agents_rows:
-        cnt = len(rows)
-        if cnt == 0:
-            continue
-        steps += 1
-        r = batch["idx"][rows]
-        Xs, Xn = batch["feat"][rows], batch["next_feat"][rows]
-        qn = np_forward(*target, Xn, slope, ex)[-1]
-        rew = batch["rewards"][r, agent].astype(np.float64)
-        y = np.where(batch["dones"][r] != 0, rew, rew + gamma * qn.max(1))
-        Z = np_forward(W, B, Xs, slope, ex)
-        act = batch["actions"][r, agent]
-        diff = Z[-1][np.arange(cnt), act] - y
-        ex.check(min(ex.quantum(Z[-1]), ex.quantum(y)), np.abs(Z[-1][np.arange(cnt), act]) + np.abs(y))
-        sq = diff * diff
-        loss_ex = ExactSums()
-        loss_ex.check(loss_ex.quantum(sq), np.array([sq.sum()]))
-        loss_exact = loss_exact and loss_ex.ok and float(np.float32(sq.sum() / cnt)) == sq.sum() / cnt
-        loss_total += sq.sum() / cnt
-        dz = np.zeros_like(Z[-1])
-        dz[np.arange(cnt), act] = 2.0 / cnt * diff
-        for l in range(L_ - 1, -1, -1):
-            h = Xs if l == 0 else np.where(Z[l - 1] > 0, Z[l - 1], slope * Z[l - 1])
-            q_w = np.outer(ex.quantum_cols(dz), ex.quantum_cols(h))  # dW[n][k]: terms dz[s][n] h[s][k]
-            ex.check(q_w, np.abs(dz).T @ np.abs(h))
-            ex.check(ex.quantum_cols(dz), np.abs(dz).sum(0))
-            uW, uB = dz.T @ h, dz.sum(0)
-            gW[l], aW[l], qW[l] = gW[l] + uW, aW[l] + np.abs(uW), np.minimum(qW[l], q_w)
-            gB[l], aB[l], qB[l] = gB[l] + uB, aB[l] + np.abs(uB), np.minimum(qB[l], ex.quantum_cols(dz))
-            if l > 0:
-                ex.matmul(dz, W[l])
-                dh = dz @ W[l]
-                z = Z[l - 1]
-                terms = np.where(z > 0, 0.0, z * dh)
-                ex.check(ex.quantum(terms), np.array([np.abs(terms).sum()]))
-                gA[l - 1], aA[l - 1], qA[l - 1] = gA[l - 1] + terms.sum(), aA[l - 1] + abs(terms.sum()), min(qA[l - 1], ex.quantum(terms))
-                dz = np.where(z > 0, dh, slope * dh)
-    for l in range(L_):  # the accumulation over the updates
-        ex.check(qW[l], aW[l])
-        ex.check(qB[l], aB[l])
-        if l < L_ - 1:
-            ex.check(qA[l], np.array([aA[l]]))
-    return flatten(gW, gB, gA), loss_total, steps, loss_exact
-
-
+# ---- 1. exact (the C ABI by hand, the exactness condition and the float64 restatement: tests/train_exact.py) --------------------------------
 def exact_case(dims, n, seed):
     rng = np.random.default_rng(seed)
     A, M = 4, n + 7
@@ -305,13 +67,13 @@ def test_exact_against_float64_restatement(pkg, env4, dims, n):
     teams = [dict(dims=dims, params=flatten(*nets[t][0], slopes), target=flatten(*nets[t][1], slopes), lr=0.0, betas=(0.0, 0.999)) for t in range(2)]
     losses, got = abi_step(pkg, env4, teams, batch, 0.5)
     for t in range(2):
-        grad, loss, steps, loss_exact = want[t]
+        grad, loss, steps, loss_exact, info = want[t]
         assert got[t]["step"] == steps == (2, 4)[t]
         assert np.array_equal(got[t]["params"], teams[t]["params"]), "lr = 0: the weights must not move"
         for (name, g_), (_, w_) in zip(split(dims, got[t]["exp_avg"]), split(dims, grad)):
             assert np.array_equal(g_, w_), f"team {t} {name}: max |diff| {np.abs(g_ - w_).max():.3e} of {np.abs(w_).max():.3e}"
-        if loss_exact:
-            assert losses[t] == loss, (t, losses[t], loss)
+        if loss_exact:  # (the updates' means accumulated in float32, as the step does: equal to `loss` wherever that sum is a float32 value)
+            assert losses[t] == info["loss32"], (t, losses[t], info["loss32"], loss)
         else:
             np.testing.assert_allclose(losses[t], loss, rtol=1e-6)
 
