@@ -14,6 +14,7 @@
  *   susnet_policy_actions  run_game's acting step          src/visualize.py:547-562 (train.py:355-381, epsilon = 0)
  *   susnet_qnet_*          MLP.forward on the flat features src/models/dqn.py:72-108, 322-329
  *   susnet_mlp_forward     MLP.forward of any served layer stack on caller-supplied feature rows  src/models/dqn.py:72-108, 322-329
+ *   susnet_window_push     the acting loop's state window, one tick on (as feature rows)  src/train.py:318-322, 388-389, 441-445
  *   susnet_policy_step     argmax per team + env.step        src/visualize.py:547-582
  *   susnet_step            FourRoomEnv.step                src/environment/base.py:332-407 (tagging.py:120-235)
  *                          + _agent_step 462-533, check_win_condition 409-460 (pred_prey.py:78-99),
@@ -449,6 +450,31 @@ typedef struct susnet_mlp_io {
     float *q_out;              /* device [n][n_out] float32 */
 } susnet_mlp_io;
 int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream);
+
+/* The trainer's state window (src/train.py:318-322, 388-389, 441-445) as FEATURE rows on the device, one tick on.  The reference keeps the
+ * last T flattened states per env, featurizes all T every tick (FlatFeaturizer.fit, src/features/model_ready.py:325-354) and MLP.forward
+ * flattens the [B, T, F] features into one T * F wide input, oldest state first (src/models/dqn.py:86-90).  Here the window is kept
+ * featurized: a row of T segments of F floats -- an input row of susnet_mlp_forward / susnet_mlp_train_step with dims[0] = T * F -- and per
+ * tick only the new state's row (fresh) is produced.  Per row b, with ended = (done && done[b]) || (truncated && truncated[b]):
+ *     ended      dst[b] = fresh[b] repeated T times    (train.py:441-445: the window is refilled with the fresh first state; 318-322 at start)
+ *     otherwise  dst[b] = src[b][F:] ++ fresh[b]       (train.py:388-389: np.roll(-1), the last slot is the new state)
+ *   OUT OF PLACE by design: dst must not overlap src (nor fresh); callers ping-pong two buffers.  Values move as 32-bit patterns: NaN payloads
+ * and -0.0 survive.  done / truncated are read in place, e.g. a slot of the replay feed the stepping kernel has just written.
+ *   Served: T in 1 .. 8, F >= 1, T * F <= SUSNET_MLP_MAX_F, n >= 1; fresh / src / dst non-NULL and 4-byte aligned (rows of arbitrary F are
+ * only 4-byte aligned: every access is one dword), the byte ranges of src and dst disjoint.  Anything else: SUSNET_E_INVALID, with a
+ * message that names the field, before anything is launched.
+ *   One launch (grid-stride over chunks of rows), no LDS, no atomics.  The handle supplies the stream and error conventions only: no
+ * environment state is read, and the handle need not have its state bound. */
+typedef struct susnet_window_io {
+    const float *fresh;       /* device [n][F]: FlatFeaturizer row of the state AFTER the tick (after the auto-reset where the episode ended) */
+    const uint8_t *done;      /* device [n] or NULL */
+    const uint8_t *truncated; /* device [n] or NULL */
+    const float *src;         /* device [n][T*F]: the window before the tick, oldest state first */
+    float *dst;               /* device [n][T*F]: the window after it; must not overlap src */
+    int32_t T, F;
+    int64_t n;
+} susnet_window_io;
+int susnet_window_push(susnet_env *env, const susnet_window_io *io, void *stream);
 
 int susnet_step(susnet_env *env, const susnet_step_io *io, void *stream);
 /* susnet_policy_actions and susnet_step in ONE launch -- a tick of the acting loop (visualize.py:547-582: argmax per team, env.step):

@@ -18,6 +18,7 @@
 #include "susnet_family.h"
 #include "susnet_qnet.h"
 #include "susnet_dense.h"
+#include "susnet_window.h"
 #include "susnet_train.h"
 #include "susnet_mlp_train.h"
 #include "susnet_episodes.h"
@@ -1055,6 +1056,42 @@ extern "C" int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void
     a.n = io->n;
     a.q = io->q_out;
     HIP_TRY(qnet_dense_launch(a, static_cast<hipStream_t>(stream)));
+    return SUSNET_OK;
+}
+
+// susnet_window_push: the feature window of the acting loop, one tick on (the kernel: inst_window.hip).  Everything is checked here, before
+// the launch; as for susnet_mlp_forward the handle gives the error conventions only (no state is read: it need not be bound).
+extern "C" int susnet_window_push(susnet_env *env, const susnet_window_io *io, void *stream) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_window_push: null env / io");
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_window_push: " + what); };
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (io->T < 1 || io->T > kWinMaxT) return bad("T = " + std::to_string(io->T) + " (served: 1 .. " + std::to_string(kWinMaxT) + " states per window)");
+    if (io->F < 1) return bad("F = " + std::to_string(io->F) + " (at least one feature per state)");
+    if ((int64_t)io->T * io->F > SUSNET_MLP_MAX_F)
+        return bad("T * F = " + std::to_string((long long)io->T * io->F) + " (a window is one input row of susnet_mlp_forward: at most SUSNET_MLP_MAX_F = " +
+                   std::to_string(SUSNET_MLP_MAX_F) + ")");
+    if (io->n < 1) return bad("n = " + std::to_string((long long)io->n) + " (at least one row)");
+    if (io->n > (INT64_MAX >> 13)) return bad("n = " + std::to_string((long long)io->n) + " (the window's byte count overflows)");
+    if (!io->fresh || misaligned(io->fresh)) return bad("fresh is NULL or not 4-byte aligned");
+    if (!io->src || misaligned(io->src)) return bad("src is NULL or not 4-byte aligned");
+    if (!io->dst || misaligned(io->dst)) return bad("dst is NULL or not 4-byte aligned");
+    const uintptr_t wbytes = (uintptr_t)io->n * (uintptr_t)io->T * (uintptr_t)io->F * 4u, fbytes = (uintptr_t)io->n * (uintptr_t)io->F * 4u;
+    const auto overlap = [](const void *p, uintptr_t pn, const void *q, uintptr_t qn) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return a < b + qn && b < a + pn;
+    };
+    if (overlap(io->dst, wbytes, io->src, wbytes)) return bad("dst overlaps src (the push is out of place: ping-pong two buffers)");
+    if (overlap(io->dst, wbytes, io->fresh, fbytes)) return bad("dst overlaps fresh");
+    WindowArgs a{};
+    a.fresh = reinterpret_cast<const uint32_t *>(io->fresh);
+    a.done = io->done;
+    a.truncated = io->truncated;
+    a.src = reinterpret_cast<const uint32_t *>(io->src);
+    a.dst = reinterpret_cast<uint32_t *>(io->dst);
+    a.T = io->T;
+    a.F = io->F;
+    a.n = io->n;
+    HIP_TRY(window_push_launch(a, static_cast<hipStream_t>(stream)));
     return SUSNET_OK;
 }
 

@@ -10,7 +10,10 @@ set or layer stack can run through the dense kernel (``PolicyRollout(..., dense=
 ``env.obs``, weights read in place) and hand its Q rows to ``susnet_policy_step``: that is what ``collect`` / ``train`` / ``evaluate`` use
 on those games.  By default, and for everything else (``SpatialDQN``, stacks wider than the dense kernel serves), the network runs
 through stock PyTorch-ROCm -- which is the faster of the two at large batches -- and hands its Q rows to ``susnet_policy_step`` /
-``susnet_policy_actions``.
+``susnet_policy_actions``.  ``PolicyRollout(..., dense=True, sequence_length=T)`` acts on the reference's WINDOW of the last T states
+(train.py:318-322, 388-389, 441-445; ``run_experiment``'s default is T = 2): the policy keeps the window as feature rows ``[B, T * F]``,
+``susnet_window_push`` moves it one tick on, and the dense kernel reads it as a row of width ``T * F`` (``MLP.forward`` flattens
+``[B, T, F]`` the same way, dqn.py:86-90).
 
 * ``MLP`` mirrors reference src/models/dqn.py:72-108 (`make_mlp` 322-329: Linear + PReLU, last activation
   dropped) INCLUDING the module names, so a reference checkpoint `{"state_dict", "config"}`
@@ -205,6 +208,34 @@ def _mlp_stack(model):
     return linears, acts
 
 
+def window_push_reference(src, fresh, done=None, truncated=None):
+    """``susnet_window_push`` restated in torch (or numpy) ops, on any device: the window ``src [n, T * F]`` one tick on with the fresh
+    rows ``fresh [n, F]`` -- ``fresh`` repeated T times where ``done | truncated`` (train.py:441-445), else ``src[:, F:] ++ fresh``
+    (train.py:388-389).  float32 tensors are moved as int32 bit patterns, as the kernel moves them.  Returns a new array."""
+    n, F = fresh.shape
+    T = src.shape[1] // F
+    assert src.shape == (n, T * F), f"src is [n, T * F] = [{n}, T * {F}], got {tuple(src.shape)}"
+    if isinstance(src, torch.Tensor):
+        bits = src.dtype == torch.float32
+        s, f = (src.view(torch.int32), fresh.view(torch.int32)) if bits else (src, fresh)
+        ended = torch.zeros(n, dtype=torch.bool, device=src.device)
+        for flag in (done, truncated):
+            if flag is not None:
+                ended = ended | flag.reshape(n).to(torch.bool)
+        out = torch.where(ended.view(n, 1), f.repeat(1, T), torch.cat([s[:, F:], f], 1)).contiguous()
+        return out.view(torch.float32) if bits else out
+    import numpy as np
+
+    bits = src.dtype == np.float32
+    s, f = (src.view(np.int32), fresh.view(np.int32)) if bits else (src, fresh)
+    ended = np.zeros(n, dtype=bool)
+    for flag in (done, truncated):
+        if flag is not None:
+            ended |= np.asarray(flag).reshape(n).astype(bool)
+    out = np.ascontiguousarray(np.where(ended[:, None], np.tile(f, (1, T)), np.concatenate([s[:, F:], f], 1)))
+    return out.view(np.float32) if bits else out
+
+
 class DenseQNet:
     """A reference ``MLP`` served by ``susnet_mlp_forward``: ``MLP.forward`` (dqn.py:72-108) as one HIP kernel on feature rows in device
     memory -- any game, component set and layer stack within the kernel's widths (1..7 ``Linear(bias=True)`` layers with single-slope
@@ -294,11 +325,18 @@ class PolicyRollout:
     ``crew_model``; agent *i* of env *b* takes the imposter model's argmax if it is an imposter there, else the
     crew model's (all agents see the same flat features, as in the reference's FlatFeaturizer,
     model_ready.py:356-367).  ``crew_model=None`` = uniformly random crew via the env's sample_actions kernel.
+
+    ``sequence_length=T`` > 1 (with ``dense=True``): the networks read the WINDOW of the last T states' feature rows, oldest first
+    (train.py:318-322, 388-389, 441-445; dqn.py:86-90), so their input width is ``T * F``.  The policy owns two ``[B, T * F]`` buffers;
+    ``window_feats`` is the current one, ``q_rows()`` feeds it to the dense kernel, ``push(done, truncated)`` moves it one tick on
+    (``susnet_window_push`` with ``fresh = env.obs``, out of place: the buffers swap), ``tick()`` pushes with the flags the step
+    returned, ``reset_window()`` refills it with the current state (after ``env.reset()``).  Only dense-served networks are accepted at
+    T > 1 (``WindowedPolicyRollout`` is the torch path for everything else).
     """
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module] = None,
                  components: Sequence[str] = ("onehot_pos",), fused: bool = True, epsilon: float = 0.0, mask_dead: bool = False,
-                 dense: bool = False):
+                 dense: bool = False, sequence_length: int = 1):
         assert env.obs_config.mode == "flat" and list(env.obs_config.components) == list(components), (
             "construct the env with obs=ObsConfig('flat', components) so that step() fuses the observation")
         self.env, self.imposter_model, self.crew_model = env, imposter_model, crew_model
@@ -312,8 +350,15 @@ class PolicyRollout:
         # (profiles/dense_qnet_bench.json), so plain acting keeps the torch module on env.obs, as does anything else (SpatialDQN, wider
         # stacks)
         self.components = list(components)
-        self.fused_imposter = pack_mlp(env, imposter_model, components) if fused else None
-        self.fused_crew = pack_mlp(env, crew_model, components) if fused and crew_model is not None else None
+        T = self.sequence_length = int(sequence_length)
+        if T < 1:
+            raise ValueError(f"PolicyRollout: sequence_length = {sequence_length} (a window holds at least one state)")
+        if T > 1:  # the compiled-in layouts read ONE state's F features: they never serve a window
+            fused_nets = False
+        else:
+            fused_nets = fused
+        self.fused_imposter = pack_mlp(env, imposter_model, components) if fused_nets else None
+        self.fused_crew = pack_mlp(env, crew_model, components) if fused_nets and crew_model is not None else None
         self.dense_imposter = self._dense(imposter_model, env.n_imposter_actions) if fused and dense and self.fused_imposter is None else None
         self.dense_crew = self._dense(crew_model, env.n_crew_actions) if fused and dense and crew_model is not None and self.fused_crew is None else None
         self._packed_version = (_weights_version(imposter_model), _weights_version(crew_model))
@@ -324,12 +369,89 @@ class PolicyRollout:
         B = env.batch
         self._spatial = torch.zeros(B, 1, 1, device=env.device)  # FlatFeaturizer's dummy spatial input
         self._actions = torch.zeros(B, env.n_agents, dtype=torch.int64, device=env.device)
+        self._windows, self._window_at, self._window_generation = None, 0, None
+        if T > 1:
+            self._check_window_served(fused and dense)
+            F = env.obs.shape[-1]
+            self._windows = [torch.zeros(B, T * F, dtype=torch.float32, device=env.device) for _ in range(2)]  # ping / pong
 
     def _dense(self, model, n_actions):
         net = DenseQNet(self.env, model)
-        if net is None or net.dims[0] != self.env.obs.shape[-1] or net.dims[-1] != n_actions:
+        if net is None or net.dims[0] != self.sequence_length * self.env.obs.shape[-1] or net.dims[-1] != n_actions:
             return None
         return net
+
+    def _check_window_served(self, asked: bool) -> None:
+        """At ``sequence_length`` > 1 there is no torch path in this class: a network the dense kernel does not serve is an error."""
+        from . import _lib as L
+
+        env, T = self.env, self.sequence_length
+        F = env.obs.shape[-1]
+        need = (f"PolicyRollout: sequence_length = {T} is served through the dense kernel only (dense=True): reference MLPs whose input is the "
+                f"flattened window, T * F = {T} * {F} = {T * F} <= {L.MLP_MAX_F} wide, on a game with at most 16 actions per team "
+                "(WindowedPolicyRollout runs everything else through torch)")
+        if not asked:
+            raise ValueError(need + "; got dense=False")
+        if T > L.WINDOW_MAX_T or T * F > L.MLP_MAX_F:
+            raise ValueError(need + f"; this window is {T} states, {T * F} features wide")
+        if max(env.n_imposter_actions, env.n_crew_actions) > 16:
+            raise ValueError(need + f"; this game has {env.n_imposter_actions} / {env.n_crew_actions} actions")
+        for team, model, net in (("imposter", self.imposter_model, self.dense_imposter), ("crew", self.crew_model, self.dense_crew)):
+            if model is not None and net is None:
+                stack = _mlp_stack(model)
+                got = f"an MLP with {stack[0][0].in_features} inputs" if stack is not None else type(model).__name__
+                raise ValueError(need + f"; the {team} model is {got}")
+
+    @property
+    def window_feats(self) -> Optional[torch.Tensor]:
+        """The current feature window ``[B, T * F]`` (oldest state first), or None at ``sequence_length`` 1."""
+        return None if self._windows is None else self._windows[self._window_at]
+
+    @torch.no_grad()
+    def reset_window(self) -> torch.Tensor:
+        """``window_feats`` = ``env.obs`` repeated T times (train.py:318-322): the window of a fresh episode, or of the current state."""
+        assert self._windows is not None, "reset_window: built with sequence_length = 1, there is no window"
+        env = self.env
+        self._windows[self._window_at].copy_(env.obs.repeat(1, self.sequence_length))
+        self._window_generation = getattr(env, "reset_generation", 0)
+        return self.window_feats
+
+    def load_window(self) -> torch.Tensor:
+        """The current buffer, for a caller that is about to WRITE the window itself (``DeviceReplayBuffer.collect`` featurizes its
+        carried raw window into it): marks the window as belonging to the env's current episode generation."""
+        assert self._windows is not None, "load_window: built with sequence_length = 1, there is no window"
+        self._window_generation = getattr(self.env, "reset_generation", 0)
+        return self.window_feats
+
+    def _window_current(self) -> None:
+        if self._window_generation != getattr(self.env, "reset_generation", 0):  # never filled, or the env was reset() since
+            self.reset_window()
+
+    @torch.no_grad()
+    def push(self, done: Optional[torch.Tensor] = None, truncated: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The window one tick on (``susnet_window_push``, one launch, asynchronous): ``env.obs`` -- the state AFTER the tick -- enters as the
+        newest state, or fills the window where ``done | truncated`` (bool / uint8 ``[B]`` on the env's device, read in place; None: no row
+        ended).  The two buffers swap; returns the new ``window_feats``."""
+        import ctypes as C
+
+        from . import _lib as L
+
+        assert self._windows is not None, "push: built with sequence_length = 1, there is no window"
+        env = self.env
+        self._window_current()
+        src, dst = self._windows[self._window_at], self._windows[self._window_at ^ 1]
+        io = L.WindowIO()
+        io.fresh, io.src, io.dst = env.obs.data_ptr(), src.data_ptr(), dst.data_ptr()
+        for name, flag in (("done", done), ("truncated", truncated)):
+            if flag is not None:
+                assert flag.dtype in (torch.bool, torch.uint8) and flag.numel() == env.batch and flag.is_contiguous() and flag.device == env.device, (
+                    f"push: {name} must be a contiguous bool / uint8 [{env.batch}] tensor on {env.device}")
+                setattr(io, name, flag.data_ptr())
+        io.T, io.F, io.n = self.sequence_length, env.obs.shape[-1], env.batch
+        with env._on_device():
+            L.check(env.lib.susnet_window_push(env._h, C.byref(io), env._stream()))
+        self._window_at ^= 1
+        return dst
 
     def _team_q(self, fused, dense, model, feats):
         if fused is not None:
@@ -360,6 +482,9 @@ class PolicyRollout:
         env = self.env
         self.refresh_weights(force=False)
         feats = env.obs  # [B, F] float32, refreshed by reset()/step()
+        if self._windows is not None:  # [B, T * F]: the last T states' rows, oldest first
+            self._window_current()
+            feats = self.window_feats
         q_imp = self._team_q(self.fused_imposter, self.dense_imposter, self.imposter_model, feats)
         q_crew = None
         if self.crew_model is not None:
@@ -382,9 +507,11 @@ class PolicyRollout:
         fits = max(env.n_imposter_actions, env.n_crew_actions) <= 16 and (q_crew is not None or env.rng_kind == "philox")
         if fits:
             _, rew, done, trunc, _, a = env.policy_step(q_imp, q_crew, actions_out=self._actions, epsilon=self.epsilon, mask_dead=self.mask_dead)
-            return a, rew, done, trunc
-        a = self.act()
-        _, rew, done, trunc, _ = env.step(a)
+        else:
+            a = self.act()
+            _, rew, done, trunc, _ = env.step(a)
+        if self._windows is not None:  # (the step has written the new state's row into env.obs)
+            self.push(done, trunc)
         return a, rew, done, trunc
 
     @torch.no_grad()
@@ -439,6 +566,9 @@ class PolicyRollout:
         obs_before`` tensors with a leading ``[n_ticks]`` dimension that every replay overwrites (parity tests).  Needs an env
         built with ``rng='philox', check_errors=False, export_state=False`` (both would synchronise inside the capture)."""
         env = self.env
+        if self._windows is not None:
+            raise ValueError(f"capture: sequence_length = {self.sequence_length}: the window's two buffers swap every tick, a captured graph would "
+                             "freeze their pointers; graph capture serves sequence_length = 1")
         assert env.rng_kind == "philox", "graph replay needs the counter-based production stream"
         assert not env.check_errors and not env.export_state, "construct the env with check_errors=False, export_state=False"
         env.device_tick(True)

@@ -159,7 +159,14 @@ class DeviceReplayBuffer:
         (``susnet_qnet_policy_rollout``: the weights are fixed within a block anyway).  The sequence window carries over between calls
         (``reset_collection`` after an ``env.reset()``).  Row order = tick-major, env-minor; with ``batch=1``,
         ``rng='numpy'`` and two networks the ring equals the reference's for the same numpy seed and weights
-        (tests/golden/collect_*.npz).  Returns the number of transitions added."""
+        (tests/golden/collect_*.npz).
+
+        ``policy.sequence_length`` = T > 1 (``PolicyRollout(dense=True, sequence_length=T)``; it must equal ``trajectory_size``): the
+        networks act on the window of the last T states.  At the start of every call the policy's feature window is derived from the
+        carried raw window (ONE ``susnet_featurize`` launch over its ``B * T`` rows), so it follows the raw window under every rule above;
+        per tick after the first, ``susnet_window_push`` moves it one tick on, reading the flags ``policy_tick_into`` wrote into the feed in
+        place (tests/golden/window/wcollect_*.npz pin the ring against the reference's at T = 2 and 3).  Returns the number of
+        transitions added."""
         import ctypes as C
 
         from . import _lib as L
@@ -179,6 +186,11 @@ class DeviceReplayBuffer:
             raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
         assert env.flattened_state_size == self.state_size and env.n_agents == self.n_agents and env.n_imposters == self.n_imposters
         T, B = self.trajectory_size, env.batch
+        windowed = getattr(policy, "sequence_length", 1) > 1
+        if windowed:
+            assert dense, "collect: a policy with sequence_length > 1 acts through the dense kernel"
+            assert policy.sequence_length == T, (f"collect: the policy acts on windows of {policy.sequence_length} states, the ring stores "
+                                                 f"windows of {T} (trajectory_size)")
         # the carried window and the feed block belong to ONE env (identity, device) between two of its resets: another env of the same
         # batch, or the same env after reset(), starts from its own current state
         owner = (id(env), str(env.device), getattr(env, "reset_generation", 0))
@@ -195,6 +207,13 @@ class DeviceReplayBuffer:
         if feed is None or feed["n_ticks"] != n_block or feed["actions"].shape[1] != B:
             feed = self._collect_feed = env.alloc_feed(n_block)
         io = self._ring_io(env, feed, self._collect_window)
+        if windowed:  # the feature window of the carried raw window: [B * T] rows of F = [B] rows of T * F, oldest state first
+            spec = env._make_obs(ObsConfig("flat", policy.components), 1, rows=1)[0]
+            spec.out = policy.load_window().data_ptr()
+            rows = self._collect_window
+            with torch.cuda.device(env.device):
+                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], B * T, C.byref(spec), env._stream()))
+        last = None  # the feed slot of the previous tick of this call
         # one launch per BLOCK where the env serves the whole tick in one kernel and the block's observation slots are 16-byte aligned
         fused_block = (one_launch_per_block and not dense and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
                        and (n_block == 1 or (B * self.state_size) % 16 == 0))
@@ -207,8 +226,11 @@ class DeviceReplayBuffer:
             elif dense:  # a game / layer stack without a fused path: the dense forward(s) on the current flat observation, then the tick
                 for t in range(n):
                     env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
+                    if windowed and last is not None:  # the previous tick's flags, read where the stepping kernel wrote them
+                        policy.push(feed["done"][last], feed["truncated"][last])
                     q_imp, q_crew = policy.q_rows()
                     env.policy_tick_into(feed, t, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                    last = t
             else:
                 for t in range(n):
                     env.policy_tick_into(feed, t, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)

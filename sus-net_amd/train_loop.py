@@ -259,15 +259,19 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
     entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
     ``dense_train=True`` (opt-in): the trainer is built with ``dense=True`` -- off the compiled-in layouts the train step is
-    ``susnet_mlp_train_step`` instead of the torch loop."""
+    ``susnet_mlp_train_step`` instead of the torch loop.  ``sequence_length`` = T > 1 (the reference's default is 2, train.py:160): the
+    networks read the flattened window of the last T states, ``T * F`` inputs (dqn.py:86-90); acting, collecting and the train step
+    then all go through the dense kernels (the trainer is built ``dense=True`` whatever ``dense_train`` says), and a network that is not
+    dense-served at that T is a ``ValueError``."""
     components = list(components)
+    sequence_length = int(sequence_length)
     if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
         raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
-    if sequence_length != 1:
-        raise ValueError("run_experiment: a window of one state is served (sequence_length=1): the Q-network kernel and "
-                         "susnet_dqn_train_step read one state")
     if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
         raise ValueError("run_experiment: served are reference MLPs (a crew model of None acts randomly)")
+    # (built before anything is written: at sequence_length > 1 a network that is not dense-served is refused here, naming sequence_length
+    # and the input width T * F it would need)
+    policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True, sequence_length=sequence_length)
     base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
     experiment_dir = base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     experiment_dir.mkdir(parents=True, exist_ok=True)
@@ -278,9 +282,12 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                                 learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval)
     (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
 
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True)
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
-                                   train_crew=train_crew, policy=policy, dense=dense_train)
+                                   train_crew=train_crew, policy=policy, dense=dense_train or sequence_length > 1,
+                                   sequence_length=sequence_length if sequence_length > 1 else None)
+    if sequence_length > 1 and any(trainer.trained) and not trainer.dense:
+        raise ValueError(f"run_experiment: sequence_length = {sequence_length}: the trained networks are not served by susnet_mlp_train_step on "
+                         f"windows of {sequence_length} states (needed: reference MLP stacks with a network input of T * F)")
     scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
     metrics = EpisodicMetricHandler()
     ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
@@ -383,17 +390,21 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
 
 @torch.no_grad()
 def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, block_ticks: int = 64,
-             mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None) -> dict:
+             mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None, sequence_length: int = 1) -> dict:
     """How a pair of models plays: ``env.reset()``, then the acting loop for ``n_ticks`` lockstep ticks in blocks of ``block_ticks`` (one
     policy rollout launch into a feed + one ``EpisodeLog.update`` per block; no ring, no trainer), and ONE read-back at the end.
     ``crew_model=None``: a random crew.  Returns ``episodes``, ``imposter_win_rate``, ``crew_win_rate``, ``truncation_rate``,
     ``mean_imposter_return``, ``mean_crew_return`` (``gamma``-discounted; 1.0 = plain sums), ``mean_length`` and the mean of every info
     counter per finished episode (``mean_<counter>``), plus ``dropped`` (episodes beyond ``capacity``, not in the means) and ``ticks``.
-    Rates and means of zero episodes are NaN."""
+    Rates and means of zero episodes are NaN.  ``sequence_length`` = T > 1: models that read the window of the last T states (``T * F``
+    inputs), acting as in ``DeviceReplayBuffer.collect``: the dense kernel on the policy's feature window, ``susnet_window_push`` between
+    ticks."""
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
     components = list(components)
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead, dense=True)
+    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead, dense=True,
+                           sequence_length=sequence_length)
+    windowed = policy.sequence_length > 1
     imp_served, crew_served, dense = served_by_kernels(policy)
     if not imp_served or not crew_served:
         raise ValueError("evaluate: served are reference MLPs a network kernel runs (the compiled-in feature layouts, or the dense kernel); "
@@ -415,6 +426,7 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     log = EpisodeLog(env, gamma=gamma, capacity=capacity)
     feed = env.alloc_feed(n_block)
     t = 0
+    last = None  # the feed slot of the previous tick
     while t < n_ticks:
         n = min(n_block, n_ticks - t)
         if fused:
@@ -422,8 +434,14 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
         elif dense:  # the dense forward(s) on the current flat observation, then susnet_policy_step into the feed
             for k in range(n):
                 env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
+                if windowed:  # the first tick acts on the fresh state T times (train.py:318-322), later ones on the pushed window
+                    if last is None:
+                        policy.reset_window()
+                    else:
+                        policy.push(feed["done"][last], feed["truncated"][last])
                 q_imp, q_crew = policy.q_rows()
                 env.policy_tick_into(feed, k, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                last = k
         else:
             for k in range(n):
                 env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
@@ -453,7 +471,8 @@ def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:
 def evaluate_checkpoints(experiment_dir, env, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, **kw) -> dict:
     """``evaluate`` for every checkpoint pair ``imposter_mlp_<p>.pt`` / ``crew_mlp_<p>.pt`` that ``run_experiment`` wrote into
     ``experiment_dir`` (a run without a crew model: the imposters against a random crew), as a table ``{<p>: summary}`` in the order of
-    training progress (``"0"``, ..., ``"100%"``)."""
+    training progress (``"0"``, ..., ``"100%"``).  Further keywords go to ``evaluate`` (``sequence_length=T`` for a run trained on
+    windows)."""
     d = pathlib.Path(experiment_dir)
     found = {}
     for path in d.glob("imposter_mlp_*.pt"):

@@ -6,8 +6,10 @@ from a ``DeviceReplayBuffer`` (``ReplayBuffer.sample``, src/replay_memory.py:75-
   team) update one gradient launch and one reduce + Adam launch, no host synchronisation, and the teams' packed images (what
   ``PolicyRollout`` acts with) are rewritten on the device.
 * dense HIP path (``susnet_mlp_train_step``, csrc/susnet_mlp_train.h; opt-in: ``DeviceDQNTeamTrainer(..., dense=True)``): reference
-  ``MLP``s of any served layer stack on ANY game and component set, a window of one state, one imposter.  The batch's states are gathered
-  and featurized (the FLAT featurizer kernel) into reused buffers, then one call: the same launches per update, no host synchronisation.
+  ``MLP``s of any served layer stack on ANY game and component set, one imposter, a window of T >= 1 states: the networks read the
+  flattened window, ``T * F`` inputs (dqn.py:86-90), and T is the ring's ``trajectory_size``.  The batch's ``[n, T, S]`` windows are
+  gathered and featurized as ``n * T`` rows (the FLAT featurizer kernel) into reused buffers -- ``[n * T, F]`` IS the ``[n][T * F]``
+  layout the step reads --, then one call: the same launches per update, no host synchronisation.
   There is no packed image: a ``PolicyRollout(dense=True)`` reads the parameters in place and follows the step without a refresh.
 * torch path (``torch_train_step``): the same algorithm in torch ops for anything else -- ``SpatialDQN``, other layer stacks, longer
   windows, CPU tensors.
@@ -83,10 +85,12 @@ class DeviceDQNTeamTrainer:
     ``components``).  ``featurizer``: what the torch path featurizes the ring's states with (``features.FlatFeaturizer`` over
     ``components`` by default; a ``SpatialDQN`` needs a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of the same env).
     ``dense=True`` (opt-in): what ``susnet_dqn_train_step`` does not serve goes to ``susnet_mlp_train_step`` where that serves it
-    (``uses_dense``), before the torch path."""
+    (``uses_dense``), before the torch path.  ``sequence_length``: the window length T the trained networks read (their input is
+    ``T * F`` wide); None (default): T is taken from the networks' input width, ``dims[0] / F``."""
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module], components: Sequence[str], lr: float, gamma: float,
-                 train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None, dense: bool = False):
+                 train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None, dense: bool = False,
+                 sequence_length: Optional[int] = None):
         if env.n_imposters >= 2:
             raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
                              "(src/train.py:83) has n_imposters * N entries")
@@ -127,6 +131,7 @@ class DeviceDQNTeamTrainer:
         self._ws, self._losses = None, None
         # the dense step: each trained team's [F, h.., n_actions] where susnet_mlp_train_step serves it
         self._dense_dims = [self._stack_dims(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self.sequence_length = None if sequence_length is None else int(sequence_length)  # (the dense step's T: settled by _dense_served)
         self.dense = (bool(dense) and self.device.type == "cuda" and any(self.trained) and featurizer is None
                       and all(c in L.FLAT_COMPONENTS for c in self.components)
                       and all(d is not None for d, tr in zip(self._dense_dims, self.trained) if tr) and self._dense_served())
@@ -207,8 +212,9 @@ class DeviceDQNTeamTrainer:
 
     def uses_dense(self, ring) -> bool:
         """Whether ``ring`` is trained on by ``susnet_mlp_train_step``: a ``dense=True`` trainer of reference MLP stacks within the
-        kernel's bounds, cuda tensors, a window of one state -- and ``uses_hip`` does not hold (that path goes first)."""
-        return self.dense and not self.uses_hip(ring) and ring.trajectory_size == 1 and ring.states.device == self.device
+        kernel's bounds whose input is the ring's window, ``trajectory_size * F`` wide, cuda tensors -- and ``uses_hip`` does not hold
+        (that path goes first)."""
+        return self.dense and not self.uses_hip(ring) and ring.trajectory_size == self.sequence_length and ring.states.device == self.device
 
     def _dense_io(self) -> "L.MlpTrainIO":
         io = L.MlpTrainIO()
@@ -229,8 +235,11 @@ class DeviceDQNTeamTrainer:
         from .env import ObsConfig
 
         F = self.env._make_obs(ObsConfig("flat", self.components), 1, rows=1)[1].shape[-1]
-        if any(d[0] != F for d, tr in zip(self._dense_dims, self.trained) if tr):
-            return False  # the networks do not read this featurizer's rows
+        widths = set(d[0] for d, tr in zip(self._dense_dims, self.trained) if tr)
+        T = self.sequence_length if self.sequence_length is not None else max(widths) // F
+        if widths != {T * F} or not 1 <= T <= L.WINDOW_MAX_T or T * F > L.MLP_MAX_F:
+            return False  # the networks do not read windows of this featurizer's rows
+        self.sequence_length = T
         io = self._dense_io()
         io.max_size, io.n = 1, 1
         nbytes = C.c_uint64()
@@ -277,11 +286,12 @@ class DeviceDQNTeamTrainer:
         return self._losses.clone()  # (a new tensor per step, as the torch path returns; enqueued, no host wait)
 
     def _dense_step(self, ring, idx):
-        """Gather + featurize the batch's states and next states into reused buffers, then ``susnet_mlp_train_step``: nothing waits on the
-        host (with ``env.check_errors`` the featurizer's row check is polled, as ``env.featurize`` does)."""
+        """Gather + featurize the batch's windows and next windows (``[n, T, S]``, as ``n * T`` rows) into reused buffers, then
+        ``susnet_mlp_train_step`` on the ``[n][T * F]`` rows: nothing waits on the host (with ``env.check_errors`` the featurizer's row
+        check is polled, as ``env.featurize`` does)."""
         from .env import ObsConfig
 
-        env, n = self.env, int(idx.numel())
+        env, n, T = self.env, int(idx.numel()), ring.trajectory_size
         for t in range(2):
             self._state_to_flat(t)
         if self._losses is None:
@@ -292,7 +302,7 @@ class DeviceDQNTeamTrainer:
                 oc = ObsConfig("flat", self.components)
                 self._dense_bufs = (n, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
                                     torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
-                                    env._make_obs(oc, 1, rows=n), env._make_obs(oc, 1, rows=n))
+                                    env._make_obs(oc, 1, rows=n * T), env._make_obs(oc, 1, rows=n * T))
             _, rows, next_rows, (spec, feat, _), (next_spec, next_feat, _) = self._dense_bufs
             torch.index_select(ring.states, 0, idx, out=rows)
             torch.index_select(ring.next_states, 0, idx, out=next_rows)
@@ -309,8 +319,8 @@ class DeviceDQNTeamTrainer:
         with torch.cuda.device(self.device):
             if n > 0:
                 dt = env._ROW_DTYPES[rows.dtype]
-                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), dt, n, C.byref(spec), env._stream()))
-                L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n, C.byref(next_spec), env._stream()))
+                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), dt, n * T, C.byref(spec), env._stream()))
+                L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n * T, C.byref(next_spec), env._stream()))
                 if env.check_errors:
                     env.poll_errors()
             L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
