@@ -1020,8 +1020,10 @@ struct BufDst {
     // guard; on gfx950 that was measured to be wrong: cfg4 records showed the NEXT tick's action digits in one dword
     // of a few waves).  So the tick offset is added on the vector unit here (one v_add per tick and destination,
     // the +off constants go into the instruction's immediate) and the offset field stays 0.
+    // AUX: the store's cache policy bits (0 = default, 2 = nt, 16 = sc1, write-through); see kRecordStoreAux.
+    template <int AUX = 0>
     __device__ __forceinline__ void st128(uint32_t off, uint32_t a, uint32_t b, uint32_t c, uint32_t d) const {
-        const u32x4 w = {a, b, c, d}; __builtin_amdgcn_raw_buffer_store_b128(w, r, vo + so + off, 0, 0);
+        const u32x4 w = {a, b, c, d}; __builtin_amdgcn_raw_buffer_store_b128(w, r, vo + so + off, 0, AUX);
     }
 };
 __device__ __forceinline__ BufDst make_buf_dst(void *base, uint64_t bytes, uint32_t lane_off) {

@@ -1321,6 +1321,16 @@ __global__ __launch_bounds__(kBlock) void k_rollout_swar2(Consts c, State s, Rol
     }
 }
 
+// Cache policy of the 1v1 kernel's compact record store (OUT_RECORD16: written once, never read by the kernel): the buffer store's aux bits,
+// 0 = default, 2 = nt (non-temporal), 16 = sc1 (write-through).  nt: same-box alternated runs of the three forms (profiles/duel_stage_ab.json,
+// DESIGN.md section 5) gave 99.2-101.5 us per 512-tick launch with the default, 88.5-90.1 with sc1 and 87.3-88.2 with nt, against 85.4-85.9
+// with every record store dropped by the range check (the kernel's issue time); on the wall map 95.7-96.5 / 91.0-91.7 / 91.6-92.2.  The bytes
+// are the same.  SUSNET_EXP_REC_AUX: diagnostic builds of this unit (tools/build_variant_tu.sh).
+#ifndef SUSNET_EXP_REC_AUX
+#define SUSNET_EXP_REC_AUX 2
+#endif
+constexpr int kRecordStoreAux = SUSNET_EXP_REC_AUX;
+
 // Fused random rollout of the 1v1 no-walls game (susnet_duel.h): the headline kernel.  Same contract as k_rollout for the
 // modes OUT_NONE / OUT_TRAJ / OUT_TRAJ_RAW8; RNG = the production stream or caller-supplied words (numpy parity).
 // WALLS: the wall-map flavour of the step (susnet_duel.h DuelWallTable; Consts::duel_walls)
@@ -1376,7 +1386,11 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
     // launch limit (2^31 - 1 bytes unless the caller set a smaller one), so nt * kRecBytes * B < 2^31.  Lanes without an environment (ragged
     // last wave, fewer than 64 environments per wave) have left above: the range check sees the per-lane offset and the whole launch's size
     // only, so it would not drop a stray lane's store into the next tick's slab.
+#ifdef SUSNET_EXP_DUEL_REC_DROP // diagnostic builds only: the record descriptor spans 0 bytes, every record store is issued and dropped -- NO records
+    BufDst drec = make_buf_dst(a.record, 0ull, (uint32_t)bl * kRecBytes);
+#else
     BufDst drec = make_buf_dst(a.record, nt * kRecBytes * B, (uint32_t)bl * kRecBytes);
+#endif
     const uint32_t rec_slab = kRecBytes * (uint32_t)c.B;
     // the terminal states (replay feed): bound or not is a fact of the launch -- without the tensor the descriptor spans 0 bytes and the range
     // check drops the two stores, so the episode-end block carries no test of the pointer
@@ -1513,7 +1527,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_duel(Consts c, State s, Roll
             drec.st32(16u, duel_alive_bytes(d));
         }
         if (kRec16) // rewards | x0 y0 x1 y1 | alive0 alive1, a0 | a1 << 3 | done << 6 | truncated << 7, 0: ONE store, a whole 16-byte piece of a line
-            drec.st128(0u, __float_as_uint(r0), __float_as_uint(r1), d.pq - k01, duel_alive_bytes(d) | ((a0 | (a1 << 3) | (done << 6) | (trunc << 7)) << 16));
+            drec.st128<kRecordStoreAux>(0u, __float_as_uint(r0), __float_as_uint(r1), d.pq - k01, duel_alive_bytes(d) | ((a0 | (a1 << 3) | (done << 6) | (trunc << 7)) << 16));
         if constexpr (kFlat) { // onehot_pos of the state after the step (and after an in-launch reset)
             const uint32_t pos = d.pq - k01;
             const uint32_t fx[2] = {pos & 0xffu, (pos >> 16) & 0xffu}, fy[2] = {(pos >> 8) & 0xffu, pos >> 24}, fal[2] = {d.lv & 1u, d.lv >> 31};
