@@ -1,7 +1,9 @@
 """Compile sus-net_amd/csrc/*.hip -> sus-net_amd/libsusnet_hip.so for gfx950 (in-tree).
 
-One object per translation unit (susnet_capi.hip = host side + the small kernels; inst_*.hip = one compiled-in
-configuration of the stepping kernels each), compiled in parallel, then linked into ONE shared library."""
+One object per translation unit (susnet_capi.hip = the handle and the acting side of the C ABI + their small kernels;
+susnet_capi_ring.hip / susnet_capi_train.hip / susnet_capi_episodes.hip = the replay ring, the DQN learners and the episode
+bookkeeping, each entry point with its kernels; inst_*.hip = one compiled-in configuration of the stepping kernels each, the
+Q-network, window and dense-learner kernels), compiled in parallel, then linked into ONE shared library."""
 from __future__ import annotations
 
 import glob
@@ -24,6 +26,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-p
 # (+0.7 %), the wall-map flavour 3 % slower (300.9 -> 292.1 G, gpurun_out/r05ad).  Nor for susnet_capi.hip: its kernels (feature rows,
 # ring append, reset, observe) run many waves per SIMD and live on occupancy -- under max-ilp k_ring_append goes from 69 to 77 vector
 # registers (7 -> 6 waves), k_featurize / k_observe from 83 to 105 (5 -> 4)
+# -- nor for the units carved out of it (susnet_capi_*.hip: ring, learners, episodes).  The dense learner's kernels (inst_mlp_train.hip) are
+# under max-ilp by their unit's name; they were tested and timed in that form and nobody has measured the alternative
 ILP_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
 

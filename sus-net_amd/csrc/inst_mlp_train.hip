@@ -1,20 +1,8 @@
 // the dense learner's kernels (susnet_mlp_train.h: susnet_mlp_train_step) -- a translation unit of its own
 #include "susnet_mlp_train.h"
 
-#include <atomic>
-
-// susnet_train.h's device functions (tr_mfma, tr_forward_layer, tr_backward_layer) are used here unchanged.  Its four kernels that are not
-// templates belong to susnet_capi.hip, which launches them; in this unit they get names of their own so the two objects link.
-#include "susnet_qnet.h" // (susnet_train.h's pack kernels name QNet)
-#define k_train_select k_train_select_mt_
-#define k_train_sweep_select k_train_sweep_select_mt_
-#define k_train_adam k_train_adam_mt_
-#define k_train_sweep_adam k_train_sweep_adam_mt_
-#include "susnet_train.h"
-#undef k_train_select
-#undef k_train_sweep_select
-#undef k_train_adam
-#undef k_train_sweep_adam
+#include "susnet_host.h" // lds_opt_in
+#include "susnet_train_core.h"
 
 namespace susnet {
 
@@ -25,49 +13,12 @@ constexpr int kMtOH0 = 0, kMtOH1 = kMtBuf, kMtODA = 2 * kMtBuf, kMtODB = 3 * kMt
 constexpr int kMtLdsBytes = kMtLdsFloats * 4;
 static_assert(kMtLdsBytes <= 160 * 1024, "gfx950 LDS");
 static_assert(kMtMaxOut <= kMtMaxHidden && kTrThreads >= kMtMaxHidden, "a thread per unit for the bias gradients");
-constexpr int kMtMaxDevices = 64;
 
 // ---- k_mlp_train_select: ONE workgroup of kTrThreads; tr_select with batch positions in the lists ----
 __global__ __launch_bounds__(kTrThreads) void k_mlp_train_select(MlpTrainBatch b, int32_t *lists, int32_t *counts, float *gacc0, int P0, float *gacc1,
                                                                  int P1, float *losses) {
     extern __shared__ int32_t mt_scan[];
-    const int t = threadIdx.x;
-    const int64_t N = b.n;
-    for (int p = t; p < P0; p += kTrThreads) gacc0[p] = 0.0f;
-    for (int p = t; p < P1; p += kTrThreads) gacc1[p] = 0.0f;
-    if (t < 2) losses[t] = 0.0f;
-    const int64_t chunk = (N + kTrThreads - 1) / kTrThreads, lo = (int64_t)t * chunk, hi = lo + chunk < N ? lo + chunk : N;
-    for (int agent = 0; agent < b.A; agent++) {
-        int32_t c = 0;
-        for (int64_t s = lo; s < hi; s++) {
-            int64_t r = b.idx[s];
-            r = r < 0 ? 0 : (r >= b.max_size ? b.max_size - 1 : r);
-            c += (int)b.imposters[r * b.n_imp] == agent ? 1 : 0;
-        }
-        mt_scan[t] = c;
-        __syncthreads();
-        for (int off = 1; off < kTrThreads; off <<= 1) { // inclusive Hillis-Steele scan
-            const int32_t v = t >= off ? mt_scan[t - off] : 0;
-            __syncthreads();
-            mt_scan[t] += v;
-            __syncthreads();
-        }
-        const int32_t total = mt_scan[kTrThreads - 1];
-        int32_t pi = mt_scan[t] - c;                  // imposter rows before this chunk
-        int32_t pc = (int32_t)(lo < N ? lo : N) - pi; // crew rows before this chunk
-        int32_t *li = tr_list(lists, N, agent, 0), *lc = tr_list(lists, N, agent, 1);
-        for (int64_t s = lo; s < hi; s++) {
-            int64_t r = b.idx[s];
-            r = r < 0 ? 0 : (r >= b.max_size ? b.max_size - 1 : r);
-            if ((int)b.imposters[r * b.n_imp] == agent) li[pi++] = (int32_t)s;
-            else lc[pc++] = (int32_t)s;
-        }
-        if (t == 0) {
-            counts[2 * agent] = total;
-            counts[2 * agent + 1] = (int32_t)N - total;
-        }
-        __syncthreads();
-    }
+    tr_select<true>(b, b.idx, b.n, lists, counts, gacc0, P0, gacc1, P1, losses, mt_scan);
 }
 
 // layer 1 from the feature rows in global memory: Z[n][s] = b[n] + sum_k W[n][k] X[pos[s]][k]; a column past nvalid is a zero operand
@@ -247,12 +198,7 @@ __global__ __launch_bounds__(kTrThreads) void k_mlp_train_grad(MlpTrainBatch b, 
 #pragma unroll
     for (int q = 0; q < kMtMaxLayers; q++) {
         if (q < nl) { // q < nl - 1: the slope behind layer q; q == nl - 1: the loss
-            red[t] = q < nl - 1 ? sacc[q < 6 ? q : 5] : lacc;
-            __syncthreads();
-            for (int off = kTrThreads / 2; off > 0; off >>= 1) {
-                if (t < off) red[t] += red[t + off];
-                __syncthreads();
-            }
+            tr_block_sum(q < nl - 1 ? sacc[q < 6 ? q : 5] : lacc, red, t);
             if (t == 0) out[q < nl - 1 ? net.oA[q < 6 ? q : 5] : net.P] = red[0];
             __syncthreads();
         }
@@ -268,15 +214,8 @@ hipError_t mlp_train_select_launch(const MlpTrainBatch &b, int32_t *lists, int32
 hipError_t mlp_train_grad_launch(const MlpTrainBatch &b, const MlpTrainNet &net, const float *prm, const float *tgt, const int32_t *lists,
                                  const int32_t *counts, int agent, int team, float gamma, float *partial, float *zsave, float *step, int G, hipStream_t st) {
     // the kernel's dynamic-LDS ceiling, set once per device (not repeated inside a capture after the first eager step)
-    static std::atomic<bool> opted[kMtMaxDevices];
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    const bool known = dev >= 0 && dev < kMtMaxDevices;
-    if (!known || !opted[dev].load(std::memory_order_acquire)) {
-        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_train_grad), hipFuncAttributeMaxDynamicSharedMemorySize, kMtLdsBytes))
-            return e;
-        if (known) opted[dev].store(true, std::memory_order_release);
-    }
+    static LdsOptIn opted;
+    if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_mlp_train_grad), kMtLdsBytes, opted)) return e;
     hipLaunchKernelGGL(k_mlp_train_grad, dim3((unsigned)G), dim3(kTrThreads), kMtLdsBytes, st, b, net, prm, tgt, lists, counts, agent, team, gamma, partial,
                        zsave, step);
     return hipGetLastError();

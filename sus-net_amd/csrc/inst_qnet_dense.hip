@@ -2,7 +2,7 @@
 // Q-network units
 #include "susnet_dense.h"
 
-#include <atomic>
+#include "susnet_host.h" // lds_opt_in
 
 namespace susnet {
 
@@ -130,16 +130,8 @@ size_t qnet_dense_lds(DenseArgs &a) {
 hipError_t qnet_dense_launch(DenseArgs a, hipStream_t st) {
     const size_t lds = qnet_dense_lds(a);
     if (lds > kDnLdsNoOptIn) { // the opt-in to a large dynamic LDS block: once per device, off the per-tick path after that
-        static std::atomic<bool> opted[kDnMaxDevices];
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev)) return e;
-        const bool known = dev >= 0 && dev < kDnMaxDevices;
-        if (!known || !opted[dev].load(std::memory_order_acquire)) {
-            if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_qnet_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   2 * kDnMaxHidden * kDnRows * 4))
-                return e;
-            if (known) opted[dev].store(true, std::memory_order_release);
-        }
+        static LdsOptIn opted;
+        if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_qnet_dense), 2 * kDnMaxHidden * kDnRows * 4, opted)) return e;
     }
     const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
     hipLaunchKernelGGL(k_qnet_dense, dim3((unsigned)(tiles < kDnMaxGrid ? tiles : kDnMaxGrid)), dim3(kDnThreads), lds, st, a);

@@ -1,10 +1,13 @@
-// susnet_capi.hip -- kernels + the C ABI declared in include/susnet.h (libsusnet_hip.so, gfx950 only).
+// susnet_capi.hip -- the handle and the acting side of the C ABI declared in include/susnet.h (libsusnet_hip.so, gfx950 only): lifecycle,
+// reset, sample, step, policy, rollout, observe, featurize, scent, the Q-network pack and forward entry points, state import / export,
+// the tick and error words, with their small kernels.  The rest of the ABI lives in units of its own behind susnet_host.h:
+// susnet_capi_ring.hip (susnet_ring_append), susnet_capi_train.hip (the DQN learners), susnet_capi_episodes.hip (susnet_episode_stats);
+// the stepping, Q-network, window and dense-learner kernels are the inst_*.hip units.
 //
-// Build:  hipcc -O3 --offload-arch=gfx950 -shared -fPIC -o libsusnet_hip.so susnet_capi.hip
+// Build:  sus-net_amd/build_hip.py (one object per csrc/*.hip, linked into one shared library)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -19,9 +22,7 @@
 #include "susnet_qnet.h"
 #include "susnet_dense.h"
 #include "susnet_window.h"
-#include "susnet_train.h"
-#include "susnet_mlp_train.h"
-#include "susnet_episodes.h"
+#include "susnet_host.h"
 
 namespace susnet {
 SUSNET_DECLARE(GenericSpec) SUSNET_DECLARE(SpecCfg2) SUSNET_DECLARE(SpecCfg3) SUSNET_DECLARE(SpecCfg4) SUSNET_DECLARE(SpecTag5)
@@ -456,48 +457,7 @@ __global__ __launch_bounds__(256) void k_reduce_lifetime(Consts c, State s, int6
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-struct susnet_env {
-    susnet_config cfg;
-    Consts c;
-    State s;
-    bool bound = false;
-    bool float_exact = false;
-    uint64_t ticks = 0; // steps taken (index of the production action stream)
-    // test hooks, read ONCE at susnet_create (include/susnet.h SUSNET_OVERRIDE_*)
-    bool force_generic = false;
-    int ring_tile = 0;   // susnet_ring_append: environments of a wave's (ticks x envs) tile (8 / 16 / 32; 0: consecutive rows per wave)
-    uint64_t launch_limit = (1ull << 31) - 1u, launch_limit_default = (1ull << 31) - 1u;
-    int spec = 0; // pick_spec(): which compiled-in kernel family serves the handle (0 = generic)
-    susnet_layout layout;
-    uint64_t off_err, off_agent, off_job, off_jobdone, off_t, off_timer, off_flags, off_rng, off_msteps, off_mfix, off_msab,
-        off_mkv, off_life, off_tickw, off_ep;
-};
-
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-// (messages about a handle created under test hooks say so: a stray environment variable is then visible where it bites)
-static int fail(const susnet_env *env, int code, const std::string &msg) {
-    std::string m = msg;
-    if (env && env->layout.test_overrides) {
-        m += " [handle created with";
-        if (env->layout.test_overrides & SUSNET_OVERRIDE_FORCE_GENERIC) m += " SUSNET_FORCE_GENERIC";
-        if (env->layout.test_overrides & SUSNET_OVERRIDE_EPW) m += " SUSNET_EPW";
-        if (env->layout.test_overrides & SUSNET_OVERRIDE_TRAJ_MAX_BYTES) m += " SUSNET_TRAJ_MAX_BYTES";
-        if (env->layout.test_overrides & SUSNET_OVERRIDE_RING_TILE) m += " SUSNET_RING_TILE";
-        m += "]";
-    }
-    return fail(code, m);
-}
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(SUSNET_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-static inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+thread_local std::string g_err;
 
 extern "C" int susnet_abi_version(void) { return SUSNET_ABI_VERSION; }
 extern "C" const char *susnet_last_error(void) { return g_err.c_str(); }
@@ -721,13 +681,6 @@ extern "C" int susnet_bind_tape(susnet_env *env, const uint32_t *tape, int64_t w
     return SUSNET_OK;
 }
 
-static int check_bound(const susnet_env *env) {
-    if (!env) return fail(SUSNET_E_INVALID, "null handle");
-    if (!env->bound) return fail(SUSNET_E_STATE, "state blob not bound (susnet_bind_state)");
-    return SUSNET_OK;
-}
-static inline dim3 grid_for(const susnet_env *env) { return dim3((unsigned)((env->c.B + kBlock - 1) / kBlock)); }
-
 extern "C" int susnet_seed(susnet_env *env, uint64_t seed, uint64_t cursor, void *stream) {
     if (int rc = check_bound(env)) return rc;
     env->c.seed = seed;
@@ -908,8 +861,8 @@ extern "C" int susnet_policy_actions(susnet_env *env, const float *q_imposter, c
 }
 
 // ---- the policy loop's Q-network (susnet_qnet.h) ----
-// which compiled-in feature layout (susnet_flat.h) a component list on this handle is: 0 = none
-static int qnet_feat(const susnet_env *env, const int32_t *comp, int32_t ncomp) {
+// which compiled-in feature layout (susnet_flat.h) a component list on this handle is: 0 = none (susnet_capi_train.hip asks too)
+int qnet_feat(const susnet_env *env, const int32_t *comp, int32_t ncomp) {
     if (!env || !comp) return 0;
     const Consts &c = env->c;
     if (c.A == 2 && c.N == 9 && ncomp == 1 && comp[0] == SUSNET_F_ONEHOT_POS) return FEAT_ONEHOT;
@@ -920,7 +873,7 @@ static int qnet_feat(const susnet_env *env, const int32_t *comp, int32_t ncomp) 
     return 0;
 }
 template <class ROW>
-static bool qnet_dims_ok(const int32_t *dims, int32_t n_dims) {
+bool qnet_dims_ok(const int32_t *dims, int32_t n_dims) {
     using Q = QNet<ROW>;
     const int cap[6] = {Q::F, Q::H1, Q::H2, Q::H3, Q::H4, Q::NO};
     if (!dims || n_dims != 6 || dims[0] != Q::F) return false;
@@ -928,6 +881,9 @@ static bool qnet_dims_ok(const int32_t *dims, int32_t n_dims) {
         if (dims[l] < 1 || dims[l] > cap[l]) return false;
     return true;
 }
+template bool qnet_dims_ok<QRow1>(const int32_t *, int32_t);
+template bool qnet_dims_ok<QRow3>(const int32_t *, int32_t);
+template bool qnet_dims_ok<QRowC>(const int32_t *, int32_t);
 // torch Linear weight [dn][dk] -> 32 x 32 blocks in [kb][nb] order; inside a block lane l holds, as four float4, the 16 k values of row
 // n = 32 nb + l % 32 in MFMA-step order: float4 q = columns 32 kb + 8 q + 4 (l / 32) + {0, 1, 2, 3}
 static void qnet_pack_dense(const float *W, int dk, int dn, int KP, int NP, float *dst) {
@@ -1513,599 +1469,6 @@ extern "C" int susnet_scent(susnet_env *env, const void *rows, int32_t rows_dtyp
     return SUSNET_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// replay ring (susnet_ring_append)
-// ---------------------------------------------------------------------------------------------------
-struct RingArgs {
-    susnet_ring_io io;
-    int64_t B, n0, n1; // envs; first / one-past-last transition (n = tick * B + env) this launch writes
-    int32_t A, S, n_imp;
-    int32_t rows_per_wave; // 64, or fewer when 64 rows of 2 x trajectory_size x S bytes would not fit the LDS images
-    int32_t tile_log2e;    // k_ring_append_tile: log2 of the tile's environments (3: 8 ticks x 8 envs)
-    int32_t n0_b;            // n0 = n0_t * B + n0_b; pos_n0 = ring position of transition n0
-    int64_t n0_t, pos_n0;
-    // the trajectory as PACKED RECORDS (io.record; whole records only: the 1v1 kernels), wave-uniform: record size (0 = separate
-    // tensors) and field offsets; rec_packed: actions and flags share one byte (SUSNET_RECORD_COMPACT)
-    int32_t rec_bytes, rec_obs, rec_act, rec_rew, rec_done, rec_trunc, rec_packed;
-};
-// the trajectory's fields at (tick u, env b), from the separate tensors or from the records -- a compile-time choice (REC): as a run-time
-// one every access carried a uniform branch and both address forms, and the append of the small 1v1 rows ran at 81 us instead of 56
-__device__ __forceinline__ const uint8_t *ring_rec(const RingArgs &r, int64_t u, int64_t b) { return r.io.record + ((size_t)u * r.B + b) * (size_t)r.rec_bytes; }
-template <bool REC>
-__device__ __forceinline__ uint32_t ring_done(const RingArgs &r, int64_t u, int64_t b) {
-    if constexpr (REC) return r.rec_packed ? (ring_rec(r, u, b)[r.rec_done] >> 6) & 1u : (uint32_t)ring_rec(r, u, b)[r.rec_done];
-    else return r.io.done[u * r.B + b];
-}
-template <bool REC>
-__device__ __forceinline__ uint32_t ring_trunc(const RingArgs &r, int64_t u, int64_t b) {
-    if constexpr (REC) return r.rec_packed ? (uint32_t)(ring_rec(r, u, b)[r.rec_trunc] >> 7) : (uint32_t)ring_rec(r, u, b)[r.rec_trunc];
-    else return r.io.truncated[u * r.B + b];
-}
-template <bool REC>
-__device__ __forceinline__ uint32_t ring_action(const RingArgs &r, int64_t t, int64_t b, int i) {
-    if constexpr (REC) return r.rec_packed ? (ring_rec(r, t, b)[r.rec_act] >> (3 * i)) & 7u : (uint32_t)ring_rec(r, t, b)[r.rec_act + i];
-    else return r.io.actions[((size_t)t * r.B + b) * r.A + i];
-}
-template <bool REC>
-__device__ __forceinline__ float ring_reward(const RingArgs &r, int64_t t, int64_t b, int i) {
-    if constexpr (REC) return reinterpret_cast<const float *>(ring_rec(r, t, b) + r.rec_rew)[i];
-    else return r.io.rewards[((size_t)t * r.B + b) * r.A + i];
-}
-// the flattened state an env's window holds at virtual tick u (= the state after tick u; u < 0: the carried-in window)
-template <bool REC>
-__device__ __forceinline__ const uint8_t *ring_state(const RingArgs &r, int64_t u, int64_t b) {
-    const int Tw = r.io.trajectory_size;
-    if (u < 0) return r.io.window + ((size_t)b * Tw + (size_t)(Tw + u < 0 ? 0 : Tw + u)) * r.S; // window[Tw - 1] = state before tick 0
-    if constexpr (REC) return ring_rec(r, u, b) + r.rec_obs;
-    else return r.io.obs + ((size_t)u * r.B + b) * r.S;
-}
-// One wave per 64 consecutive transitions (32 / 16 / 8 for long windows: RingArgs::rows_per_wave).
-// Lane r gathers what its row needs into flat images in LDS, laid out exactly as the wave's 64 rows lie in each ring tensor (row-major;
-// `states` and `next_states`: Tw * S bytes per row, the Tw - 1 shared states written to both; actions, rewards, done, imposters
-// likewise), and the wave then writes every tensor as ONE linear range: 16 bytes per lane and step, no index arithmetic.  (One image of
-// Tw + 1 states per row, read at offsets 0 and S, needs a quarter less LDS but its reads are unaligned dwords: measured 2.1 / 3.4 TB/s
-// against 3.0 / 4.2 on the 1v1 and 1v2 shapes.)
-// Two things made the first version slow (3.1-3.5 TB/s, 82 % of the wave cycles waiting): every element index was divided by Tw * S to
-// find its row, and each lane stored its row's small tensors between its loads -- stores the loads behind them had to wait for
-// (may-alias), one memory round trip per element.  Now a lane only LOADS in the gather phase (flags first, unrolled without an early
-// exit; then rows, actions, rewards, roles) and all global stores happen after it.
-constexpr int kRingFlagsUnroll = 8;
-constexpr int kRingGroup = 3, kRingChunk = 8; // source states per load group; dwords of a state per load group
-template <bool REC>
-__global__ __launch_bounds__(64) void k_ring_append(RingArgs r) {
-    extern __shared__ uint32_t smem[];
-    const int lane = threadIdx.x, Tw = r.io.trajectory_size, S = r.S, A = r.A, NI = r.n_imp;
-    const int R = r.rows_per_wave;
-    const int TS = Tw * S;
-    const int img = (R * TS + 15) & ~15; // bytes of one state image (padded: the vector loops read up to 3 bytes past the last row)
-    uint8_t *st_img = reinterpret_cast<uint8_t *>(smem), *nx_img = st_img + img;
-    float *rew_img = reinterpret_cast<float *>(nx_img + img);        // [R][A]
-    uint8_t *act_img = reinterpret_cast<uint8_t *>(rew_img + R * A); // [R][A] (+ pad)
-    uint8_t *done_img = act_img + ((R * A + 15) & ~15);              // [R]
-    int16_t *imp_img = reinterpret_cast<int16_t *>(done_img + 64);   // [R][NI]
-    // (tick, env) of the lane's transition n = n0 + rel + lane without a 64-bit division per lane: the host supplies n0's, the rest is
-    // 32-bit (rel + B < 2^32: checked there)
-    const uint32_t rel = (uint32_t)blockIdx.x * (uint32_t)R;
-    const int64_t n_first = r.n0 + (int64_t)rel;
-    const int rows = (int)((r.n1 - n_first) < R ? (r.n1 - n_first) : R);
-    if (lane < rows) {
-        const uint32_t x = rel + (uint32_t)r.n0_b + (uint32_t)lane, tq = x / (uint32_t)r.B;
-        const int64_t t = r.n0_t + (int64_t)tq, b = (int64_t)(x - tq * (uint32_t)r.B);
-        // most recent episode boundary before tick t within the window's reach (the episode's first state is obs[e]); all flag
-        // loads are independent of each other
-        int64_t e = -(1ll << 62);
-        if (Tw <= kRingFlagsUnroll) {
-            uint32_t fd[kRingFlagsUnroll], ft[kRingFlagsUnroll];
-#pragma unroll
-            for (int k = 1; k <= kRingFlagsUnroll; k++) { // every lane loads (tick clamped): no per-lane branch, no wait between the loads
-                const int64_t u = t - k < 0 ? 0 : t - k;
-                const bool want = k <= Tw; // (wave-uniform)
-                fd[k - 1] = want ? ring_done<REC>(r, u, b) : 0u;
-                ft[k - 1] = want ? ring_trunc<REC>(r, u, b) : 0u;
-            }
-#pragma unroll
-            for (int k = kRingFlagsUnroll; k >= 1; k--)
-                if ((fd[k - 1] | ft[k - 1]) != 0u && t - k >= 0) e = t - k; // (descending k: the most recent boundary wins)
-        } else {
-            for (int64_t u = t - 1; u >= 0 && u > t - 1 - Tw; u--)
-                if (ring_done<REC>(r, u, b) | ring_trunc<REC>(r, u, b)) { e = u; break; }
-        }
-        const uint32_t dn = ring_done<REC>(r, t, b), tr = ring_trunc<REC>(r, t, b);
-        const uint32_t role_bits = r.io.roles ? (uint32_t)r.io.roles[t * r.B + b] : ((1u << NI) - 1u);
-        uint8_t *my_st = st_img + (size_t)lane * TS, *my_nx = nx_img + (size_t)lane * TS;
-        // The row needs Tw + 1 source states (replay_memory.py:108-113, 122-127): the window's Tw states -> states[k], and shifted by one
-        // -> next_states[k - 1]; the state after the tick (the terminal observation where the episode ended) -> next_states[Tw - 1].  A
-        // state = S consecutive bytes at an arbitrary address, fetched as UNALIGNED dwords (gfx950 serves them, global and LDS alike) + a
-        // byte tail.  All loads of a group of kRingGroup states are issued before the first LDS store: one memory round trip per group,
-        // not one per dword (the rolled load -> store loop this replaces made 18 dependent round trips per row and left the kernel
-        // latency-bound at 3.7 TB/s).
-        const uint8_t *nxt = (dn | tr) ? r.io.term_obs + ((size_t)t * r.B + b) * S : ring_state<REC>(r, t, b);
-        auto source = [&](int k) -> const uint8_t * {
-            if (k >= Tw) return nxt;
-            int64_t u = t - Tw + k;
-            if (u < e) u = e;
-            return ring_state<REC>(r, u, b);
-        };
-        for (int k0 = 0; k0 <= Tw; k0 += kRingGroup) {
-            for (int c0 = 0; c0 < S; c0 += 4 * kRingChunk) {
-                uint32_t v[kRingGroup][kRingChunk];
-                uint8_t tail[kRingGroup][3];
-#pragma unroll
-                for (int g = 0; g < kRingGroup; g++) {
-                    if (k0 + g > Tw) break; // (wave-uniform)
-                    const uint8_t *src = source(k0 + g) + c0;
-#pragma unroll
-                    for (int q = 0; q < kRingChunk; q++)
-                        if (c0 + 4 * q + 4 <= S) __builtin_memcpy(&v[g][q], src + 4 * q, 4);
-                    if (S - c0 < 4 * kRingChunk) { // the row ends in this chunk: its last S % 4 bytes
-                        const int f0 = (S - c0) & ~3;
-#pragma unroll
-                        for (int q = 0; q < 3; q++)
-                            if (f0 + q < S - c0) tail[g][q] = src[f0 + q];
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < kRingGroup; g++) {
-                    const int k = k0 + g;
-                    if (k > Tw) break;
-                    uint8_t *d0 = k < Tw ? my_st + k * S + c0 : nullptr, *d1 = k > 0 ? my_nx + (k - 1) * S + c0 : nullptr;
-#pragma unroll
-                    for (int q = 0; q < kRingChunk; q++)
-                        if (c0 + 4 * q + 4 <= S) {
-                            if (d0) __builtin_memcpy(d0 + 4 * q, &v[g][q], 4);
-                            if (d1) __builtin_memcpy(d1 + 4 * q, &v[g][q], 4);
-                        }
-                    if (S - c0 < 4 * kRingChunk) {
-                        const int f0 = (S - c0) & ~3;
-#pragma unroll
-                        for (int q = 0; q < 3; q++)
-                            if (f0 + q < S - c0) {
-                                if (d0) d0[f0 + q] = tail[g][q];
-                                if (d1) d1[f0 + q] = tail[g][q];
-                            }
-                    }
-                }
-            }
-        }
-        for (int i0 = 0; i0 < A; i0 += 8) { // (loads of eight agents in flight, then their LDS stores)
-            uint8_t av[8];
-            float rv[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                if (i0 + q < A) {
-                    av[q] = (uint8_t)ring_action<REC>(r, t, b, i0 + q);
-                    rv[q] = ring_reward<REC>(r, t, b, i0 + q);
-                }
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                if (i0 + q < A) {
-                    act_img[lane * A + i0 + q] = av[q];
-                    rew_img[lane * A + i0 + q] = rv[q];
-                }
-        }
-        done_img[lane] = dn ? 1 : 0; // replay_memory.py:131: done, not truncation
-        uint32_t m = role_bits;
-        for (int k = 0; k < NI; k++) { // ascending agent indices
-            const int i = __ffs((int)m) - 1;
-            imp_img[lane * NI + k] = (int16_t)(i < 0 ? 0 : i);
-            m &= m - 1u;
-        }
-    }
-    wave_lds_fence();
-    // ring position of row 0 of this wave; rows are consecutive positions modulo max_size
-    int64_t pos0 = r.pos_n0 + (int64_t)rel; // (pos_n0 = (idx + n0) % max_size from the host; rel < max_size)
-    if (pos0 >= r.io.max_size) pos0 -= r.io.max_size;
-    const int total = rows * TS;
-    if (__builtin_expect(pos0 + rows <= r.io.max_size, 1)) { // no wrap inside the wave: every output is ONE contiguous range
-        float *out_s = r.io.states + (size_t)pos0 * TS, *out_n = r.io.next_states + (size_t)pos0 * TS;
-        if ((((size_t)pos0 * TS) & 3u) == 0) { // 16-byte aligned ranges: four elements per lane and step
-            const uint32_t *s4 = reinterpret_cast<const uint32_t *>(st_img), *n4 = reinterpret_cast<const uint32_t *>(nx_img);
-            for (int g = 4 * lane; g < total; g += 256) {
-                const uint32_t a = s4[g >> 2], c = n4[g >> 2];
-                const float4 fa = make_float4((float)(a & 0xffu), (float)((a >> 8) & 0xffu), (float)((a >> 16) & 0xffu), (float)(a >> 24));
-                const float4 fc = make_float4((float)(c & 0xffu), (float)((c >> 8) & 0xffu), (float)((c >> 16) & 0xffu), (float)(c >> 24));
-                if (g + 4 <= total) {
-                    *reinterpret_cast<float4 *>(out_s + g) = fa;
-                    *reinterpret_cast<float4 *>(out_n + g) = fc;
-                } else { // the range's last, partial group
-                    const float va[4] = {fa.x, fa.y, fa.z, fa.w}, vc[4] = {fc.x, fc.y, fc.z, fc.w};
-                    for (int q = 0; q < total - g; q++) { out_s[g + q] = va[q]; out_n[g + q] = vc[q]; }
-                }
-            }
-        } else {
-            for (int g = lane; g < total; g += 64) {
-                out_s[g] = (float)st_img[g];
-                out_n[g] = (float)nx_img[g];
-            }
-        }
-        int64_t *out_a = r.io.ring_actions + (size_t)pos0 * A;
-        float *out_r = r.io.ring_rewards + (size_t)pos0 * A;
-        for (int g = lane; g < rows * A; g += 64) {
-            out_a[g] = (int64_t)act_img[g];
-            out_r[g] = rew_img[g];
-        }
-        if (lane < rows) r.io.ring_dones[pos0 + lane] = done_img[lane];
-        for (int g = lane; g < rows * NI; g += 64) r.io.ring_imposters[(size_t)pos0 * NI + g] = imp_img[g];
-    } else { // the ring wraps inside this wave's rows (once per trip round the ring): element by element
-        for (int g = lane; g < total; g += 64) {
-            const int row = g / TS, k = g - row * TS;
-            int64_t p = pos0 + row;
-            if (p >= r.io.max_size) p -= r.io.max_size;
-            r.io.states[(size_t)p * TS + k] = (float)st_img[g];
-            r.io.next_states[(size_t)p * TS + k] = (float)nx_img[g];
-        }
-        if (lane < rows) {
-            int64_t p = pos0 + lane;
-            if (p >= r.io.max_size) p -= r.io.max_size;
-            for (int i = 0; i < A; i++) {
-                r.io.ring_actions[p * A + i] = (int64_t)act_img[lane * A + i];
-                r.io.ring_rewards[p * A + i] = rew_img[lane * A + i];
-            }
-            r.io.ring_dones[p] = done_img[lane];
-            for (int k = 0; k < NI; k++) r.io.ring_imposters[p * NI + k] = imp_img[lane * NI + k];
-        }
-    }
-}
-// The same rows from a TILE per wave: TT consecutive ticks x TE consecutive environments (TT * TE = 64; lane = dt * TE + db).  A row needs
-// the Tw + 1 states around its tick (replay_memory.py:108-113, 122-127) and in the kernel above every lane fetches all of them itself:
-// each state of the trajectory is read by Tw + 1 waves.  Here the wave fetches the (TT + Tw) x TE states its tile touches ONCE into an
-// LDS image (one state per lane + Tw * TE states ahead of the tile + the terminal states where an episode ended) and every lane then
-// assembles its row from that image: (TT + Tw) / TT reads per state instead of Tw + 1.  The rows of one tick are TE consecutive ring
-// positions, so the wave writes TT contiguous runs per tensor; run bases live in a small LDS table and the store loop walks all runs as
-// one flattened index space (run = index / groups-per-run by a multiply), 16 bytes per lane and step as above.
-struct RingRun {
-    int64_t pos;      // ring position of the run's first row
-    int32_t first, n; // first lane-row of the run in the images (dt * TE + lo); rows (0: nothing to write; < 0: -n rows, the ring wraps inside)
-};
-__device__ __forceinline__ void ring_copy_state(uint8_t *d0, uint8_t *d1, const uint8_t *src, int S) {
-    int c = 0;
-    for (; c + 16 <= S; c += 16) {
-        uint32_t v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) __builtin_memcpy(&v[q], src + c + 4 * q, 4);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (d0) __builtin_memcpy(d0 + c + 4 * q, &v[q], 4);
-            if (d1) __builtin_memcpy(d1 + c + 4 * q, &v[q], 4);
-        }
-    }
-    for (; c + 4 <= S; c += 4) {
-        uint32_t v;
-        __builtin_memcpy(&v, src + c, 4);
-        if (d0) __builtin_memcpy(d0 + c, &v, 4);
-        if (d1) __builtin_memcpy(d1 + c, &v, 4);
-    }
-    for (; c < S; c++) {
-        const uint8_t v = src[c];
-        if (d0) d0[c] = v;
-        if (d1) d1[c] = v;
-    }
-}
-template <bool REC>
-__global__ __launch_bounds__(64) void k_ring_append_tile(RingArgs r) {
-    extern __shared__ uint32_t smem[];
-    const int lane = threadIdx.x, Tw = r.io.trajectory_size, S = r.S, A = r.A, NI = r.n_imp;
-    const int le = r.tile_log2e, TE = 1 << le, TT = 64 >> le;
-    const int64_t tiles_b = (r.B + TE - 1) >> le;
-    const int64_t tile_t = (int64_t)blockIdx.x / tiles_b, tile_b = (int64_t)blockIdx.x - tile_t * tiles_b;
-    const int64_t t_first = r.n0 / r.B; // first tick with a row to write
-    const int64_t t0 = t_first + tile_t * TT, b0 = tile_b << le;
-    const int dt = lane >> le, db = lane & (TE - 1);
-    const int64_t t = t0 + dt, b = b0 + db;
-    const bool live = t < r.io.n_ticks && b < r.B; // the lane's (tick, env) exists (its row is written only if t * B + b >= n0)
-    const int TS = Tw * S;
-    // LDS: [source states (TT + Tw) x TE][their episode-end flags][states image 64 x TS][next_states image][rewards][actions][done][imposters][runs]
-    const int n_src = (TT + Tw) * TE;
-    uint8_t *src_img = reinterpret_cast<uint8_t *>(smem);
-    uint8_t *flg_img = src_img + ((n_src * S + 15) & ~15);
-    uint8_t *st_img = flg_img + ((n_src + 15) & ~15);
-    const int img = (64 * TS + 15) & ~15;
-    uint8_t *nx_img = st_img + img;
-    float *rew_img = reinterpret_cast<float *>(nx_img + img);
-    uint8_t *act_img = reinterpret_cast<uint8_t *>(rew_img + 64 * A);
-    uint8_t *done_img = act_img + ((64 * A + 15) & ~15);
-    int16_t *imp_img = reinterpret_cast<int16_t *>(done_img + 64);
-    RingRun *runs = reinterpret_cast<RingRun *>(reinterpret_cast<uint8_t *>(imp_img) + ((64 * NI * 2 + 15) & ~15));
-    uint8_t *my_st = st_img + (size_t)lane * TS, *my_nx = nx_img + (size_t)lane * TS;
-
-    // ---- phase A: every global load of the tile, then the LDS stores
-    uint32_t dn = 0, tr = 0;
-    if (live) { dn = ring_done<REC>(r, t, b); tr = ring_trunc<REC>(r, t, b); }
-    const bool ended = (dn | tr) != 0u;
-    // the Tw ticks ahead of the tile: lane = du * TE + db' for du < Tw (Tw * TE <= 64: checked on the host)
-    const int du = lane >> le;
-    const int64_t u_pre = t0 - Tw + du;
-    const bool pre = du < Tw && b < r.B;
-    uint32_t pre_flag = 0;
-    if (pre && u_pre >= 0) pre_flag = ring_done<REC>(r, u_pre, b) | ring_trunc<REC>(r, u_pre, b);
-    const uint8_t *sp[3] = {live ? ring_state<REC>(r, t, b) : nullptr, pre ? ring_state<REC>(r, u_pre, b) : nullptr,
-                            live && ended ? r.io.term_obs + ((size_t)t * r.B + b) * S : nullptr};
-    uint8_t *own_slot = src_img + (size_t)((dt + Tw) * TE + db) * S, *pre_slot = src_img + (size_t)(du * TE + db) * S, *last = my_nx + (size_t)(Tw - 1) * S;
-    for (int c0 = 0; c0 < S; c0 += 4 * kRingChunk) {
-        uint32_t v[3][kRingChunk];
-        uint8_t tail[3][3];
-#pragma unroll
-        for (int g = 0; g < 3; g++) {
-            if (sp[g] == nullptr) continue;
-            const uint8_t *src = sp[g] + c0;
-#pragma unroll
-            for (int q = 0; q < kRingChunk; q++)
-                if (c0 + 4 * q + 4 <= S) __builtin_memcpy(&v[g][q], src + 4 * q, 4);
-            if (S - c0 < 4 * kRingChunk) {
-                const int f0 = (S - c0) & ~3;
-#pragma unroll
-                for (int q = 0; q < 3; q++)
-                    if (f0 + q < S - c0) tail[g][q] = src[f0 + q];
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < 3; g++) {
-            if (sp[g] == nullptr) continue;
-            // own state -> its source slot, and the row's last next-state unless the episode ended (then the terminal state is)
-            uint8_t *d0 = g == 0 ? own_slot + c0 : g == 1 ? pre_slot + c0 : last + c0;
-            uint8_t *d1 = g == 0 && !ended ? last + c0 : nullptr;
-#pragma unroll
-            for (int q = 0; q < kRingChunk; q++)
-                if (c0 + 4 * q + 4 <= S) {
-                    __builtin_memcpy(d0 + 4 * q, &v[g][q], 4);
-                    if (d1) __builtin_memcpy(d1 + 4 * q, &v[g][q], 4);
-                }
-            if (S - c0 < 4 * kRingChunk) {
-                const int f0 = (S - c0) & ~3;
-#pragma unroll
-                for (int q = 0; q < 3; q++)
-                    if (f0 + q < S - c0) {
-                        d0[f0 + q] = tail[g][q];
-                        if (d1) d1[f0 + q] = tail[g][q];
-                    }
-            }
-        }
-    }
-    if (live) {
-        const uint32_t role_bits = r.io.roles ? (uint32_t)r.io.roles[t * r.B + b] : ((1u << NI) - 1u);
-        for (int i0 = 0; i0 < A; i0 += 8) {
-            uint8_t av[8];
-            float rv[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                if (i0 + q < A) {
-                    av[q] = (uint8_t)ring_action<REC>(r, t, b, i0 + q);
-                    rv[q] = ring_reward<REC>(r, t, b, i0 + q);
-                }
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                if (i0 + q < A) {
-                    act_img[lane * A + i0 + q] = av[q];
-                    rew_img[lane * A + i0 + q] = rv[q];
-                }
-        }
-        done_img[lane] = dn ? 1 : 0; // replay_memory.py:131: done, not truncation
-        uint32_t m = role_bits;
-        for (int k = 0; k < NI; k++) { // ascending agent indices
-            const int i = __ffs((int)m) - 1;
-            imp_img[lane * NI + k] = (int16_t)(i < 0 ? 0 : i);
-            m &= m - 1u;
-        }
-    }
-    flg_img[(dt + Tw) * TE + db] = ended ? 1 : 0;
-    if (du < Tw) flg_img[du * TE + db] = pre_flag ? 1 : 0;
-    if (lane < TT) { // the runs: tick t0 + lane, rows [lo, hi) of the tile's TE environments
-        const int64_t tt = t0 + lane;
-        RingRun run = {0, 0, 0};
-        if (tt < r.io.n_ticks) {
-            const int64_t nb = tt * r.B + b0; // transition index of the run's first environment
-            const int lo = nb >= r.n0 ? 0 : (r.n0 - nb >= TE ? TE : (int)(r.n0 - nb));
-            const int hi = r.B - b0 >= TE ? TE : (int)(r.B - b0);
-            if (hi > lo) {
-                run.pos = (r.io.idx + nb + lo) % r.io.max_size;
-                run.first = lane * TE + lo;
-                run.n = run.pos + (hi - lo) <= r.io.max_size ? hi - lo : -(hi - lo);
-            }
-        }
-        runs[lane] = run;
-    }
-    wave_lds_fence();
-
-    // ---- phase B: the row's window from the source image (states[k] and, shifted by one, next_states[k - 1])
-    if (live) {
-        int64_t e = -(1ll << 62); // most recent episode boundary before tick t within the window's reach
-        for (int k = Tw; k >= 1; k--)
-            if (flg_img[(dt + Tw - k) * TE + db] != 0 && t - k >= 0) e = t - k;
-        for (int k = 0; k < Tw; k++) {
-            int64_t u = t - Tw + k;
-            if (u < e) u = e;
-            const uint8_t *src = src_img + (size_t)((int)(u - t0 + Tw) * TE + db) * S;
-            ring_copy_state(my_st + (size_t)k * S, k > 0 ? my_nx + (size_t)(k - 1) * S : nullptr, src, S);
-        }
-    }
-    wave_lds_fence();
-
-    // ---- phase C: TT contiguous runs per tensor
-    const uint32_t run_elems = (uint32_t)(TE * TS); // floats of a full run
-    bool fast = true;                              // every run: no wrap inside, 16-byte aligned start, whole groups of four floats
-#pragma unroll 1
-    for (int q = 0; q < TT; q++) {
-        const RingRun run = runs[q];
-        if (run.n < 0 || ((((size_t)run.pos * TS) | (size_t)((run.first & (TE - 1)) * TS) | (size_t)(run.n > 0 ? run.n * TS : 0)) & 3u) != 0) fast = false;
-    }
-    if (__builtin_expect(fast, 1)) {
-        const uint32_t gpr = run_elems >> 2; // float4 groups of a full run (a shorter run: the groups past its end are skipped)
-        const uint32_t magic = 0xffffffffu / gpr + 1u;
-        const uint32_t total = gpr * (uint32_t)TT;
-        const uint32_t *s4 = reinterpret_cast<const uint32_t *>(st_img), *n4 = reinterpret_cast<const uint32_t *>(nx_img);
-        for (uint32_t g = lane; g < total; g += 64) {
-            const uint32_t q = __umulhi(g, magic), w = g - q * gpr;
-            const RingRun run = runs[q];
-            if ((int)(4 * w) >= run.n * TS) continue;
-            const uint32_t at = (uint32_t)run.first * (uint32_t)TS + 4 * w; // byte offset into the images (a multiple of 4: checked above)
-            const uint32_t a = s4[at >> 2], c = n4[at >> 2];
-            const float4 fa = make_float4((float)(a & 0xffu), (float)((a >> 8) & 0xffu), (float)((a >> 16) & 0xffu), (float)(a >> 24));
-            const float4 fc = make_float4((float)(c & 0xffu), (float)((c >> 8) & 0xffu), (float)((c >> 16) & 0xffu), (float)(c >> 24));
-            const size_t o = (size_t)run.pos * TS + 4 * w;
-            *reinterpret_cast<float4 *>(r.io.states + o) = fa;
-            *reinterpret_cast<float4 *>(r.io.next_states + o) = fc;
-        }
-    } else { // a run that wraps round the ring's end or starts off a 16-byte boundary: element by element
-        for (int q = 0; q < TT; q++) {
-            const RingRun run = runs[q];
-            const int n = run.n < 0 ? -run.n : run.n;
-            for (int g = lane; g < n * TS; g += 64) {
-                const int row = g / TS, k = g - row * TS;
-                int64_t p = run.pos + row;
-                if (p >= r.io.max_size) p -= r.io.max_size;
-                r.io.states[(size_t)p * TS + k] = (float)st_img[(size_t)run.first * TS + g];
-                r.io.next_states[(size_t)p * TS + k] = (float)nx_img[(size_t)run.first * TS + g];
-            }
-        }
-    }
-    // the small tensors: lane-row l of the images is row l - run.first of run l / TE
-    {
-        const RingRun run = runs[dt];
-        const int n = run.n < 0 ? -run.n : run.n;
-        const int row = lane - run.first;
-        if (row >= 0 && row < n) {
-            int64_t p = run.pos + row;
-            if (p >= r.io.max_size) p -= r.io.max_size;
-            r.io.ring_dones[p] = done_img[lane];
-            for (int k = 0; k < NI; k++) r.io.ring_imposters[p * NI + k] = imp_img[lane * NI + k];
-        }
-        const uint32_t magic_a = 0xffffffffu / (uint32_t)A + 1u;
-        for (uint32_t g = lane; g < 64u * (uint32_t)A; g += 64) { // consecutive lanes: consecutive elements of a run
-            const uint32_t l = __umulhi(g, magic_a), i = g - l * (uint32_t)A;
-            const RingRun rl = runs[l >> le];
-            const int nl = rl.n < 0 ? -rl.n : rl.n, rw = (int)l - rl.first;
-            if (rw < 0 || rw >= nl) continue;
-            int64_t p = rl.pos + rw;
-            if (p >= r.io.max_size) p -= r.io.max_size;
-            r.io.ring_actions[p * A + i] = (int64_t)act_img[g];
-            r.io.ring_rewards[p * A + i] = rew_img[g];
-        }
-    }
-}
-// the carried window of every env after the launch: the window before the tick that follows the last one
-template <bool REC>
-__global__ __launch_bounds__(64) void k_ring_window(RingArgs r) {
-    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (b >= r.B) return;
-    const int Tw = r.io.trajectory_size, S = r.S;
-    const int64_t t = r.io.n_ticks;
-    int64_t e = -(1ll << 62);
-    for (int64_t u = t - 1; u >= 0 && u > t - 1 - Tw; u--)
-        if (ring_done<REC>(r, u, b) | ring_trunc<REC>(r, u, b)) { e = u; break; }
-    // in place, slots ascending: slot k of the new window comes from obs, or (launches shorter than the window) from slot
-    // k + t > k of the old one, which has not been overwritten yet
-    // (a group's loads are all issued before its first store, as in k_ring_append: a slot read from the old window lies above every slot
-    // written so far)
-    uint8_t *dst = r.io.window + (size_t)b * Tw * S;
-    for (int k0 = 0; k0 < Tw; k0 += kRingGroup) {
-        for (int c0 = 0; c0 < S; c0 += 4 * kRingChunk) {
-            uint32_t v[kRingGroup][kRingChunk];
-            uint8_t tail[kRingGroup][3];
-#pragma unroll
-            for (int g = 0; g < kRingGroup; g++) {
-                if (k0 + g >= Tw) break;
-                int64_t u = t - Tw + k0 + g;
-                if (u < e) u = e;
-                const uint8_t *src = ring_state<REC>(r, u, b) + c0;
-#pragma unroll
-                for (int q = 0; q < kRingChunk; q++)
-                    if (c0 + 4 * q + 4 <= S) __builtin_memcpy(&v[g][q], src + 4 * q, 4);
-                if (S - c0 < 4 * kRingChunk) {
-                    const int f0 = (S - c0) & ~3;
-#pragma unroll
-                    for (int q = 0; q < 3; q++)
-                        if (f0 + q < S - c0) tail[g][q] = src[f0 + q];
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < kRingGroup; g++) {
-                if (k0 + g >= Tw) break;
-                uint8_t *d = dst + (k0 + g) * S + c0;
-#pragma unroll
-                for (int q = 0; q < kRingChunk; q++)
-                    if (c0 + 4 * q + 4 <= S) __builtin_memcpy(d + 4 * q, &v[g][q], 4);
-                if (S - c0 < 4 * kRingChunk) {
-                    const int f0 = (S - c0) & ~3;
-#pragma unroll
-                    for (int q = 0; q < 3; q++)
-                        if (f0 + q < S - c0) d[f0 + q] = tail[g][q];
-                }
-            }
-        }
-    }
-}
-
-extern "C" int susnet_ring_append(susnet_env *env, const susnet_ring_io *io, void *stream) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "null argument");
-    if (io->n_ticks < 1 || io->trajectory_size < 1 || io->max_size < 1 || io->idx < 0 || io->idx >= io->max_size)
-        return fail(SUSNET_E_INVALID, "susnet_ring_append: n_ticks, trajectory_size, max_size must be positive and 0 <= idx < max_size");
-    const bool from_records = io->record != nullptr;
-    if (from_records && (io->actions || io->rewards || io->done || io->truncated || io->obs))
-        return fail(SUSNET_E_INVALID, "susnet_ring_append: record is an alternative to the separate trajectory tensors, not an addition");
-    if ((!from_records && (!io->actions || !io->rewards || !io->done || !io->truncated || !io->obs)) || !io->term_obs || !io->window || !io->states ||
-        !io->next_states || !io->ring_actions || !io->ring_rewards || !io->ring_dones || !io->ring_imposters)
-        return fail(SUSNET_E_INVALID, "susnet_ring_append: null buffer");
-    if (!io->roles && env->c.shuffle_imp) return fail(SUSNET_E_INVALID, "susnet_ring_append: roles are drawn per episode here (shuffle_imposter_index): pass roles");
-    RingArgs r;
-    r.io = *io;
-    r.B = env->c.B;
-    r.A = env->c.A;
-    r.S = env->layout.obs_raw_size;
-    r.n_imp = env->c.n_imp;
-    r.rec_bytes = 0;
-    if (from_records) { // the trajectory as the packed records a fused rollout wrote (whole records: the 1v1 kernels)
-        susnet_record_layout_t lay;
-        if (int rc = susnet_record_layout_of(env, io->record_format, &lay)) return rc;
-        if (lay.record_bytes == 0 || lay.planar || lay.n_obs_segments != 1)
-            return fail(env, SUSNET_E_INVALID, "susnet_ring_append: reads packed records where the handle stores them whole (the 1v1 kernels); the "
-                                               "multi-agent kernels' planar records go through the separate trajectory tensors");
-        r.rec_bytes = lay.record_bytes; r.rec_obs = lay.off_obs; r.rec_act = lay.off_actions; r.rec_rew = lay.off_rewards;
-        r.rec_done = lay.off_done; r.rec_trunc = lay.off_truncated; r.rec_packed = lay.flags_packed;
-    }
-    const int64_t total = (int64_t)io->n_ticks * r.B;
-    r.n0 = total > io->max_size ? total - io->max_size : 0; // (earlier rows would be overwritten by later ones of this same launch)
-    r.n1 = total;
-    r.n0_t = r.n0 / r.B;
-    r.n0_b = (int32_t)(r.n0 % r.B);
-    r.pos_n0 = (io->idx + r.n0) % io->max_size;
-    if (r.n1 - r.n0 + r.B + 64 >= (1ll << 32)) return fail(SUSNET_E_INVALID, "susnet_ring_append: more than 2^32 rows in one launch");
-    // the row images of k_ring_append: states, next_states (bytes), rewards (f32), actions (bytes), done, imposters (i16); a wave
-    // takes 64 rows, or 32 / 16 / 8 when the window is long (trajectory_size x S bytes per row, twice): the reference's
-    // ReplayBuffer accepts any trajectory_size (replay_memory.py:33-44)
-    auto images = [&](size_t R) {
-        return 2 * ((R * (size_t)io->trajectory_size * (size_t)r.S + 15) & ~(size_t)15) + R * r.A * 4 + ((R * r.A + 15) & ~(size_t)15) + 64 +
-               R * r.n_imp * 2 + 16;
-    };
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // a (ticks x envs) tile per wave where the window is short enough for the tile's lanes to fetch the Tw ticks ahead of it and the
-    // images fit; else 64 (32 / 16 / 8) consecutive rows per wave
-    r.rows_per_wave = 64;
-    r.tile_log2e = 0;
-    const int te = env->ring_tile;
-    const size_t Tw = (size_t)io->trajectory_size;
-    const size_t tile_lds = te ? ((((size_t)(64 / te) + Tw) * te * r.S + 15) & ~(size_t)15) + ((((size_t)(64 / te) + Tw) * te + 15) & ~(size_t)15) +
-                                     2 * ((64 * Tw * r.S + 15) & ~(size_t)15) + 64 * (size_t)r.A * 4 + ((64 * (size_t)r.A + 15) & ~(size_t)15) + 64 +
-                                     ((64 * (size_t)r.n_imp * 2 + 15) & ~(size_t)15) + (64 / te) * sizeof(RingRun)
-                                : 0;
-    if (te && Tw * te <= 64 && tile_lds <= 32 * 1024 && r.A >= 2) {
-        r.tile_log2e = te == 8 ? 3 : te == 16 ? 4 : 5;
-        const int64_t t_first = r.n0 / r.B, tiles_t = (io->n_ticks - t_first + 64 / te - 1) / (64 / te), tiles_b = (r.B + te - 1) / te;
-        if (tiles_t * tiles_b > 0x7fffffffll) return fail(SUSNET_E_INVALID, "susnet_ring_append: too many tiles for one launch");
-        if (from_records) hipLaunchKernelGGL(k_ring_append_tile<true>, dim3((unsigned)(tiles_t * tiles_b)), dim3(64), tile_lds, st, r);
-        else hipLaunchKernelGGL(k_ring_append_tile<false>, dim3((unsigned)(tiles_t * tiles_b)), dim3(64), tile_lds, st, r);
-    } else {
-        while (r.rows_per_wave > 8 && images((size_t)r.rows_per_wave) > 64 * 1024) r.rows_per_wave /= 2;
-        const size_t sh = images((size_t)r.rows_per_wave);
-        if (sh > 64 * 1024) return fail(SUSNET_E_INVALID, "susnet_ring_append: trajectory_size x state size too large (8 rows of the window exceed 64 KiB)");
-        const int64_t waves = (r.n1 - r.n0 + r.rows_per_wave - 1) / r.rows_per_wave;
-        if (from_records) hipLaunchKernelGGL(k_ring_append<true>, dim3((unsigned)waves), dim3(64), sh, st, r);
-        else hipLaunchKernelGGL(k_ring_append<false>, dim3((unsigned)waves), dim3(64), sh, st, r);
-    }
-    if (from_records) hipLaunchKernelGGL(k_ring_window<true>, dim3((unsigned)((r.B + 63) / 64)), dim3(64), 0, st, r);
-    else hipLaunchKernelGGL(k_ring_window<false>, dim3((unsigned)((r.B + 63) / 64)), dim3(64), 0, st, r);
-    HIP_TRY(hipGetLastError());
-    return SUSNET_OK;
-}
 
 extern "C" int susnet_observe(susnet_env *env, const susnet_obs_spec *obs, void *stream) {
     if (int rc = check_bound(env)) return rc;
@@ -2237,485 +1600,5 @@ extern "C" int susnet_poll_errors(susnet_env *env, uint32_t *bits_out, void *str
     if (bits & SUSNET_ERRBIT_INDEX) return fail(SUSNET_E_ACTION_INDEX, "role-invalid action index");
     if (bits & SUSNET_ERRBIT_TAPE) return fail(SUSNET_E_TAPE, "random tape exhausted");
     if (bits & SUSNET_ERRBIT_ROW) return fail(SUSNET_E_ROW, "susnet_featurize: a state row holds a coordinate outside the grid");
-    return SUSNET_OK;
-}
-
-// ---- the learner's train step (susnet_train.h) ----
-struct DqnPlan {
-    int feat = 0;
-    TrainNet net[2];
-    int64_t G = 1;
-    uint64_t off_lists = 0, off_counts = 0, off_gacc[2] = {0, 0}, off_partial = 0, bytes = 0;
-};
-static int dqn_net(const susnet_dqn_team &tm, int feat, TrainNet &net) {
-    bool ok = false;
-    switch (feat) {
-    case FEAT_ONEHOT: ok = qnet_dims_ok<QRow1>(tm.dims, tm.n_dims); break;
-    case FEAT_ONEHOT_ALIVE_CLOSEST: ok = qnet_dims_ok<QRow3>(tm.dims, tm.n_dims); break;
-    case FEAT_COORD: ok = qnet_dims_ok<QRowC>(tm.dims, tm.n_dims); break;
-    }
-    if (!ok || tm.dims[0] > kTrMaxF) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: served are five Linear layers [F, <=256, <=128, <=64, <=32, <=32] on the "
-                                                             "compiled-in feature layouts (those of susnet_qnet_forward)");
-    int off = 0;
-    for (int l = 0; l < 6; l++) net.d[l] = tm.dims[l];
-    for (int l = 0; l < 5; l++) { // MLP.parameters(): Linear weight, Linear bias, PReLU weight, ... (dqn.py:322-329)
-        net.oW[l] = off;
-        off += net.d[l + 1] * net.d[l];
-        net.oB[l] = off;
-        off += net.d[l + 1];
-        if (l < 4) net.oA[l] = off++;
-    }
-    net.P = off;
-    net.Pp = (off + 1 + 3) / 4 * 4;
-    return SUSNET_OK;
-}
-static int dqn_plan(const susnet_env *env, const susnet_dqn_io *io, DqnPlan &pl) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null env / io");
-    if (env->c.n_imp != 1)
-        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: one imposter is served -- the reference's train_step fails on two or more, "
-                                      "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
-    if (io->trajectory_size != 1) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: trajectory_size 1 is served (MLP on one state)");
-    if (io->n < 0 || io->n > (1ll << 30)) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n out of range");
-    if (io->n_components < 1 || io->n_components > 16) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n_components");
-    pl.feat = qnet_feat(env, io->components, io->n_components);
-    if (!pl.feat) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: the feature layout has no compiled-in writer");
-    int64_t pmax = 4;
-    for (int tm = 0; tm < 2; tm++) {
-        pl.net[tm] = TrainNet{};
-        if (!io->team[tm].enabled) continue;
-        if (int rc = dqn_net(io->team[tm], pl.feat, pl.net[tm])) return rc;
-        pmax = std::max<int64_t>(pmax, pl.net[tm].Pp);
-    }
-    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
-    pl.G = std::max<int64_t>(1, std::min<int64_t>(kTrMaxGrid, tiles));
-    const int A = env->c.A;
-    uint64_t o = 0;
-    pl.off_lists = o;
-    o = up(o + 4ull * 2 * A * (uint64_t)std::max<int64_t>(io->n, 1), 256);
-    pl.off_counts = o;
-    o = up(o + 4ull * 2 * A, 256);
-    for (int tm = 0; tm < 2; tm++) {
-        pl.off_gacc[tm] = o;
-        o = up(o + 4ull * (uint64_t)std::max(pl.net[tm].Pp, 4), 256);
-    }
-    pl.off_partial = o;
-    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)pmax, 256);
-    pl.bytes = o;
-    return SUSNET_OK;
-}
-
-extern "C" int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out) {
-    DqnPlan pl;
-    if (int rc = dqn_plan(env, io, pl)) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_dqn_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
-}
-
-template <class ROW>
-static int dqn_launch(const susnet_env *env, const susnet_dqn_io *io, const DqnPlan &pl, hipStream_t st) {
-    // the kernel's dynamic-LDS ceiling, set once per device (a cheap host call; not repeated inside a capture after the first eager step)
-    static std::atomic<uint64_t> lds_set{0};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(lds_set.load() & bit)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_train_grad<ROW>), hipFuncAttributeMaxDynamicSharedMemorySize, kTrLdsBytes));
-        lds_set.fetch_or(bit);
-    }
-    char *ws = static_cast<char *>(io->workspace);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
-    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
-    TrainRing ring{io->states, io->next_states, io->actions, io->rewards, io->dones, io->imposters, io->max_size,
-                   (int32_t)env->layout.obs_raw_size, (int32_t)env->c.A, (int32_t)env->c.n_imp};
-    const int64_t N = io->n;
-    hipLaunchKernelGGL(k_train_select, dim3(1), dim3(kTrThreads), kTrThreads * 4, st, ring, io->indices, N, lists, counts, gacc[0], pl.net[0].P, gacc[1],
-                       pl.net[1].P, io->losses_out);
-    HIP_TRY(hipGetLastError());
-    if (N == 0) return SUSNET_OK;
-    for (int agent = 0; agent < env->c.A; agent++)
-        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
-            const susnet_dqn_team &T = io->team[tm];
-            if (!T.enabled) continue;
-            hipLaunchKernelGGL(k_train_grad<ROW>, dim3((unsigned)pl.G), dim3(kTrThreads), kTrLdsBytes, st, ring, pl.net[tm], T.params, T.target_params, lists,
-                               counts, N, agent, tm, (float)io->gamma, partial, T.step);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm], counts, agent, tm, partial,
-                               (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
-            HIP_TRY(hipGetLastError());
-        }
-    for (int tm = 0; tm < 2; tm++) {
-        const susnet_dqn_team &T = io->team[tm];
-        if (!T.enabled || !T.packed) continue;
-        hipLaunchKernelGGL(k_train_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256)), dim3(256), 0, st, pl.net[tm], T.params, T.packed);
-        HIP_TRY(hipGetLastError());
-    }
-    return SUSNET_OK;
-}
-
-// what susnet_dqn_train_step requires of one io beyond dqn_plan (the sweep asks the same of every learner)
-static int dqn_check_io(const susnet_dqn_io *io, const DqnPlan &pl) {
-    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
-        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: workspace missing, smaller than susnet_dqn_workspace_bytes or not 256-byte aligned");
-    if (!io->states || !io->next_states || !io->actions || !io->rewards || !io->dones || !io->imposters || !io->losses_out || io->max_size < 1 ||
-        (io->n > 0 && !io->indices))
-        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null ring tensor / indices / losses_out");
-    for (int tm = 0; tm < 2; tm++) {
-        const susnet_dqn_team &T = io->team[tm];
-        if (T.enabled && (!T.params || !T.target_params || !T.exp_avg || !T.exp_avg_sq || !T.step))
-            return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: an enabled team needs params / target_params / exp_avg / exp_avg_sq / step");
-    }
-    return SUSNET_OK;
-}
-
-extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream) {
-    if (int rc = check_bound(env)) return rc;
-    DqnPlan pl;
-    if (int rc = dqn_plan(env, io, pl)) return rc;
-    if (int rc = dqn_check_io(io, pl)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (pl.feat) {
-    case FEAT_ONEHOT: return dqn_launch<QRow1>(env, io, pl, st);
-    case FEAT_COORD: return dqn_launch<QRowC>(env, io, pl, st);
-    default: return dqn_launch<QRow3>(env, io, pl, st);
-    }
-}
-
-// ---- a sweep's train step: K learners in the launches of one (susnet_train.h, k_train_sweep_*) ----
-template <class ROW>
-static int dqn_sweep_launch(susnet_env *const *envs, const susnet_dqn_io *ios, int K, const DqnPlan *pls, hipStream_t st) {
-    static std::atomic<uint64_t> lds_set{0}; // (as dqn_launch: the dynamic-LDS ceiling of this instantiation, once per device)
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(lds_set.load() & bit)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_train_sweep_grad<ROW>), hipFuncAttributeMaxDynamicSharedMemorySize, kTrLdsBytes));
-        lds_set.fetch_or(bit);
-    }
-    const susnet_env *env = envs[0];
-    const DqnPlan &pl = pls[0]; // dims, n and the agent count agree: every learner has this grid and these nets
-    const int64_t N = ios[0].n;
-    TrainSelTable sel{};
-    TrainTable tab[2] = {};
-    bool packs[2] = {false, false};
-    for (int k = 0; k < K; k++) {
-        const susnet_dqn_io &io = ios[k];
-        char *ws = static_cast<char *>(io.workspace);
-        int32_t *lists = reinterpret_cast<int32_t *>(ws + pls[k].off_lists), *counts = reinterpret_cast<int32_t *>(ws + pls[k].off_counts);
-        float *gacc[2] = {reinterpret_cast<float *>(ws + pls[k].off_gacc[0]), reinterpret_cast<float *>(ws + pls[k].off_gacc[1])};
-        const TrainRing ring{io.states, io.next_states, io.actions, io.rewards, io.dones, io.imposters, io.max_size,
-                             (int32_t)envs[k]->layout.obs_raw_size, (int32_t)envs[k]->c.A, (int32_t)envs[k]->c.n_imp};
-        sel.l[k] = TrainSelLearner{ring, io.indices, lists, counts, gacc[0], gacc[1], io.losses_out};
-        for (int tm = 0; tm < 2; tm++) {
-            const susnet_dqn_team &T = io.team[tm];
-            if (!T.enabled) continue;
-            tab[tm].l[k] = TrainLearner{ring, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, lists, counts, gacc[tm],
-                                        reinterpret_cast<float *>(ws + pls[k].off_partial), io.losses_out, T.packed,
-                                        T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
-            packs[tm] = packs[tm] || T.packed != nullptr;
-        }
-    }
-    const unsigned Ku = (unsigned)K;
-    hipLaunchKernelGGL(k_train_sweep_select, dim3(1, Ku), dim3(kTrThreads), kTrThreads * 4, st, sel, N, pl.net[0].P, pl.net[1].P);
-    HIP_TRY(hipGetLastError());
-    if (N == 0) return SUSNET_OK;
-    for (int agent = 0; agent < env->c.A; agent++)
-        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
-            if (!ios[0].team[tm].enabled) continue;
-            hipLaunchKernelGGL(k_train_sweep_grad<ROW>, dim3((unsigned)pl.G, Ku), dim3(kTrThreads), kTrLdsBytes, st, tab[tm], pl.net[tm], N, agent, tm);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_train_sweep_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm], agent, tm,
-                               (int)pl.G);
-            HIP_TRY(hipGetLastError());
-        }
-    for (int tm = 0; tm < 2; tm++) {
-        if (!ios[0].team[tm].enabled || !packs[tm]) continue;
-        hipLaunchKernelGGL(k_train_sweep_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm]);
-        HIP_TRY(hipGetLastError());
-    }
-    return SUSNET_OK;
-}
-
-extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream) {
-    if (!envs || !ios) return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: null envs / ios");
-    if (n_learners < 1 || n_learners > SUSNET_DQN_MAX_LEARNERS)
-        return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
-                                          std::to_string(SUSNET_DQN_MAX_LEARNERS));
-    const int K = n_learners;
-    auto who = [](int k, const std::string &what) { return "susnet_dqn_train_sweep: learner " + std::to_string(k) + ": " + what; };
-    DqnPlan pls[SUSNET_DQN_MAX_LEARNERS];
-    for (int k = 0; k < K; k++) { // each learner passes susnet_dqn_train_step's checks ...
-        int rc = check_bound(envs[k]);
-        if (!rc) rc = dqn_plan(envs[k], &ios[k], pls[k]);
-        if (!rc) rc = dqn_check_io(&ios[k], pls[k]);
-        if (rc) return fail(rc, who(k, g_err));
-    }
-    const susnet_env *e0 = envs[0];
-    const susnet_dqn_io &i0 = ios[0];
-    for (int k = 1; k < K; k++) { // ... and all agree on what shapes the step
-        const susnet_env *e = envs[k];
-        const susnet_dqn_io &io = ios[k];
-        const char *field = nullptr;
-        if (e->c.A != e0->c.A || e->c.n_imp != e0->c.n_imp) field = "agent count";
-        else if (e->layout.obs_raw_size != e0->layout.obs_raw_size) field = "raw row size";
-        else if (e->c.N != e0->c.N || memcmp(e->c.grid_rows, e0->c.grid_rows, sizeof(e0->c.grid_rows)) != 0) field = "grid";
-        else if (io.n_components != i0.n_components || memcmp(io.components, i0.components, sizeof(int32_t) * (size_t)i0.n_components) != 0)
-            field = "components";
-        else if (pls[k].feat != pls[0].feat) field = "feature layout";
-        else if (io.n != i0.n) field = "n";
-        for (int tm = 0; tm < 2 && !field; tm++) {
-            if ((io.team[tm].enabled != 0) != (i0.team[tm].enabled != 0)) field = tm ? "team[1].enabled" : "team[0].enabled";
-            else if (io.team[tm].enabled && (io.team[tm].n_dims != i0.team[tm].n_dims || memcmp(io.team[tm].dims, i0.team[tm].dims, sizeof(int32_t) * 6) != 0))
-                field = tm ? "team[1].dims" : "team[0].dims";
-        }
-        if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " differs from learner 0's (a sweep runs learners of one shape)"));
-    }
-    for (int k = 1; k < K; k++) // no two learners write the same memory
-        for (int j = 0; j < k; j++) {
-            const char *field = nullptr;
-            if (ios[k].workspace == ios[j].workspace) field = "workspace";
-            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
-            for (int a = 0; a < 2 && !field; a++)
-                for (int b = 0; b < 2 && !field; b++)
-                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
-                        field = a ? "team[1].params" : "team[0].params";
-            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
-        }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (pls[0].feat) {
-    case FEAT_ONEHOT: return dqn_sweep_launch<QRow1>(envs, ios, K, pls, st);
-    case FEAT_COORD: return dqn_sweep_launch<QRowC>(envs, ios, K, pls, st);
-    default: return dqn_sweep_launch<QRow3>(envs, ios, K, pls, st);
-    }
-}
-
-// ---- the dense learner's train step (susnet_mlp_train.h; the kernels: inst_mlp_train.hip) ----
-struct MlpTrainPlan {
-    MlpTrainNet net[2];
-    TrainNet adam[2]; // what k_train_adam reads: P and Pp
-    int64_t G = 1;
-    uint64_t off_lists = 0, off_counts = 0, off_gacc[2] = {0, 0}, off_partial = 0, off_z = 0, bytes = 0;
-};
-static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, MlpTrainPlan &pl) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_train_step: null env / io");
-    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
-    if (env->c.n_imp != 1)
-        return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
-                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
-    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + std::to_string(env->c.A) + " (served: 2 .. 16)");
-    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + std::to_string((long long)io->n) + " (served: 0 .. 2^30)");
-    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
-    int64_t pmax = 4, zmax = 0;
-    int F = 0;
-    for (int tm = 0; tm < 2; tm++) {
-        pl.net[tm] = MlpTrainNet{};
-        pl.adam[tm] = TrainNet{};
-        const susnet_dqn_team &T = io->team[tm];
-        if (!T.enabled) continue;
-        const std::string who = "team[" + std::to_string(tm) + "].";
-        if (T.n_dims < 2 || T.n_dims > 8) return bad(who + "n_dims = " + std::to_string(T.n_dims) + " (served: 2 .. 8, i.e. 1 .. 7 Linear layers)");
-        const int nl = T.n_dims - 1;
-        if (T.dims[0] < 1 || T.dims[0] > SUSNET_MLP_MAX_F)
-            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
-        for (int l = 1; l < nl; l++)
-            if (T.dims[l] < 1 || T.dims[l] > kMtMaxHidden)
-                return bad(who + "dims[" + std::to_string(l) + "] = " + std::to_string(T.dims[l]) + " (hidden widths: 1 .. " + std::to_string(kMtMaxHidden) + ")");
-        if (T.dims[nl] < 1 || T.dims[nl] > kMtMaxOut)
-            return bad(who + "dims[" + std::to_string(nl) + "] = " + std::to_string(T.dims[nl]) + " (n_out: 1 .. " + std::to_string(kMtMaxOut) + ")");
-        if (F && T.dims[0] != F)
-            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " but team[0].dims[0] = " + std::to_string(F) + ": both teams read the same feature rows");
-        F = T.dims[0];
-        if (T.packed) return bad(who + "packed must be NULL (the dense forward reads params in place: there is no image to rewrite)");
-        if (!(T.lr >= 0.0) || !(T.beta1 >= 0.0 && T.beta1 < 1.0) || !(T.beta2 >= 0.0 && T.beta2 < 1.0) || !(T.eps >= 0.0))
-            return bad(who + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
-        MlpTrainNet &net = pl.net[tm];
-        net.nl = nl;
-        int off = 0, z = 0;
-        for (int l = 0; l <= nl; l++) net.d[l] = T.dims[l];
-        for (int l = 0; l < nl; l++) { // MLP.parameters(): Linear weight, Linear bias, PReLU weight, ... (dqn.py:322-329)
-            net.oW[l] = off;
-            off += net.d[l + 1] * net.d[l];
-            net.oB[l] = off;
-            off += net.d[l + 1];
-            if (l < nl - 1) {
-                net.oA[l] = off++;
-                net.zo[l] = z;
-                z += net.d[l + 1] * kTrTS;
-            }
-        }
-        net.P = off;
-        net.Pp = (off + 1 + 3) / 4 * 4;
-        net.Z = z;
-        pl.adam[tm].P = net.P;
-        pl.adam[tm].Pp = net.Pp;
-        pmax = std::max<int64_t>(pmax, net.Pp);
-        zmax = std::max<int64_t>(zmax, z);
-    }
-    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
-    pl.G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMtMaxGrid, tiles), (int64_t)(kMtMaxPartialBytes / (4ull * (uint64_t)pmax))));
-    const int A = env->c.A;
-    uint64_t o = 0;
-    pl.off_lists = o;
-    o = up(o + 4ull * 2 * A * (uint64_t)std::max<int64_t>(io->n, 1), 256);
-    pl.off_counts = o;
-    o = up(o + 4ull * 2 * A, 256);
-    for (int tm = 0; tm < 2; tm++) {
-        pl.off_gacc[tm] = o;
-        o = up(o + 4ull * (uint64_t)std::max(pl.net[tm].Pp, 4), 256);
-    }
-    pl.off_partial = o;
-    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)pmax, 256);
-    pl.off_z = o;
-    o = up(o + 4ull * (uint64_t)pl.G * (uint64_t)std::max<int64_t>(zmax, 4), 256);
-    pl.bytes = o;
-    return SUSNET_OK;
-}
-
-extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out) {
-    MlpTrainPlan pl;
-    if (int rc = mlp_train_plan(env, io, pl)) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_mlp_train_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
-}
-
-// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
-extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
-    MlpTrainPlan pl;
-    if (int rc = mlp_train_plan(env, io, pl)) return rc;
-    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
-    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
-        return bad("workspace missing, smaller than susnet_mlp_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
-                   " bytes) or not 256-byte aligned");
-    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
-    if (!io->actions) return bad("actions is NULL");
-    if (!io->rewards) return bad("rewards is NULL");
-    if (!io->dones) return bad("dones is NULL");
-    if (!io->imposters) return bad("imposters is NULL");
-    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
-    if (io->n > 0) {
-        if (!io->indices) return bad("indices is NULL");
-        if (!io->feat || misaligned(io->feat)) return bad("feat is NULL or not 4-byte aligned");
-        if (!io->next_feat || misaligned(io->next_feat)) return bad("next_feat is NULL or not 4-byte aligned");
-    }
-    for (int tm = 0; tm < 2; tm++) {
-        const susnet_dqn_team &T = io->team[tm];
-        if (!T.enabled) continue;
-        const std::string who = "team[" + std::to_string(tm) + "].";
-        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
-        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
-        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
-        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
-        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(io->workspace);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
-    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial), *zsave = reinterpret_cast<float *>(ws + pl.off_z);
-    const MlpTrainBatch b{io->feat, io->next_feat, io->actions, io->rewards, io->dones, io->imposters, io->indices, io->max_size, io->n,
-                          (int32_t)env->c.A, (int32_t)env->c.n_imp};
-    HIP_TRY(mlp_train_select_launch(b, lists, counts, gacc[0], pl.net[0].P, gacc[1], pl.net[1].P, io->losses_out, st));
-    if (io->n == 0) return SUSNET_OK;
-    for (int agent = 0; agent < env->c.A; agent++)
-        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
-            const susnet_dqn_team &T = io->team[tm];
-            if (!T.enabled) continue;
-            HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, zsave, T.step,
-                                          (int)pl.G, st));
-            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.adam[tm], counts, agent, tm, partial,
-                               (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
-            HIP_TRY(hipGetLastError());
-        }
-    return SUSNET_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// episode bookkeeping (susnet_episode_stats, susnet_episodes.h)
-// ---------------------------------------------------------------------------------------------------
-struct EpisodePlan {
-    int32_t A, B, W;
-    uint64_t carry_bytes, off_t, off_position, workspace_bytes;
-};
-
-static int episode_plan(const susnet_env *env, int64_t n_ticks, EpisodePlan &pl) {
-    if (!env) return fail(SUSNET_E_INVALID, "susnet_episode_stats: null env");
-    pl.A = env->c.A;
-    pl.B = env->c.B;
-    if (pl.A < 2 || pl.A > 12) return fail(env, SUSNET_E_INVALID, "susnet_episode_stats: 2 .. 12 agents are served");
-    if (n_ticks < 1) return fail(SUSNET_E_INVALID, "susnet_episode_stats: n_ticks must be positive");
-    pl.W = (pl.B + 63) / 64;
-    if (n_ticks * (int64_t)pl.W > 0x7fffffffll || n_ticks * (int64_t)pl.B > (1ll << 40))
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: n_ticks x batch too large for one call");
-    pl.off_t = 8ull * (uint64_t)pl.A * (uint64_t)pl.B;
-    pl.carry_bytes = pl.off_t + 4ull * (uint64_t)pl.B;
-    pl.off_position = up(4ull * (uint64_t)n_ticks * (uint64_t)pl.W, 256);
-    pl.workspace_bytes = pl.off_position + 8ull * (uint64_t)n_ticks * (uint64_t)pl.W;
-    return SUSNET_OK;
-}
-
-extern "C" int susnet_episode_stats_bytes(const susnet_env *env, int32_t n_ticks, uint64_t *carry_bytes_out, uint64_t *workspace_bytes_out) {
-    EpisodePlan pl;
-    if (int rc = episode_plan(env, n_ticks, pl)) return rc;
-    if (!carry_bytes_out || !workspace_bytes_out) return fail(SUSNET_E_INVALID, "susnet_episode_stats_bytes: null output");
-    *carry_bytes_out = pl.carry_bytes;
-    *workspace_bytes_out = pl.workspace_bytes;
-    return SUSNET_OK;
-}
-
-template <int A>
-static void episode_write_launch(const EpisodeArgs &p, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_episode_write<A>, dim3(grid), dim3(kEpThreads), 0, st, p);
-}
-
-extern "C" int susnet_episode_stats(susnet_env *env, const susnet_episode_io *io, void *stream) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_episode_stats: null env / io");
-    EpisodePlan pl;
-    if (int rc = episode_plan(env, io->n_ticks, pl)) return rc;
-    if (!io->rewards || !io->done || !io->truncated || !io->roles || !io->count || !io->dropped)
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: null feed array / count / dropped");
-    if (io->capacity < 0 || (io->capacity > 0 && !io->log)) return fail(SUSNET_E_INVALID, "susnet_episode_stats: capacity < 0, or a capacity without a log");
-    if (!(io->gamma == io->gamma)) return fail(SUSNET_E_INVALID, "susnet_episode_stats: gamma is NaN");
-    if (!io->carry || io->carry_bytes < pl.carry_bytes || (reinterpret_cast<uintptr_t>(io->carry) & 7u))
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: carry missing, smaller than susnet_episode_stats_bytes or not 8-byte aligned");
-    if (!io->workspace || io->workspace_bytes < pl.workspace_bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 7u))
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: workspace missing, smaller than susnet_episode_stats_bytes or not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(io->log) & 7u) || (reinterpret_cast<uintptr_t>(io->count) & 7u) || (reinterpret_cast<uintptr_t>(io->dropped) & 7u))
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: log / count / dropped must be 8-byte aligned");
-    if ((io->info == nullptr) != (io->info_log == nullptr)) return fail(SUSNET_E_INVALID, "susnet_episode_stats: info and info_log go together (both or neither)");
-    if ((reinterpret_cast<uintptr_t>(io->info) & 15u) || (reinterpret_cast<uintptr_t>(io->info_log) & 15u))
-        return fail(SUSNET_E_INVALID, "susnet_episode_stats: info / info_log must be 16-byte aligned");
-    EpisodeArgs p;
-    p.info = io->info; p.info_log = io->info_log;
-    p.rewards = io->rewards; p.done = io->done; p.truncated = io->truncated; p.roles = io->roles;
-    p.G = static_cast<double *>(io->carry);
-    p.t_episode = reinterpret_cast<int32_t *>(static_cast<char *>(io->carry) + pl.off_t);
-    p.log = io->log; p.capacity = io->capacity; p.count = io->count; p.dropped = io->dropped;
-    p.counts = static_cast<int32_t *>(io->workspace);
-    p.position = reinterpret_cast<int64_t *>(static_cast<char *>(io->workspace) + pl.off_position);
-    p.gamma = io->gamma; p.tick_base = io->tick_base;
-    p.T = io->n_ticks; p.B = pl.B; p.W = pl.W;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned grid = (unsigned)((pl.B + kEpThreads - 1) / kEpThreads);
-    hipLaunchKernelGGL(k_episode_count, dim3(grid), dim3(kEpThreads), 0, st, p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_episode_scan, dim3(1), dim3(kEpScanThreads), (kEpScanThreads / 64) * sizeof(long long), st, p);
-    HIP_TRY(hipGetLastError());
-    switch (pl.A) {
-    case 2: episode_write_launch<2>(p, grid, st); break;
-    case 3: episode_write_launch<3>(p, grid, st); break;
-    case 4: episode_write_launch<4>(p, grid, st); break;
-    case 5: episode_write_launch<5>(p, grid, st); break;
-    case 6: episode_write_launch<6>(p, grid, st); break;
-    case 7: episode_write_launch<7>(p, grid, st); break;
-    case 8: episode_write_launch<8>(p, grid, st); break;
-    case 9: episode_write_launch<9>(p, grid, st); break;
-    case 10: episode_write_launch<10>(p, grid, st); break;
-    case 11: episode_write_launch<11>(p, grid, st); break;
-    default: episode_write_launch<12>(p, grid, st); break;
-    }
-    HIP_TRY(hipGetLastError());
     return SUSNET_OK;
 }

@@ -1,0 +1,343 @@
+// susnet_capi_train.hip -- the DQN learners of the C ABI: susnet_dqn_train_step and susnet_dqn_train_sweep (the fused learner on the
+// compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step (the dense learner on any served stack;
+// its gradient kernels: inst_mlp_train.hip).  Both end every update with this unit's k_train_adam.
+#include <algorithm>
+#include <cstring>
+
+#include "susnet_qnet.h" // QNet, QRow1 / QRow3 / QRowC: the pack kernels write susnet_qnet_pack's image
+#include "susnet_train.h"
+#include "susnet_mlp_train.h"
+#include "susnet_host.h"
+
+using namespace susnet;
+
+// ---- the learner's train step (susnet_train.h) ----
+struct DqnPlan : TrWorkspace {
+    int feat = 0;
+    TrainNet net[2];
+    int64_t G = 1;
+    uint64_t bytes = 0;
+};
+static int dqn_net(const susnet_dqn_team &tm, int feat, TrainNet &net) {
+    bool ok = false;
+    switch (feat) {
+    case FEAT_ONEHOT: ok = qnet_dims_ok<QRow1>(tm.dims, tm.n_dims); break;
+    case FEAT_ONEHOT_ALIVE_CLOSEST: ok = qnet_dims_ok<QRow3>(tm.dims, tm.n_dims); break;
+    case FEAT_COORD: ok = qnet_dims_ok<QRowC>(tm.dims, tm.n_dims); break;
+    }
+    if (!ok || tm.dims[0] > kTrMaxF) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: served are five Linear layers [F, <=256, <=128, <=64, <=32, <=32] on the "
+                                                             "compiled-in feature layouts (those of susnet_qnet_forward)");
+    for (int l = 0; l < 6; l++) net.d[l] = tm.dims[l];
+    tr_param_layout(net, 5);
+    return SUSNET_OK;
+}
+static int dqn_plan(const susnet_env *env, const susnet_dqn_io *io, DqnPlan &pl) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null env / io");
+    if (env->c.n_imp != 1)
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: one imposter is served -- the reference's train_step fails on two or more, "
+                                      "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (io->trajectory_size != 1) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: trajectory_size 1 is served (MLP on one state)");
+    if (io->n < 0 || io->n > (1ll << 30)) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n out of range");
+    if (io->n_components < 1 || io->n_components > 16) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: n_components");
+    pl.feat = qnet_feat(env, io->components, io->n_components);
+    if (!pl.feat) return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: the feature layout has no compiled-in writer");
+    int64_t pmax = 4;
+    for (int tm = 0; tm < 2; tm++) {
+        pl.net[tm] = TrainNet{};
+        if (!io->team[tm].enabled) continue;
+        if (int rc = dqn_net(io->team[tm], pl.feat, pl.net[tm])) return rc;
+        pmax = std::max<int64_t>(pmax, pl.net[tm].Pp);
+    }
+    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
+    pl.G = std::max<int64_t>(1, std::min<int64_t>(kTrMaxGrid, tiles));
+    pl.bytes = tr_workspace_layout(pl, env->c.A, io->n, pl.net[0].Pp, pl.net[1].Pp, pl.G, pmax);
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out) {
+    DqnPlan pl;
+    if (int rc = dqn_plan(env, io, pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_dqn_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+template <class ROW>
+static int dqn_launch(const susnet_env *env, const susnet_dqn_io *io, const DqnPlan &pl, hipStream_t st) {
+    static LdsOptIn opted; // the dynamic-LDS ceiling of this instantiation's kernel, once per device (susnet_host.h)
+    HIP_TRY(lds_opt_in(reinterpret_cast<const void *>(&k_train_grad<ROW>), kTrLdsBytes, opted));
+    char *ws = static_cast<char *>(io->workspace);
+    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
+    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
+    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    TrainRing ring{io->states, io->next_states, io->actions, io->rewards, io->dones, io->imposters, io->max_size,
+                   (int32_t)env->layout.obs_raw_size, (int32_t)env->c.A, (int32_t)env->c.n_imp};
+    const int64_t N = io->n;
+    hipLaunchKernelGGL(k_train_select, dim3(1), dim3(kTrThreads), kTrThreads * 4, st, ring, io->indices, N, lists, counts, gacc[0], pl.net[0].P, gacc[1],
+                       pl.net[1].P, io->losses_out);
+    HIP_TRY(hipGetLastError());
+    if (N == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            const susnet_dqn_team &T = io->team[tm];
+            if (!T.enabled) continue;
+            hipLaunchKernelGGL(k_train_grad<ROW>, dim3((unsigned)pl.G), dim3(kTrThreads), kTrLdsBytes, st, ring, pl.net[tm], T.params, T.target_params, lists,
+                               counts, N, agent, tm, (float)io->gamma, partial, T.step);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
+                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
+            HIP_TRY(hipGetLastError());
+        }
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled || !T.packed) continue;
+        hipLaunchKernelGGL(k_train_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256)), dim3(256), 0, st, pl.net[tm], T.params, T.packed);
+        HIP_TRY(hipGetLastError());
+    }
+    return SUSNET_OK;
+}
+
+// what susnet_dqn_train_step requires of one io beyond dqn_plan (the sweep asks the same of every learner)
+static int dqn_check_io(const susnet_dqn_io *io, const DqnPlan &pl) {
+    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: workspace missing, smaller than susnet_dqn_workspace_bytes or not 256-byte aligned");
+    if (!io->states || !io->next_states || !io->actions || !io->rewards || !io->dones || !io->imposters || !io->losses_out || io->max_size < 1 ||
+        (io->n > 0 && !io->indices))
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: null ring tensor / indices / losses_out");
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (T.enabled && (!T.params || !T.target_params || !T.exp_avg || !T.exp_avg_sq || !T.step))
+            return fail(SUSNET_E_INVALID, "susnet_dqn_train_step: an enabled team needs params / target_params / exp_avg / exp_avg_sq / step");
+    }
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_train_step(susnet_env *env, const susnet_dqn_io *io, void *stream) {
+    if (int rc = check_bound(env)) return rc;
+    DqnPlan pl;
+    if (int rc = dqn_plan(env, io, pl)) return rc;
+    if (int rc = dqn_check_io(io, pl)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (pl.feat) {
+    case FEAT_ONEHOT: return dqn_launch<QRow1>(env, io, pl, st);
+    case FEAT_COORD: return dqn_launch<QRowC>(env, io, pl, st);
+    default: return dqn_launch<QRow3>(env, io, pl, st);
+    }
+}
+
+// ---- a sweep's train step: K learners in the launches of one (susnet_train.h, k_train_sweep_*) ----
+template <class ROW>
+static int dqn_sweep_launch(susnet_env *const *envs, const susnet_dqn_io *ios, int K, const DqnPlan *pls, hipStream_t st) {
+    static LdsOptIn opted; // (as dqn_launch)
+    HIP_TRY(lds_opt_in(reinterpret_cast<const void *>(&k_train_sweep_grad<ROW>), kTrLdsBytes, opted));
+    const susnet_env *env = envs[0];
+    const DqnPlan &pl = pls[0]; // dims, n and the agent count agree: every learner has this grid and these nets
+    const int64_t N = ios[0].n;
+    TrainSelTable sel{};
+    TrainTable tab[2] = {};
+    bool packs[2] = {false, false};
+    for (int k = 0; k < K; k++) {
+        const susnet_dqn_io &io = ios[k];
+        char *ws = static_cast<char *>(io.workspace);
+        int32_t *lists = reinterpret_cast<int32_t *>(ws + pls[k].off_lists), *counts = reinterpret_cast<int32_t *>(ws + pls[k].off_counts);
+        float *gacc[2] = {reinterpret_cast<float *>(ws + pls[k].off_gacc[0]), reinterpret_cast<float *>(ws + pls[k].off_gacc[1])};
+        const TrainRing ring{io.states, io.next_states, io.actions, io.rewards, io.dones, io.imposters, io.max_size,
+                             (int32_t)envs[k]->layout.obs_raw_size, (int32_t)envs[k]->c.A, (int32_t)envs[k]->c.n_imp};
+        sel.l[k] = TrainSelLearner{ring, io.indices, lists, counts, gacc[0], gacc[1], io.losses_out};
+        for (int tm = 0; tm < 2; tm++) {
+            const susnet_dqn_team &T = io.team[tm];
+            if (!T.enabled) continue;
+            tab[tm].l[k] = TrainLearner{ring, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, lists, counts, gacc[tm],
+                                        reinterpret_cast<float *>(ws + pls[k].off_partial), io.losses_out, T.packed,
+                                        T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
+            packs[tm] = packs[tm] || T.packed != nullptr;
+        }
+    }
+    const unsigned Ku = (unsigned)K;
+    hipLaunchKernelGGL(k_train_sweep_select, dim3(1, Ku), dim3(kTrThreads), kTrThreads * 4, st, sel, N, pl.net[0].P, pl.net[1].P);
+    HIP_TRY(hipGetLastError());
+    if (N == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            if (!ios[0].team[tm].enabled) continue;
+            hipLaunchKernelGGL(k_train_sweep_grad<ROW>, dim3((unsigned)pl.G, Ku), dim3(kTrThreads), kTrLdsBytes, st, tab[tm], pl.net[tm], N, agent, tm);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_train_sweep_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm], agent, tm,
+                               (int)pl.G);
+            HIP_TRY(hipGetLastError());
+        }
+    for (int tm = 0; tm < 2; tm++) {
+        if (!ios[0].team[tm].enabled || !packs[tm]) continue;
+        hipLaunchKernelGGL(k_train_sweep_pack<ROW>, dim3((unsigned)((QNet<ROW>::kPacked + 255) / 256), Ku), dim3(256), 0, st, tab[tm], pl.net[tm]);
+        HIP_TRY(hipGetLastError());
+    }
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream) {
+    if (!envs || !ios) return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: null envs / ios");
+    if (n_learners < 1 || n_learners > SUSNET_DQN_MAX_LEARNERS)
+        return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
+                                          std::to_string(SUSNET_DQN_MAX_LEARNERS));
+    const int K = n_learners;
+    auto who = [](int k, const std::string &what) { return "susnet_dqn_train_sweep: learner " + std::to_string(k) + ": " + what; };
+    DqnPlan pls[SUSNET_DQN_MAX_LEARNERS];
+    for (int k = 0; k < K; k++) { // each learner passes susnet_dqn_train_step's checks ...
+        int rc = check_bound(envs[k]);
+        if (!rc) rc = dqn_plan(envs[k], &ios[k], pls[k]);
+        if (!rc) rc = dqn_check_io(&ios[k], pls[k]);
+        if (rc) return fail(rc, who(k, g_err));
+    }
+    const susnet_env *e0 = envs[0];
+    const susnet_dqn_io &i0 = ios[0];
+    for (int k = 1; k < K; k++) { // ... and all agree on what shapes the step
+        const susnet_env *e = envs[k];
+        const susnet_dqn_io &io = ios[k];
+        const char *field = nullptr;
+        if (e->c.A != e0->c.A || e->c.n_imp != e0->c.n_imp) field = "agent count";
+        else if (e->layout.obs_raw_size != e0->layout.obs_raw_size) field = "raw row size";
+        else if (e->c.N != e0->c.N || memcmp(e->c.grid_rows, e0->c.grid_rows, sizeof(e0->c.grid_rows)) != 0) field = "grid";
+        else if (io.n_components != i0.n_components || memcmp(io.components, i0.components, sizeof(int32_t) * (size_t)i0.n_components) != 0)
+            field = "components";
+        else if (pls[k].feat != pls[0].feat) field = "feature layout";
+        else if (io.n != i0.n) field = "n";
+        for (int tm = 0; tm < 2 && !field; tm++) {
+            if ((io.team[tm].enabled != 0) != (i0.team[tm].enabled != 0)) field = tm ? "team[1].enabled" : "team[0].enabled";
+            else if (io.team[tm].enabled && (io.team[tm].n_dims != i0.team[tm].n_dims || memcmp(io.team[tm].dims, i0.team[tm].dims, sizeof(int32_t) * 6) != 0))
+                field = tm ? "team[1].dims" : "team[0].dims";
+        }
+        if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " differs from learner 0's (a sweep runs learners of one shape)"));
+    }
+    for (int k = 1; k < K; k++) // no two learners write the same memory
+        for (int j = 0; j < k; j++) {
+            const char *field = nullptr;
+            if (ios[k].workspace == ios[j].workspace) field = "workspace";
+            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
+            for (int a = 0; a < 2 && !field; a++)
+                for (int b = 0; b < 2 && !field; b++)
+                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
+                        field = a ? "team[1].params" : "team[0].params";
+            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
+        }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (pls[0].feat) {
+    case FEAT_ONEHOT: return dqn_sweep_launch<QRow1>(envs, ios, K, pls, st);
+    case FEAT_COORD: return dqn_sweep_launch<QRowC>(envs, ios, K, pls, st);
+    default: return dqn_sweep_launch<QRow3>(envs, ios, K, pls, st);
+    }
+}
+
+// ---- the dense learner's train step (susnet_mlp_train.h; the kernels: inst_mlp_train.hip) ----
+struct MlpTrainPlan : TrWorkspace {
+    MlpTrainNet net[2];
+    int64_t G = 1;
+    uint64_t off_z = 0, bytes = 0;
+};
+static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, MlpTrainPlan &pl) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_train_step: null env / io");
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
+    if (env->c.n_imp != 1)
+        return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
+                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + std::to_string(env->c.A) + " (served: 2 .. 16)");
+    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + std::to_string((long long)io->n) + " (served: 0 .. 2^30)");
+    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
+    int64_t pmax = 4, zmax = 0;
+    int F = 0;
+    for (int tm = 0; tm < 2; tm++) {
+        pl.net[tm] = MlpTrainNet{};
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (T.n_dims < 2 || T.n_dims > 8) return bad(who + "n_dims = " + std::to_string(T.n_dims) + " (served: 2 .. 8, i.e. 1 .. 7 Linear layers)");
+        const int nl = T.n_dims - 1;
+        if (T.dims[0] < 1 || T.dims[0] > SUSNET_MLP_MAX_F)
+            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
+        for (int l = 1; l < nl; l++)
+            if (T.dims[l] < 1 || T.dims[l] > kMtMaxHidden)
+                return bad(who + "dims[" + std::to_string(l) + "] = " + std::to_string(T.dims[l]) + " (hidden widths: 1 .. " + std::to_string(kMtMaxHidden) + ")");
+        if (T.dims[nl] < 1 || T.dims[nl] > kMtMaxOut)
+            return bad(who + "dims[" + std::to_string(nl) + "] = " + std::to_string(T.dims[nl]) + " (n_out: 1 .. " + std::to_string(kMtMaxOut) + ")");
+        if (F && T.dims[0] != F)
+            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " but team[0].dims[0] = " + std::to_string(F) + ": both teams read the same feature rows");
+        F = T.dims[0];
+        if (T.packed) return bad(who + "packed must be NULL (the dense forward reads params in place: there is no image to rewrite)");
+        if (!(T.lr >= 0.0) || !(T.beta1 >= 0.0 && T.beta1 < 1.0) || !(T.beta2 >= 0.0 && T.beta2 < 1.0) || !(T.eps >= 0.0))
+            return bad(who + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
+        MlpTrainNet &net = pl.net[tm];
+        net.nl = nl;
+        for (int l = 0; l <= nl; l++) net.d[l] = T.dims[l];
+        tr_param_layout(net, nl);
+        for (int l = 0; l < nl - 1; l++) { // the hidden layers' saved pre-activations, [unit][32] each
+            net.zo[l] = net.Z;
+            net.Z += net.d[l + 1] * kTrTS;
+        }
+        pmax = std::max<int64_t>(pmax, net.Pp);
+        zmax = std::max<int64_t>(zmax, net.Z);
+    }
+    const int64_t tiles = (io->n + kTrTS - 1) / kTrTS;
+    pl.G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMtMaxGrid, tiles), (int64_t)(kMtMaxPartialBytes / (4ull * (uint64_t)pmax))));
+    pl.off_z = tr_workspace_layout(pl, env->c.A, io->n, pl.net[0].Pp, pl.net[1].Pp, pl.G, pmax);
+    pl.bytes = up(pl.off_z + 4ull * (uint64_t)pl.G * (uint64_t)std::max<int64_t>(zmax, 4), 256);
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out) {
+    MlpTrainPlan pl;
+    if (int rc = mlp_train_plan(env, io, pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_mlp_train_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
+extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
+    MlpTrainPlan pl;
+    if (int rc = mlp_train_plan(env, io, pl)) return rc;
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
+        return bad("workspace missing, smaller than susnet_mlp_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
+                   " bytes) or not 256-byte aligned");
+    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
+    if (!io->actions) return bad("actions is NULL");
+    if (!io->rewards) return bad("rewards is NULL");
+    if (!io->dones) return bad("dones is NULL");
+    if (!io->imposters) return bad("imposters is NULL");
+    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
+    if (io->n > 0) {
+        if (!io->indices) return bad("indices is NULL");
+        if (!io->feat || misaligned(io->feat)) return bad("feat is NULL or not 4-byte aligned");
+        if (!io->next_feat || misaligned(io->next_feat)) return bad("next_feat is NULL or not 4-byte aligned");
+    }
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
+        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
+        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
+        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
+        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(io->workspace);
+    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
+    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
+    float *partial = reinterpret_cast<float *>(ws + pl.off_partial), *zsave = reinterpret_cast<float *>(ws + pl.off_z);
+    const MlpTrainBatch b{io->feat, io->next_feat, io->actions, io->rewards, io->dones, io->imposters, io->indices, io->max_size, io->n,
+                          (int32_t)env->c.A, (int32_t)env->c.n_imp};
+    HIP_TRY(mlp_train_select_launch(b, lists, counts, gacc[0], pl.net[0].P, gacc[1], pl.net[1].P, io->losses_out, st));
+    if (io->n == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            const susnet_dqn_team &T = io->team[tm];
+            if (!T.enabled) continue;
+            HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, zsave, T.step,
+                                          (int)pl.G, st));
+            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
+                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
+            HIP_TRY(hipGetLastError());
+        }
+    return SUSNET_OK;
+}

@@ -24,8 +24,7 @@ namespace susnet {
 
 constexpr int kDnThreads = 512, kDnWaves = kDnThreads / 64, kDnRows = SUSNET_MLP_ROW_TILE, kDnMaxGrid = SUSNET_MLP_MAX_GRID;
 constexpr int kDnMaxHidden = 256, kDnMaxOut = 32;
-constexpr size_t kDnLdsNoOptIn = 48 * 1024; // a dynamic LDS block up to this size launches without hipFuncSetAttribute
-constexpr int kDnMaxDevices = 64;
+constexpr size_t kDnLdsNoOptIn = 48 * 1024; // a dynamic LDS block up to this size launches without the opt-in (lds_opt_in, susnet_host.h)
 static_assert(kDnRows == 64, "the LDS layout below is 64 rows per unit");
 
 struct DenseArgs { // by value: the kernel's arguments

@@ -1,0 +1,83 @@
+// susnet_host.h -- what every host-side translation unit of the C ABI shares (susnet_capi*.hip; the launchers of inst_qnet_dense.hip and
+// inst_mlp_train.hip take the LDS opt-in from here): the handle, the error conventions, and the small helpers of the entry points.
+// Private to csrc/: the public interface is include/susnet.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdint>
+#include <string>
+
+#include "susnet_device.h"
+
+struct susnet_env {
+    susnet_config cfg;
+    susnet::Consts c;
+    susnet::State s;
+    bool bound = false;
+    bool float_exact = false;
+    uint64_t ticks = 0; // steps taken (index of the production action stream)
+    // test hooks, read ONCE at susnet_create (include/susnet.h SUSNET_OVERRIDE_*)
+    bool force_generic = false;
+    int ring_tile = 0;   // susnet_ring_append: environments of a wave's (ticks x envs) tile (8 / 16 / 32; 0: consecutive rows per wave)
+    uint64_t launch_limit = (1ull << 31) - 1u, launch_limit_default = (1ull << 31) - 1u;
+    int spec = 0; // pick_spec(): which compiled-in kernel family serves the handle (0 = generic)
+    susnet_layout layout;
+    uint64_t off_err, off_agent, off_job, off_jobdone, off_t, off_timer, off_flags, off_rng, off_msteps, off_mfix, off_msab,
+        off_mkv, off_life, off_tickw, off_ep;
+};
+
+extern thread_local std::string g_err; // what susnet_last_error returns (defined in susnet_capi.hip)
+inline int fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
+// (messages about a handle created under test hooks say so: a stray environment variable is then visible where it bites)
+inline int fail(const susnet_env *env, int code, const std::string &msg) {
+    std::string m = msg;
+    if (env && env->layout.test_overrides) {
+        m += " [handle created with";
+        if (env->layout.test_overrides & SUSNET_OVERRIDE_FORCE_GENERIC) m += " SUSNET_FORCE_GENERIC";
+        if (env->layout.test_overrides & SUSNET_OVERRIDE_EPW) m += " SUSNET_EPW";
+        if (env->layout.test_overrides & SUSNET_OVERRIDE_TRAJ_MAX_BYTES) m += " SUSNET_TRAJ_MAX_BYTES";
+        if (env->layout.test_overrides & SUSNET_OVERRIDE_RING_TILE) m += " SUSNET_RING_TILE";
+        m += "]";
+    }
+    return fail(code, m);
+}
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) return fail(SUSNET_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+inline uint64_t up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+inline int check_bound(const susnet_env *env) {
+    if (!env) return fail(SUSNET_E_INVALID, "null handle");
+    if (!env->bound) return fail(SUSNET_E_STATE, "state blob not bound (susnet_bind_state)");
+    return SUSNET_OK;
+}
+inline dim3 grid_for(const susnet_env *env) { return dim3((unsigned)((env->c.B + susnet::kBlock - 1) / susnet::kBlock)); }
+
+// A kernel's dynamic-LDS ceiling (hipFuncAttributeMaxDynamicSharedMemorySize), raised once per device: a cheap host call, made on the first
+// launch on a device and -- `opted` is the kernel's own flag array, one static per launch site -- never again, so after one eager step
+// nothing is repeated inside a stream capture.  A device past the array is opted in on every call.
+constexpr int kLdsOptInDevices = 64;
+using LdsOptIn = std::atomic<bool>[kLdsOptInDevices];
+inline hipError_t lds_opt_in(const void *kernel, int bytes, LdsOptIn &opted) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    const bool known = dev >= 0 && dev < kLdsOptInDevices;
+    if (known && opted[dev].load(std::memory_order_acquire)) return hipSuccess;
+    if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
+    if (known) opted[dev].store(true, std::memory_order_release);
+    return hipSuccess;
+}
+
+// the Q-network entry points' own checks (susnet_capi.hip), which the fused learner shares: the compiled-in feature layout of a
+// component list on this handle (0 = none), and whether a layer stack fits QNet<ROW> (instantiated there for QRow1 / QRow3 / QRowC)
+int qnet_feat(const susnet_env *env, const int32_t *comp, int32_t ncomp);
+template <class ROW>
+bool qnet_dims_ok(const int32_t *dims, int32_t n_dims);

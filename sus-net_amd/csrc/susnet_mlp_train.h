@@ -9,7 +9,7 @@
 //   per (agent, enabled team) update, two launches:
 //   k_mlp_train_grad    a workgroup walks tiles of 32 of the list's rows.  Target network on next_feat (max over actions -> y, y = r on done
 //                       rows), online network on feat, then 2 (Q - y) / count back through the stack; every matrix product on
-//                       v_mfma_f32_32x32x2_f32 through susnet_train.h's tr_mfma / tr_forward_layer / tr_backward_layer on stride-33 transposed
+//                       v_mfma_f32_32x32x2_f32 through susnet_train_core.h's tr_mfma / tr_forward_layer / tr_backward_layer on stride-33 transposed
 //                       LDS tiles.  What differs from k_train_grad, because the stack is not known at compile time:
 //                         - LDS holds two activation and two dZ buffers of 256 units (135 KB) whatever the stack; the input rows are never
 //                           resident (layer 1 and its weight gradient read them from global memory), and the hidden pre-activations the backward
@@ -19,7 +19,7 @@
 //                           -- the same lane of the same wave on every tile; biases likewise, slopes and the loss in registers;
 //                         - a workgroup without a tile zero-fills its partial; nothing at all runs for an empty list;
 //                         - the layer loops are unrolled over the 7 possible layers with guards (the stack travels as a kernel argument).
-//   k_train_adam        susnet_train.h's, as it is: sums the partials in workgroup order, accumulates, Adam.  It reads P and Pp only.
+//   k_train_adam        susnet_train.h's, as it is (susnet_capi_train.hip launches it): sums the partials in workgroup order, accumulates, Adam.
 // Grid: G = min(kMtMaxGrid, tiles of n, kMtMaxPartialBytes / (4 Pp)) workgroups, at least 1: the partials stay at or below 64 MiB.
 #pragma once
 

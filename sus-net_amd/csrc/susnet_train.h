@@ -31,15 +31,15 @@
 // with table.l[blockIdx.y]: workgroup (g, k) of a sweep does exactly what workgroup g of learner k's own call does -- same tiles, same
 // partial layout, same order of every sum -- so a learner's results are bitwise those of susnet_dqn_train_step.  Learners never touch
 // one another's memory: no waits between workgroups, no atomics.
+// What the dense learner shares (tr_mfma and the layer functions, tr_select, tr_block_sum, tr_adam, the host-side layouts) is
+// susnet_train_core.h; the structures and every kernel are here -- k_train_adam too, which susnet_capi_train.hip launches for both learners.
 #pragma once
 
 #include "susnet_flat.h"
+#include "susnet_train_core.h"
 
 namespace susnet {
 
-typedef float tr_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTrThreads = 512, kTrWaves = kTrThreads / 64, kTrTS = 32, kTrSP = 33;
 constexpr int kTrMaxF = 96;        // input width cap (the compiled-in layouts: 36, 4, 88)
 constexpr int kTrMaxTiles = 9;     // weight-gradient tiles per wave: (3 x 8 + 8 x 4 + 4 x 2 + 2 + 1 = 67) / 8 waves, rounded up
 constexpr int kTrMaxGrid = 256;    // workgroups of k_train_grad (one per CU)
@@ -97,107 +97,16 @@ constexpr int kTrOX = 0, kTrOZ1 = kTrOX + kTrMaxF * kTrSP, kTrOZ2 = kTrOZ1 + 256
 constexpr int kTrLdsBytes = kTrLdsFloats * 4;
 static_assert(kTrLdsBytes <= 160 * 1024, "gfx950 LDS");
 
-__device__ __forceinline__ float tr_prelu(float z, float a) { return z > 0.0f ? z : a * z; } // torch.prelu
-
-// D[i][j] (+)= sum_p A(i, p) B(p, j) for one 32 x 32 tile, K steps of 2 on v_mfma_f32_32x32x2_f32: lane l feeds A(l % 32, p0 + l / 32)
-// and B(p0 + l / 32, l % 32); register r of the result is row 8 (r / 4) + 4 (l / 32) + r % 4, column l % 32.
-template <class FA, class FB>
-__device__ __forceinline__ tr_f32x16 tr_mfma(FA fa, FB fb, int K, tr_f32x16 acc, int lane) {
-    const int i = lane & 31, h = lane >> 5;
-    for (int p0 = 0; p0 < K; p0 += 2) {
-        const int p = p0 + h;
-        const float a = p < K ? fa(i, p) : 0.0f, b = p < K ? fb(p, i) : 0.0f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    return acc;
-}
-__device__ __forceinline__ int tr_row(int r, int lane) { return 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3); }
-
-// forward of layer l (0-based): Z_out[n][s] = b[n] + sum_k W[n][k] h_in[k][s], h_in = X (l = 0) or prelu(Z_in)
-__device__ __forceinline__ void tr_forward_layer(const float *__restrict__ W, const float *__restrict__ bias, int dk, int dn, const float *zin, float slope_in,
-                                                 bool raw_in, float *zout, int wave, int lane) {
-    const int nt_count = (dn + 31) / 32;
-    for (int nt = wave; nt < nt_count; nt += kTrWaves) {
-        const int n0 = nt * 32;
-        tr_f32x16 acc = {};
-        acc = tr_mfma([&](int i, int p) { return n0 + i < dn ? W[(size_t)(n0 + i) * dk + p] : 0.0f; },
-                      [&](int p, int j) { const float z = zin[p * kTrSP + j]; return raw_in ? z : tr_prelu(z, slope_in); }, dk, acc, lane);
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int n = n0 + tr_row(r, lane);
-            if (n < dn) zout[n * kTrSP + (lane & 31)] = acc[r] + bias[n];
-        }
-    }
-}
-
-// backward through layer l: dH_in[k][s] = sum_n W[n][k] dZ[n][s]
-__device__ __forceinline__ void tr_backward_layer(const float *__restrict__ W, int dk, int dn, const float *dz, float *dh, int wave, int lane) {
-    const int kt_count = (dk + 31) / 32;
-    for (int kt = wave; kt < kt_count; kt += kTrWaves) {
-        const int k0 = kt * 32;
-        tr_f32x16 acc = {};
-        acc = tr_mfma([&](int i, int p) { return k0 + i < dk ? W[(size_t)p * dk + k0 + i] : 0.0f; }, [&](int p, int j) { return dz[p * kTrSP + j]; }, dn,
-                      acc, lane);
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int k = k0 + tr_row(r, lane);
-            if (k < dk) dh[k * kTrSP + (lane & 31)] = acc[r];
-        }
-    }
-}
-
-// the team's rows of one agent: ring row ids, stable order
-__device__ __forceinline__ int32_t *tr_list(int32_t *lists, int64_t N, int agent, int team) { return lists + ((int64_t)agent * 2 + team) * N; }
-
-// ---- k_train_select: ONE workgroup of kTrThreads (per learner) ----
-__device__ __forceinline__ void tr_select(const TrainRing &ring, const int64_t *__restrict__ idx, int64_t N, int32_t *lists, int32_t *counts, float *gacc0,
-                                          int P0, float *gacc1, int P1, float *losses, int32_t *tr_scan) {
-    const int t = threadIdx.x;
-    for (int p = t; p < P0; p += kTrThreads) gacc0[p] = 0.0f;
-    for (int p = t; p < P1; p += kTrThreads) gacc1[p] = 0.0f;
-    if (t < 2) losses[t] = 0.0f;
-    const int64_t chunk = (N + kTrThreads - 1) / kTrThreads, lo = (int64_t)t * chunk, hi = lo + chunk < N ? lo + chunk : N;
-    for (int agent = 0; agent < ring.A; agent++) {
-        int32_t c = 0;
-        for (int64_t s = lo; s < hi; s++) {
-            int64_t r = idx[s];
-            r = r < 0 ? 0 : (r >= ring.max_size ? ring.max_size - 1 : r);
-            c += (int)ring.imposters[r * ring.n_imp] == agent ? 1 : 0;
-        }
-        tr_scan[t] = c;
-        __syncthreads();
-        for (int off = 1; off < kTrThreads; off <<= 1) { // inclusive Hillis-Steele scan
-            const int32_t v = t >= off ? tr_scan[t - off] : 0;
-            __syncthreads();
-            tr_scan[t] += v;
-            __syncthreads();
-        }
-        const int32_t total = tr_scan[kTrThreads - 1];
-        int32_t pi = tr_scan[t] - c;                       // imposter rows before this chunk
-        int32_t pc = (int32_t)(lo < N ? lo : N) - pi;        // crew rows before this chunk
-        int32_t *li = tr_list(lists, N, agent, 0), *lc = tr_list(lists, N, agent, 1);
-        for (int64_t s = lo; s < hi; s++) {
-            int64_t r = idx[s];
-            r = r < 0 ? 0 : (r >= ring.max_size ? ring.max_size - 1 : r);
-            if ((int)ring.imposters[r * ring.n_imp] == agent) li[pi++] = (int32_t)r;
-            else lc[pc++] = (int32_t)r;
-        }
-        if (t == 0) {
-            counts[2 * agent] = total;
-            counts[2 * agent + 1] = (int32_t)N - total;
-        }
-        __syncthreads();
-    }
-}
+// ---- k_train_select: ONE workgroup of kTrThreads (per learner); the lists hold ring rows ----
 __global__ __launch_bounds__(kTrThreads) void k_train_select(TrainRing ring, const int64_t *__restrict__ idx, int64_t N, int32_t *lists, int32_t *counts,
                                                              float *gacc0, int P0, float *gacc1, int P1, float *losses) {
     extern __shared__ int32_t tr_scan[];
-    tr_select(ring, idx, N, lists, counts, gacc0, P0, gacc1, P1, losses, tr_scan);
+    tr_select<false>(ring, idx, N, lists, counts, gacc0, P0, gacc1, P1, losses, tr_scan);
 }
 __global__ __launch_bounds__(kTrThreads) void k_train_sweep_select(TrainSelTable tab, int64_t N, int P0, int P1) {
     extern __shared__ int32_t tr_scan[];
     const TrainSelLearner &a = tab.l[blockIdx.y];
-    tr_select(a.ring, a.idx, N, a.lists, a.counts, a.gacc0, P0, a.gacc1, P1, a.losses, tr_scan);
+    tr_select<false>(a.ring, a.idx, N, a.lists, a.counts, a.gacc0, P0, a.gacc1, P1, a.losses, tr_scan);
 }
 
 // the tile's feature rows X[k][s] (k < F) from flattened states (base.py:234-235: positions, then alive flags)
@@ -385,12 +294,7 @@ __device__ __forceinline__ void tr_grad(const TrainRing &ring, const TrainNet &n
     float *red = lds;
     __syncthreads();
     for (int q = 0; q < 5; q++) {
-        red[t] = q < 4 ? sacc[q] : lacc;
-        __syncthreads();
-        for (int off = kTrThreads / 2; off > 0; off >>= 1) {
-            if (t < off) red[t] += red[t + off];
-            __syncthreads();
-        }
+        tr_block_sum(q < 4 ? sacc[q] : lacc, red, t);
         if (t == 0) out[q < 4 ? net.oA[q] : net.P] = red[0];
         __syncthreads();
     }
@@ -409,43 +313,16 @@ __global__ __launch_bounds__(kTrThreads) void k_train_sweep_grad(TrainTable tab,
     tr_grad<ROW>(a.ring, net, a.prm, a.tgt, a.lists, a.counts, N, agent, team, a.gamma, a.partial, a.step, lds);
 }
 
-// ---- k_train_adam: thread per parameter ----
-__device__ __forceinline__ void tr_adam(const TrainNet &net, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial, int G,
-                                        float *__restrict__ gacc, float *__restrict__ prm, float *__restrict__ m1, float *__restrict__ m2,
-                                        const float *__restrict__ step, double lr, double beta1, double beta2, double eps, float *losses) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int count = counts[2 * agent + team];
-    if (count == 0 || p > net.P) return; // an empty team takes no step (train.py:101)
-    float g = 0.0f;
-    for (int w = 0; w < G; w++) g += partial[(size_t)w * net.Pp + p];
-    if (p == net.P) { // F.mse_loss (mean) of this update, summed over agents (train.py:139)
-        losses[team] += g / (float)count;
-        return;
-    }
-    const float ga = gacc[p] + g; // loss.backward() accumulates into .grad (zero_grad once per call, train.py:64-67)
-    gacc[p] = ga;
-    // torch.optim.adam._single_tensor_adam: lerp, mul + addcmul, bias corrections in double, sqrt(v) / sqrt(bc2) + eps, addcdiv
-    const double st = (double)step[0];
-    const float b1w = (float)(1.0 - beta1);
-    float m = m1[p];
-    m = m + b1w * (ga - m);
-    float v = m2[p];
-    v = v * (float)beta2 + (float)(1.0 - beta2) * (ga * ga);
-    m1[p] = m;
-    m2[p] = v;
-    const double bc1 = 1.0 - pow(beta1, st), bc2 = 1.0 - pow(beta2, st);
-    const float step_size = (float)(lr / bc1), bc2s = (float)sqrt(bc2);
-    const float denom = sqrtf(v) / bc2s + (float)eps;
-    prm[p] = prm[p] + (-step_size) * (m / denom);
-}
-__global__ __launch_bounds__(256) void k_train_adam(TrainNet net, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial,
+
+// ---- k_train_adam: thread per parameter (tr_adam); the single-learner form serves the dense learner's stacks too ----
+__global__ __launch_bounds__(256) void k_train_adam(int P, int Pp, const int32_t *__restrict__ counts, int agent, int team, const float *__restrict__ partial,
                                                     int G, float *__restrict__ gacc, float *__restrict__ prm, float *__restrict__ m1, float *__restrict__ m2,
                                                     const float *__restrict__ step, double lr, double beta1, double beta2, double eps, float *losses) {
-    tr_adam(net, counts, agent, team, partial, G, gacc, prm, m1, m2, step, lr, beta1, beta2, eps, losses);
+    tr_adam(P, Pp, counts, agent, team, partial, G, gacc, prm, m1, m2, step, lr, beta1, beta2, eps, losses);
 }
 __global__ __launch_bounds__(256) void k_train_sweep_adam(TrainTable tab, TrainNet net, int agent, int team, int G) {
     const TrainLearner &a = tab.l[blockIdx.y];
-    tr_adam(net, a.counts, agent, team, a.partial, G, a.gacc, a.prm, a.m1, a.m2, a.step, a.lr, a.beta1, a.beta2, a.eps, a.losses);
+    tr_adam(net.P, net.Pp, a.counts, agent, team, a.partial, G, a.gacc, a.prm, a.m1, a.m2, a.step, a.lr, a.beta1, a.beta2, a.eps, a.losses);
 }
 
 // ---- k_train_pack: the team's packed image from torch-layout parameters (susnet_capi.hip qnet_pack, element for element) ----

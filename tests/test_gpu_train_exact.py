@@ -4,7 +4,7 @@ hand through the C ABI with canaries around every buffer it writes:
         compiled-in layouts, dyadic constants, power-of-two counts: every float32 summation order gives the float64 result (asserted on
         the reference), so every gradient word must be EQUAL -- at every stack shape dqn_net accepts, with one tile and with two tiles
         per workgroup;
-  c.    Adam through both compiled copies of k_train_adam (this step and susnet_mlp_train_step) against float64 Adam, within bounds
+  c.    Adam through the one k_train_adam, reached from both train steps (this step and susnet_mlp_train_step), against float64 Adam, within bounds
         counted from the kernel's roundings;
   d.    ragged counts and random float weights against torch_train_step on float64 CPU modules, at the project's tolerances.
 test_train_exact_host.py states on the CPU that the restatement equals float64 autograd and that the cases cover what is relied on here."""
@@ -90,7 +90,7 @@ def test_exact_two_tiles_per_workgroup(pkg, envs, case_key):
     check_exact(pkg, envs[case_key[0]], T.two_tile_case(case_key), packed=False)
 
 
-# ---- c. Adam, both compiled copies -------------------------------------------------------------------------------------------------------
+# ---- c. Adam, from both train steps ------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def adam_reference():
     """The Adam case, its exact gradient per team (one update per call) and, per team, eps and float64 Adam after each of the four calls."""

@@ -573,7 +573,7 @@ def two_tile_case(case_key):
     return case
 
 
-# ---- the Adam case: both compiled copies of k_train_adam on one exact batch ----------------------------------------------------------------
+# ---- the Adam case: the one k_train_adam, reached from both train steps, on one exact batch -------------------------------------------------
 ADAM_CASE = ("onehot1", "reference", 64, (64, 0))  # agent 0 the imposter on every row: each team has ONE non-empty update per call
 ADAM_BETAS = (0.5, 0.75)
 ADAM_LRS = (0.0, 0.0, 0.0, 2.0 ** -6)  # the learning rate of calls 1 .. 4
