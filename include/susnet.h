@@ -14,6 +14,7 @@
  *   susnet_policy_actions  run_game's acting step          src/visualize.py:547-562 (train.py:355-381, epsilon = 0)
  *   susnet_qnet_*          MLP.forward on the flat features src/models/dqn.py:72-108, 322-329
  *   susnet_mlp_forward     MLP.forward of any served layer stack on caller-supplied feature rows  src/models/dqn.py:72-108, 322-329
+ *   susnet_spatial_forward SpatialDQN.forward (eval mode) on the planes / perspective features     src/models/dqn.py:141-301
  *   susnet_window_push     the acting loop's state window, one tick on (as feature rows)  src/train.py:318-322, 388-389, 441-445
  *   susnet_policy_step     argmax per team + env.step        src/visualize.py:547-582
  *   susnet_step            FourRoomEnv.step                src/environment/base.py:332-407 (tagging.py:120-235)
@@ -450,6 +451,70 @@ typedef struct susnet_mlp_io {
     float *q_out;              /* device [n][n_out] float32 */
 } susnet_mlp_io;
 int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream);
+
+/* The reference's SpatialDQN.forward (src/models/dqn.py:205-301) in EVAL mode, float32, on the featurizers' (spatial, non_spatial) tensors
+ * where they lie.  Row r of n is (env r / agents, agent r % agents); its window holds T steps.  Per row and step t:
+ *     image [C][N][N] = spatial + env * spatial_stride[0] + agent * spatial_stride[1] + t * spatial_stride[2]      (floats)
+ *     -> n_conv x { Conv2d(k x k, stride, padding, dilation) + ReLU }   (CNNModel, dqn.py:141-181; the reference's repeated last layer is
+ *        simply one more entry of the lists here)
+ *     -> flattened in torch's [C_out][H][W] order, that step's Fn non-spatial features (non_spatial + the same three kinds of stride)
+ *        appended (the view and torch.cat of dqn.py:292-294): one row of rnn_in [n][T][R], R = conv_out[n_conv-1] * H_out^2 + Fn
+ *     -> nn.RNN(tanh, batch_first, num_layers = rnn_layers) over the T rows from h = 0 (RNNModel, dqn.py:184-202, 296)
+ *     -> the PReLU head -- make_mlp, as susnet_mlp_forward: Linear + nn.PReLU() with ONE slope per layer, none after the last Linear -- on
+ *        the last layer's hidden state at t = T - 1 (dqn.py:298-299): q_out [n][dims[n_dims-1]].
+ *   The PERSPECTIVE featurizer's buffers are served in place (spatial [B][T][A][C][N][N]: strides T*A*C*N*N, C*N*N, A*C*N*N), and so are the
+ * GLOBAL featurizer's shared planes ([B][T][C][N][N] with an agent stride of 0: the image's convolution is then recomputed per agent).
+ *   EVAL-mode semantics: there is no dropout in the kernels (nn.RNN's dropout between layers acts in training mode only).
+ *   Parameters are read where torch keeps them, as susnet_mlp_forward reads them: conv_weight[l] [conv_out[l]][C_in][k][k], w_ih[l]
+ * [rnn_hidden][R or rnn_hidden], w_hh[l] [rnn_hidden][rnn_hidden], the head's weight[l] [dims[l+1]][dims[l]], all row-major and only 4-byte
+ * aligned; no packed image, no host step: after an in-place optimizer step the next launch reads the new values.
+ *   Summation orders (float32 throughout): a convolution output is ONE fmaf chain that starts as the bias and runs over (c_in, ky, kx) in
+ * ascending order, padding taps being zeros; a recurrent unit's accumulator starts as b_ih + b_hh, then k ascends over W_ih (x_t, or the
+ * layer below's h at t), then over W_hh (the layer's own h at t - 1; nothing is added at t = 0), and tanh is applied to the result; the
+ * head's outputs are chains over k ascending that start as the bias.  tanh(x) is copysign(-e / (e + 2), x) with e = expm1f(-2 |x|): exactly
+ * 0 at 0 and exactly +-1 for |x| >= 16.  Values agree with torch's to float32 summation-order and tanh rounding differences.
+ *   Served: T in 1 .. 8, N in 1 .. 16, C in 1 .. 32; n_conv in 1 .. 4, conv_out[l] in 1 .. 32, k in {1, 3, 5}, conv_stride[l] in 1 .. 4,
+ * conv_padding[l] in 0 .. 8, conv_dilation[l] in 1 .. 4, every layer's output size (size + 2 padding - dilation (k - 1) - 1) / stride + 1 at
+ * least 1; Fn >= 0; R <= SUSNET_SPATIAL_MAX_R; rnn_layers in 1 .. 4, rnn_hidden in 1 .. 256; the head n_dims in 2 .. 8 with dims[0] ==
+ * rnn_hidden, hidden widths 1 .. 256 and at most 32 outputs; n >= 1, agents >= 1, strides >= 0; every pointer non-NULL and 4-byte aligned;
+ * the LDS of a call within a workgroup's 160 KiB: one image's two activation buffers for the convolutions, and (rnn_layers + 1) x 64 rows x
+ * max(rnn_hidden, the head's hidden widths) floats for the recurrence (so rnn_hidden 256 is served with one layer, 128 with up to four).
+ * Anything else: SUSNET_E_INVALID, with a message that names the field, before anything is launched.
+ *   Two launches: the convolutions on the vector ALU (at most SUSNET_SPATIAL_CONV_MAX_GRID workgroups walking groups of up to
+ * SUSNET_SPATIAL_CONV_GROUP images), the recurrence and the head on v_mfma_f32_32x32x2_f32 (the tiles and grid of susnet_mlp_forward).  rnn_in
+ * is caller-supplied workspace, written whole.  The handle supplies the stream and error conventions only. */
+#define SUSNET_SPATIAL_MAX_T 8
+#define SUSNET_SPATIAL_MAX_N 16
+#define SUSNET_SPATIAL_MAX_C 32
+#define SUSNET_SPATIAL_MAX_CONV 4
+#define SUSNET_SPATIAL_MAX_R 4096
+#define SUSNET_SPATIAL_MAX_RNN_LAYERS 4
+#define SUSNET_SPATIAL_CONV_GROUP 16
+#define SUSNET_SPATIAL_CONV_MAX_GRID 1024
+typedef struct susnet_spatial_io {
+    int32_t T, N, C;                 /* window steps, image size, input channels */
+    int32_t n_conv, k;               /* 1 .. 4 convolutions of one square kernel size k in {1, 3, 5} */
+    int32_t conv_out[4], conv_stride[4], conv_padding[4], conv_dilation[4];
+    const float *conv_weight[4];     /* device [conv_out[l]][C_in][k][k] */
+    const float *conv_bias[4];       /* device [conv_out[l]] */
+    int32_t Fn;                      /* non-spatial features per step */
+    int32_t rnn_layers, rnn_hidden;
+    const float *w_ih[4], *w_hh[4], *b_ih[4], *b_hh[4]; /* nn.RNN's weight_ih_l{l} .. bias_hh_l{l} */
+    int32_t n_dims;                  /* the head, as susnet_mlp_io: 2 .. 8 */
+    int32_t dims[8];                 /* [rnn_hidden, h1, .., n_actions] */
+    const float *weight[7];
+    const float *bias[7];
+    const float *slope[6];
+    const float *spatial;            /* device float32 */
+    int64_t spatial_stride[3];       /* floats: per env, per agent, per timestep; an image [C][N][N] is contiguous */
+    const float *non_spatial;        /* device float32 */
+    int64_t non_spatial_stride[3];   /* floats: per env, per agent, per timestep; a step's Fn features are contiguous */
+    int32_t agents;                  /* row r is env r / agents, agent r % agents */
+    int64_t n;                       /* rows */
+    float *rnn_in;                   /* device workspace [n][T][R] float32 */
+    float *q_out;                    /* device [n][dims[n_dims-1]] float32 */
+} susnet_spatial_io;
+int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *io, void *stream);
 
 /* The trainer's state window (src/train.py:318-322, 388-389, 441-445) as FEATURE rows on the device, one tick on.  The reference keeps the
  * last T flattened states per env, featurizes all T every tick (FlatFeaturizer.fit, src/features/model_ready.py:325-354) and MLP.forward

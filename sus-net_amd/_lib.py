@@ -18,6 +18,11 @@ DQN_MAX_LEARNERS = 16  # SUSNET_DQN_MAX_LEARNERS
 MLP_MAX_F, MLP_ROW_TILE, MLP_MAX_GRID = 1024, 64, 512  # SUSNET_MLP_*: susnet_mlp_forward's input width cap, rows per tile, grid cap
 MLP_MAX_HIDDEN, MLP_MAX_OUT = 256, 32
 WINDOW_MAX_T = 8  # susnet_window_push: states per window
+# SUSNET_SPATIAL_*: susnet_spatial_forward's bounds (window steps, image size, input channels, convolutions, RNN input width, RNN layers),
+# the convolution kernel's images per group and grid cap
+SPATIAL_MAX_T, SPATIAL_MAX_N, SPATIAL_MAX_C, SPATIAL_MAX_CONV, SPATIAL_MAX_R, SPATIAL_MAX_RNN_LAYERS = 8, 16, 32, 4, 4096, 4
+SPATIAL_CONV_GROUP, SPATIAL_CONV_MAX_GRID = 16, 1024
+SPATIAL_LDS_BYTES = 160 * 1024  # a workgroup's LDS: (rnn_layers + 1) x 64 rows x max(rnn_hidden, head widths) floats must fit
 
 VARIANT_BASE, VARIANT_ITG, VARIANT_TAGGING = 0, 1, 2
 RNG_TAPE, RNG_PHILOX = 1, 2
@@ -37,7 +42,7 @@ LIFETIME_NAMES = ["episodes", "crew_won", "imposter_won", "truncated", "imp_kill
 # every symbol include/susnet.h declares
 EXPORTS = [
     "susnet_abi_version", "susnet_last_error", "susnet_create", "susnet_destroy", "susnet_get_layout",
-    "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
+    "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
     "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
@@ -113,6 +118,16 @@ class PolicyOpts(C.Structure):
 class MlpIO(C.Structure):
     _fields_ = [("n_dims", C.c_int32), ("dims", C.c_int32 * 8), ("weight", C.c_void_p * 7), ("bias", C.c_void_p * 7), ("slope", C.c_void_p * 6),
                 ("rows", C.c_void_p), ("n", C.c_int64), ("q_out", C.c_void_p)]
+
+
+class SpatialIO(C.Structure):
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("n_conv", C.c_int32), ("k", C.c_int32),
+                ("conv_out", C.c_int32 * 4), ("conv_stride", C.c_int32 * 4), ("conv_padding", C.c_int32 * 4), ("conv_dilation", C.c_int32 * 4),
+                ("conv_weight", C.c_void_p * 4), ("conv_bias", C.c_void_p * 4), ("Fn", C.c_int32), ("rnn_layers", C.c_int32), ("rnn_hidden", C.c_int32),
+                ("w_ih", C.c_void_p * 4), ("w_hh", C.c_void_p * 4), ("b_ih", C.c_void_p * 4), ("b_hh", C.c_void_p * 4),
+                ("n_dims", C.c_int32), ("dims", C.c_int32 * 8), ("weight", C.c_void_p * 7), ("bias", C.c_void_p * 7), ("slope", C.c_void_p * 6),
+                ("spatial", C.c_void_p), ("spatial_stride", C.c_int64 * 3), ("non_spatial", C.c_void_p), ("non_spatial_stride", C.c_int64 * 3),
+                ("agents", C.c_int32), ("n", C.c_int64), ("rnn_in", C.c_void_p), ("q_out", C.c_void_p)]
 
 
 class WindowIO(C.Structure):
@@ -237,6 +252,7 @@ def lib():
     L.susnet_qnet_pack.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_void_p), P(C.c_void_p), C.c_void_p, C.c_void_p]
     L.susnet_qnet_forward.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, P(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.susnet_mlp_forward.argtypes = [C.c_void_p, P(MlpIO), C.c_void_p]
+    L.susnet_spatial_forward.argtypes = [C.c_void_p, P(SpatialIO), C.c_void_p]
     L.susnet_window_push.argtypes = [C.c_void_p, P(WindowIO), C.c_void_p]
     L.susnet_record_layout.argtypes = [C.c_void_p, P(RecordLayout)]
     L.susnet_set_launch_limit.argtypes = [C.c_void_p, C.c_uint64]

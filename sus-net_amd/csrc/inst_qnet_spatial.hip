@@ -1,0 +1,241 @@
+// the SpatialDQN forward kernels (susnet_spatial.h: susnet_spatial_forward) -- a translation unit of its own, default scheduling like the
+// other Q-network units
+#include "susnet_spatial.h"
+
+#include "susnet_host.h" // lds_opt_in
+
+namespace susnet {
+
+// ---- the convolution stack ------------------------------------------------------------------------------------------------------------
+// A parameter read through the constant address space: nothing writes the parameters while the kernel runs, and with a lane-independent
+// index the load is a scalar one whose result is the FMA's scalar operand.
+typedef const __attribute__((address_space(4))) float *sp_const_ptr;
+__device__ __forceinline__ float sp_param(const float *p, int idx) { return ((sp_const_ptr)(uintptr_t)p)[idx]; }
+
+// one Conv2d + ReLU layer of a group's `cnt` images: lane -> (image g, output pixel p), all Co <= CB output channels in registers
+template <int CB, int K>
+__device__ __forceinline__ void sp_conv_layer(const float *__restrict__ W, const float *__restrict__ bias, int Ci, int Co, int Hi, int Ho, int stride,
+                                              int pad, int dil, const float *in, int slot_in, float *out, int64_t slot_out, int cnt, int tid) {
+    const int P = Ho * Ho, items = cnt * P, plane = Hi * Hi;
+    for (int it = tid; it < items; it += kSpThreads) {
+        const int g = it / P, p = it - g * P, oy = p / Ho, ox = p - oy * Ho;
+        float acc[CB];
+#pragma unroll
+        for (int j = 0; j < CB; j++) acc[j] = sp_param(bias, j < Co ? j : Co - 1);
+        // the taps of this pixel: offset inside a channel plane (clamped to 0 for a padding tap) and whether the tap is inside the image
+        int off[K * K];
+        bool ok[K * K];
+#pragma unroll
+        for (int ky = 0; ky < K; ky++)
+#pragma unroll
+            for (int kx = 0; kx < K; kx++) {
+                const int iy = oy * stride - pad + ky * dil, ix = ox * stride - pad + kx * dil;
+                const bool inside = iy >= 0 && iy < Hi && ix >= 0 && ix < Hi;
+                ok[ky * K + kx] = inside;
+                off[ky * K + kx] = inside ? iy * Hi + ix : 0;
+            }
+        const float *src = in + g * slot_in;
+        for (int ci = 0; ci < Ci; ci++) {
+#pragma unroll
+            for (int tap = 0; tap < K * K; tap++) {
+                const float xv = src[ci * plane + off[tap]];
+                const float x = ok[tap] ? xv : 0.0f;
+#pragma unroll
+                for (int j = 0; j < CB; j++) { // (wave-uniform weight index: a channel past Co repeats the last one, its result is dropped)
+                    const float w = sp_param(W, ((j < Co ? j : Co - 1) * Ci + ci) * (K * K) + tap);
+                    acc[j] = fmaf(w, x, acc[j]);
+                }
+            }
+        }
+        float *dst = out + g * slot_out + p;
+#pragma unroll
+        for (int j = 0; j < CB; j++)
+            if (j < Co) dst[j * P] = acc[j] <= 0.0f ? 0.0f : acc[j]; // ReLU
+    }
+}
+
+// CB: the smallest of 4 / 8 / 16 / 32 that holds the stack's widest layer; a layer of at most half that width runs the narrower form
+template <int CB, int K>
+__global__ __launch_bounds__(kSpThreads) void k_spatial_conv(SpatialConvArgs a) {
+    extern __shared__ float sp_smem[];
+    const int tid = threadIdx.x;
+    const int64_t images = a.n * a.T, groups = (images + a.G - 1) / a.G;
+    const int imgsz = a.C * a.size[0] * a.size[0];
+    const int last_p = a.size[a.n_conv] * a.size[a.n_conv], conv_cols = a.co[a.n_conv - 1] * last_p;
+    float *buf0 = sp_smem, *buf1 = sp_smem + a.G * a.slot0;
+    for (int64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const int64_t m0 = grp * a.G;
+        const int cnt = (int)(images - m0 < a.G ? images - m0 : a.G);
+        for (int g = 0; g < cnt; g++) { // image m = row r, window step t; row r = env r / agents, agent r % agents
+            const int64_t m = m0 + g, r = m / a.T, t = m - r * a.T, env = r / a.agents, ag = r - env * a.agents;
+            const float *img = a.spatial + env * a.sp_stride[0] + ag * a.sp_stride[1] + t * a.sp_stride[2];
+            for (int e = tid; e < imgsz; e += kSpThreads) buf0[g * a.slot0 + e] = img[e];
+            const float *ns = a.non_spatial + env * a.ns_stride[0] + ag * a.ns_stride[1] + t * a.ns_stride[2];
+            float *row = a.rnn_in + m * a.R + conv_cols; // the torch.cat of dqn.py:294: the non-spatial columns follow the flattened planes
+            for (int f = tid; f < a.Fn; f += kSpThreads) row[f] = ns[f];
+        }
+        __syncthreads();
+        for (int l = 0; l < a.n_conv; l++) {
+            const bool last = l == a.n_conv - 1;
+            const float *in = (l & 1) ? buf1 : buf0;
+            const int slot_in = (l & 1) ? a.slot1 : a.slot0;
+            const int slot_lds = (l & 1) ? a.slot0 : a.slot1;
+            float *out_lds = (l & 1) ? buf0 : buf1;
+            const int Ci = l == 0 ? a.C : a.co[l - 1], Co = a.co[l];
+            float *out = last ? a.rnn_in + m0 * a.R : out_lds;
+            const int64_t slot_out = last ? (int64_t)a.R : (int64_t)slot_lds;
+            if (CB > 4 && Co <= CB / 2)
+                sp_conv_layer<(CB > 4 ? CB / 2 : CB), K>(a.W[l], a.B[l], Ci, Co, a.size[l], a.size[l + 1], a.stride[l], a.pad[l], a.dil[l], in, slot_in, out,
+                                                         slot_out, cnt, tid);
+            else
+                sp_conv_layer<CB, K>(a.W[l], a.B[l], Ci, Co, a.size[l], a.size[l + 1], a.stride[l], a.pad[l], a.dil[l], in, slot_in, out, slot_out, cnt, tid);
+            __syncthreads();
+        }
+    }
+}
+
+// ---- the recurrence and the head --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sp_tanh(float x) {
+    const float ax = fabsf(x);
+    const float e = expm1f(-2.0f * ax); // in (-1, 0]: tanh |x| = (1 - e^{-2|x|}) / (1 + e^{-2|x|}) = -e / (e + 2), no cancellation near 0
+    const float t = ax >= 16.0f ? 1.0f : -e / (e + 2.0f);
+    return copysignf(t, x);
+}
+
+__global__ __launch_bounds__(kDnThreads) void k_spatial_rnn(SpatialRnnArgs a) {
+    extern __shared__ float sr_smem[];
+    const int t_ = threadIdx.x, lane = t_ & 63, i = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(t_ >> 6);
+    const int L = a.L, H = a.H, nb = L + 1, nl = a.n_dims - 1;
+    const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t base = tile * kDnRows;
+        int c = 0; // step t L + l writes buffer c mod (L + 1); h_{l-1}[t] is one buffer back, h_l[t-1] one buffer on
+        for (int t = 0; t < a.T; t++) {
+            for (int l = 0; l < L; l++, c = c + 1 == nb ? 0 : c + 1) {
+                float *hout = sr_smem + (size_t)c * a.buf;
+                const float *below = sr_smem + (size_t)(c == 0 ? nb - 1 : c - 1) * a.buf;
+                const float *before = sr_smem + (size_t)(c + 1 == nb ? 0 : c + 1) * a.buf;
+                const float *Wih = a.w_ih[l], *Whh = a.w_hh[l], *bih = a.b_ih[l], *bhh = a.b_hh[l];
+                const int items = ((H + 31) >> 5) * 2;
+                for (int it = wave; it < items; it += kDnWaves) {
+                    const int n0 = (it >> 1) * 32, st = it & 1;
+                    const int64_t s = base + st * 32 + i;
+                    const bool svalid = s < a.n;
+                    dn_f32x16 acc = dn_bias(bih, bhh, H, n0, lane);
+                    if (l == 0) {
+                        const float *xrow = a.rnn_in + ((size_t)(svalid ? s : a.n - 1) * a.T + t) * a.R;
+                        acc = dn_chain<true>(acc, Wih, a.R, H, n0, st, xrow, svalid, nullptr, lane);
+                    } else {
+                        acc = dn_chain<false>(acc, Wih, H, H, n0, st, nullptr, svalid, below, lane);
+                    }
+                    if (t > 0) acc = dn_chain<false>(acc, Whh, H, H, n0, st, nullptr, svalid, before, lane);
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const int u = n0 + dn_row(r, lane);
+                        if (u < H) hout[dn_lds(u, st * 32 + i)] = sp_tanh(acc[r]);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // the head (dqn.py:298-299) on h_{L-1}[T-1], which the last step left one buffer back; its layers alternate between that buffer and c
+        int zi = c == 0 ? nb - 1 : c - 1, zo = c;
+        for (int l = 0; l < nl; l++) {
+            const int dk = a.d[l], dn = a.d[l + 1];
+            const float *W = a.W[l], *bias = a.B[l];
+            const bool last = l == nl - 1;
+            const float slope = last ? 1.0f : a.A[l][0];
+            const float *zin = sr_smem + (size_t)zi * a.buf;
+            float *zout = sr_smem + (size_t)zo * a.buf;
+            const int items = ((dn + 31) >> 5) * 2;
+            for (int it = wave; it < items; it += kDnWaves) {
+                const int n0 = (it >> 1) * 32, st = it & 1;
+                const int64_t s = base + st * 32 + i;
+                const bool svalid = s < a.n;
+                const dn_f32x16 acc = dn_block<false>(W, bias, dk, dn, n0, st, nullptr, svalid, zin, lane);
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int u = n0 + dn_row(r, lane);
+                    if (u < dn) {
+                        if (last) {
+                            if (svalid) a.q[(size_t)s * dn + u] = acc[r];
+                        } else {
+                            zout[dn_lds(u, st * 32 + i)] = dn_prelu(acc[r], slope);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            const int sw = zi;
+            zi = zo;
+            zo = sw;
+        }
+    }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------------------
+size_t spatial_conv_lds(SpatialConvArgs &a) {
+    int s0 = a.C * a.size[0] * a.size[0], s1 = 0; // buffer 0: the input and what layers 1, 3 write; buffer 1: layers 0, 2; the last layer writes rnn_in
+    for (int l = 0; l + 1 < a.n_conv; l++) {
+        const int o = a.co[l] * a.size[l + 1] * a.size[l + 1];
+        int &s = (l & 1) ? s0 : s1;
+        s = o > s ? o : s;
+    }
+    a.slot0 = s0;
+    a.slot1 = s1;
+    const size_t per_image = (size_t)(s0 + s1) * sizeof(float);
+    size_t g = kSpLdsGroup / per_image;
+    g = g < 1 ? 1 : (g > (size_t)kSpGroup ? (size_t)kSpGroup : g);
+    a.G = (int)g;
+    return g * per_image;
+}
+
+size_t spatial_rnn_lds(SpatialRnnArgs &a) {
+    int w = a.H;
+    for (int l = 1; l + 1 < a.n_dims; l++) w = a.d[l] > w ? a.d[l] : w;
+    a.buf = w * kDnRows;
+    return (size_t)(a.L + 1) * a.buf * sizeof(float);
+}
+
+template <int CB, int K>
+static hipError_t sp_conv_launch(const SpatialConvArgs &a, size_t lds, hipStream_t st) {
+    if (lds > kSpLdsGroup) { // (one image alone is larger than the grouping target)
+        static LdsOptIn opted;
+        if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_spatial_conv<CB, K>), (int)kSpLdsBudget, opted)) return e;
+    }
+    const int64_t groups = (a.n * a.T + a.G - 1) / a.G;
+    hipLaunchKernelGGL((k_spatial_conv<CB, K>), dim3((unsigned)(groups < kSpConvGrid ? groups : kSpConvGrid)), dim3(kSpThreads), lds, st, a);
+    return hipGetLastError();
+}
+template <int K>
+static hipError_t sp_conv_launch_k(const SpatialConvArgs &a, size_t lds, hipStream_t st) {
+    int widest = 0;
+    for (int l = 0; l < a.n_conv; l++) widest = a.co[l] > widest ? a.co[l] : widest;
+    if (widest <= 4) return sp_conv_launch<4, K>(a, lds, st);
+    if (widest <= 8) return sp_conv_launch<8, K>(a, lds, st);
+    if (widest <= 16) return sp_conv_launch<16, K>(a, lds, st);
+    return sp_conv_launch<32, K>(a, lds, st);
+}
+
+hipError_t spatial_conv_launch(SpatialConvArgs a, hipStream_t st) {
+    const size_t lds = spatial_conv_lds(a);
+    switch (a.k) {
+    case 1: return sp_conv_launch_k<1>(a, lds, st);
+    case 3: return sp_conv_launch_k<3>(a, lds, st);
+    default: return sp_conv_launch_k<5>(a, lds, st);
+    }
+}
+
+hipError_t spatial_rnn_launch(SpatialRnnArgs a, hipStream_t st) {
+    const size_t lds = spatial_rnn_lds(a);
+    if (lds > kDnLdsNoOptIn) {
+        static LdsOptIn opted;
+        if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_spatial_rnn), (int)kSpLdsBudget, opted)) return e;
+    }
+    const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
+    hipLaunchKernelGGL(k_spatial_rnn, dim3((unsigned)(tiles < kDnMaxGrid ? tiles : kDnMaxGrid)), dim3(kDnThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+} // namespace susnet

@@ -21,6 +21,7 @@
 #include "susnet_family.h"
 #include "susnet_qnet.h"
 #include "susnet_dense.h"
+#include "susnet_spatial.h"
 #include "susnet_window.h"
 #include "susnet_host.h"
 
@@ -1012,6 +1013,126 @@ extern "C" int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void
     a.n = io->n;
     a.q = io->q_out;
     HIP_TRY(qnet_dense_launch(a, static_cast<hipStream_t>(stream)));
+    return SUSNET_OK;
+}
+
+// susnet_spatial_forward: SpatialDQN.forward in eval mode (the kernels: inst_qnet_spatial.hip).  Everything is checked here, before the first
+// launch; the handle gives the error conventions only.
+extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *io, void *stream) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_forward: null env / io");
+    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_spatial_forward: " + what); };
+    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    const auto S = [](long long v) { return std::to_string(v); };
+    const auto range = [&](const std::string &field, long long v, long long lo, long long hi) {
+        return field + " = " + S(v) + " (served: " + S(lo) + " .. " + S(hi) + ")";
+    };
+    if (io->T < 1 || io->T > SUSNET_SPATIAL_MAX_T) return bad(range("T", io->T, 1, SUSNET_SPATIAL_MAX_T));
+    if (io->N < 1 || io->N > SUSNET_SPATIAL_MAX_N) return bad(range("N", io->N, 1, SUSNET_SPATIAL_MAX_N));
+    if (io->C < 1 || io->C > SUSNET_SPATIAL_MAX_C) return bad(range("C", io->C, 1, SUSNET_SPATIAL_MAX_C));
+    if (io->n_conv < 1 || io->n_conv > kSpMaxConv) return bad(range("n_conv", io->n_conv, 1, kSpMaxConv));
+    if (io->k != 1 && io->k != 3 && io->k != 5) return bad("k = " + S(io->k) + " (served: one square kernel size of 1, 3 or 5)");
+    SpatialConvArgs ca{};
+    ca.size[0] = io->N;
+    for (int l = 0; l < io->n_conv; l++) {
+        const std::string at = "[" + S(l) + "]";
+        if (io->conv_out[l] < 1 || io->conv_out[l] > 32) return bad(range("conv_out" + at, io->conv_out[l], 1, 32));
+        if (io->conv_stride[l] < 1 || io->conv_stride[l] > 4) return bad(range("conv_stride" + at, io->conv_stride[l], 1, 4));
+        if (io->conv_padding[l] < 0 || io->conv_padding[l] > 8) return bad(range("conv_padding" + at, io->conv_padding[l], 0, 8));
+        if (io->conv_dilation[l] < 1 || io->conv_dilation[l] > 4) return bad(range("conv_dilation" + at, io->conv_dilation[l], 1, 4));
+        const int span = ca.size[l] + 2 * io->conv_padding[l] - io->conv_dilation[l] * (io->k - 1) - 1;
+        if (span < 0) return bad("conv layer " + S(l) + ": output size < 1 (input " + S(ca.size[l]) + ", k " + S(io->k) + ", conv_padding" + at + " " +
+                                 S(io->conv_padding[l]) + ", conv_dilation" + at + " " + S(io->conv_dilation[l]) + ")");
+        ca.size[l + 1] = span / io->conv_stride[l] + 1;
+        if (!io->conv_weight[l] || misaligned(io->conv_weight[l])) return bad("conv_weight" + at + " is NULL or not 4-byte aligned");
+        if (!io->conv_bias[l] || misaligned(io->conv_bias[l])) return bad("conv_bias" + at + " is NULL or not 4-byte aligned");
+        ca.co[l] = io->conv_out[l];
+        ca.stride[l] = io->conv_stride[l];
+        ca.pad[l] = io->conv_padding[l];
+        ca.dil[l] = io->conv_dilation[l];
+        ca.W[l] = io->conv_weight[l];
+        ca.B[l] = io->conv_bias[l];
+    }
+    if (io->Fn < 0) return bad("Fn = " + S(io->Fn) + " (at least 0)");
+    const long long out_px = (long long)ca.size[io->n_conv] * ca.size[io->n_conv];
+    const long long R = (long long)io->conv_out[io->n_conv - 1] * out_px + io->Fn;
+    if (R > SUSNET_SPATIAL_MAX_R)
+        return bad("R = conv_out * H_out^2 + Fn = " + S(R) + " (the RNN's input width: at most SUSNET_SPATIAL_MAX_R = " + S(SUSNET_SPATIAL_MAX_R) + ")");
+    if (io->rnn_layers < 1 || io->rnn_layers > kSpMaxRnn) return bad(range("rnn_layers", io->rnn_layers, 1, kSpMaxRnn));
+    if (io->rnn_hidden < 1 || io->rnn_hidden > kDnMaxHidden) return bad(range("rnn_hidden", io->rnn_hidden, 1, kDnMaxHidden));
+    if (io->n_dims < 2 || io->n_dims > 8) return bad("n_dims = " + S(io->n_dims) + " (served: 2 .. 8, i.e. a head of 1 .. 7 Linear layers)");
+    const int nl = io->n_dims - 1;
+    if (io->dims[0] != io->rnn_hidden) return bad("dims[0] = " + S(io->dims[0]) + " (the head reads the hidden state: rnn_hidden = " + S(io->rnn_hidden) + ")");
+    for (int l = 1; l < nl; l++)
+        if (io->dims[l] < 1 || io->dims[l] > kDnMaxHidden) return bad("dims[" + S(l) + "] = " + S(io->dims[l]) + " (hidden widths: 1 .. " + S(kDnMaxHidden) + ")");
+    if (io->dims[nl] < 1 || io->dims[nl] > kDnMaxOut) return bad("dims[" + S(nl) + "] = " + S(io->dims[nl]) + " (n_out: 1 .. " + S(kDnMaxOut) + ")");
+    if (io->n < 1) return bad("n = " + S(io->n) + " (at least one row)");
+    if (io->n > (INT64_MAX >> 20)) return bad("n = " + S(io->n) + " (the workspace's byte count overflows)");
+    if (io->agents < 1) return bad("agents = " + S(io->agents) + " (at least one agent per env)");
+    for (int d = 0; d < 3; d++) {
+        if (io->spatial_stride[d] < 0) return bad("spatial_stride[" + S(d) + "] = " + S(io->spatial_stride[d]) + " (at least 0)");
+        if (io->non_spatial_stride[d] < 0) return bad("non_spatial_stride[" + S(d) + "] = " + S(io->non_spatial_stride[d]) + " (at least 0)");
+    }
+    for (int l = 0; l < io->rnn_layers; l++) {
+        const std::string at = "[" + S(l) + "]";
+        if (!io->w_ih[l] || misaligned(io->w_ih[l])) return bad("w_ih" + at + " is NULL or not 4-byte aligned");
+        if (!io->w_hh[l] || misaligned(io->w_hh[l])) return bad("w_hh" + at + " is NULL or not 4-byte aligned");
+        if (!io->b_ih[l] || misaligned(io->b_ih[l])) return bad("b_ih" + at + " is NULL or not 4-byte aligned");
+        if (!io->b_hh[l] || misaligned(io->b_hh[l])) return bad("b_hh" + at + " is NULL or not 4-byte aligned");
+    }
+    for (int l = 0; l < nl; l++) {
+        if (!io->weight[l] || misaligned(io->weight[l])) return bad("weight[" + S(l) + "] is NULL or not 4-byte aligned");
+        if (!io->bias[l] || misaligned(io->bias[l])) return bad("bias[" + S(l) + "] is NULL or not 4-byte aligned");
+        if (l < nl - 1 && (!io->slope[l] || misaligned(io->slope[l]))) return bad("slope[" + S(l) + "] is NULL or not 4-byte aligned");
+    }
+    if (!io->spatial || misaligned(io->spatial)) return bad("spatial is NULL or not 4-byte aligned");
+    if (!io->non_spatial || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
+    if (!io->rnn_in || misaligned(io->rnn_in)) return bad("rnn_in is NULL or not 4-byte aligned");
+    if (!io->q_out || misaligned(io->q_out)) return bad("q_out is NULL or not 4-byte aligned");
+    ca.T = io->T;
+    ca.C = io->C;
+    ca.n_conv = io->n_conv;
+    ca.k = io->k;
+    ca.Fn = io->Fn;
+    ca.agents = io->agents;
+    ca.R = (int32_t)R;
+    ca.spatial = io->spatial;
+    ca.non_spatial = io->non_spatial;
+    for (int d = 0; d < 3; d++) {
+        ca.sp_stride[d] = io->spatial_stride[d];
+        ca.ns_stride[d] = io->non_spatial_stride[d];
+    }
+    ca.n = io->n;
+    ca.rnn_in = io->rnn_in;
+    SpatialRnnArgs ra{};
+    ra.T = io->T;
+    ra.R = (int32_t)R;
+    ra.L = io->rnn_layers;
+    ra.H = io->rnn_hidden;
+    for (int l = 0; l < io->rnn_layers; l++) {
+        ra.w_ih[l] = io->w_ih[l];
+        ra.w_hh[l] = io->w_hh[l];
+        ra.b_ih[l] = io->b_ih[l];
+        ra.b_hh[l] = io->b_hh[l];
+    }
+    ra.n_dims = io->n_dims;
+    for (int l = 0; l <= nl; l++) ra.d[l] = io->dims[l];
+    for (int l = 0; l < nl; l++) {
+        ra.W[l] = io->weight[l];
+        ra.B[l] = io->bias[l];
+        if (l < nl - 1) ra.A[l] = io->slope[l];
+    }
+    ra.rnn_in = io->rnn_in;
+    ra.n = io->n;
+    ra.q = io->q_out;
+    const size_t conv_lds = spatial_conv_lds(ca), rnn_lds = spatial_rnn_lds(ra);
+    if (conv_lds > kSpLdsBudget)
+        return bad("LDS: one image's activation buffers take " + S((long long)conv_lds) + " bytes of a workgroup's " + S((long long)kSpLdsBudget) +
+                   " (C, N, conv_out, conv_padding)");
+    if (rnn_lds > kSpLdsBudget)
+        return bad("LDS: (rnn_layers + 1) x 64 rows x max(rnn_hidden, head widths) floats = " + S((long long)rnn_lds) + " bytes of a workgroup's " +
+                   S((long long)kSpLdsBudget));
+    HIP_TRY(spatial_conv_launch(ca, static_cast<hipStream_t>(stream)));
+    HIP_TRY(spatial_rnn_launch(ra, static_cast<hipStream_t>(stream)));
     return SUSNET_OK;
 }
 

@@ -8,7 +8,7 @@ one kernel (``susnet_qnet_policy_step``: network on the f32-input MFMA, argmax, 
 (``susnet_qnet_forward`` + ``susnet_policy_step``) when the crew has a network too.  A reference ``MLP`` on any OTHER game, component
 set or layer stack can run through the dense kernel (``PolicyRollout(..., dense=True)``: ``DenseQNet`` -> ``susnet_mlp_forward`` on
 ``env.obs``, weights read in place) and hand its Q rows to ``susnet_policy_step``: that is what ``collect`` / ``train`` / ``evaluate`` use
-on those games.  By default, and for everything else (``SpatialDQN``, stacks wider than the dense kernel serves), the network runs
+on those games.  By default, and for everything else (stacks wider than the dense kernel serves), the network runs
 through stock PyTorch-ROCm -- which is the faster of the two at large batches -- and hands its Q rows to ``susnet_policy_step`` /
 ``susnet_policy_actions``.  ``PolicyRollout(..., dense=True, sequence_length=T)`` acts on the reference's WINDOW of the last T states
 (train.py:318-322, 388-389, 441-445; ``run_experiment``'s default is T = 2): the policy keeps the window as feature rows ``[B, T * F]``,
@@ -29,7 +29,9 @@ through stock PyTorch-ROCm -- which is the faster of the two at large batches --
   (train.py:316-389, visualize.py:502-585): a ``[B, T, S]`` window of flattened states lives on the device, every
   tick it goes through ``susnet_featurize`` (Perspective / Global / Flat featurizer), each agent's view feeds the
   imposter or the crew network by the env's role mask, argmax (optionally epsilon-greedy, train.py:355-381), step,
-  window roll (np.roll, train.py:388-389) or refill with the fresh first state where an episode ended.
+  window roll (np.roll, train.py:388-389) or refill with the fresh first state where an episode ended.  With ``kernels=True`` a
+  served ``SpatialDQN`` runs through ``SpatialQNet`` -> ``susnet_spatial_forward`` (convolutions on the vector ALU, recurrence and head on
+  the f32-input MFMA), one call per team per tick for all ``B * A`` rows.
 """
 from __future__ import annotations
 
@@ -301,6 +303,165 @@ class DenseQNet:
         io.rows, io.n, io.q_out = rows.data_ptr(), n, out.data_ptr()
         with env._on_device():
             L.check(env.lib.susnet_mlp_forward(env._h, C.byref(io), env._stream()))
+        return out
+
+
+def _spatial_stack(model):
+    """What ``susnet_spatial_forward`` needs to know of a ``SpatialDQN`` -- ``dict(convs, k, rnn, head linears, head activations)`` -- or
+    None if the module is something else or has a part the kernels do not compute."""
+    if not isinstance(model, SpatialDQN):
+        return None
+    layers = list(model.cnn.model)
+    convs, relus = layers[0::2], layers[1::2]
+    if not convs or len(relus) != len(convs) or not all(isinstance(m, nn.Conv2d) and m.bias is not None for m in convs) or \
+            not all(isinstance(m, nn.ReLU) for m in relus):
+        return None
+    same = lambda v: len(set(v)) == 1
+    for m in convs:
+        if not (same(m.kernel_size) and same(m.stride) and same(m.dilation)) or isinstance(m.padding, str) or not same(m.padding) or \
+                m.groups != 1 or m.padding_mode != "zeros" or m.kernel_size != convs[0].kernel_size:
+            return None
+    if any(a.out_channels != b.in_channels for a, b in zip(convs[:-1], convs[1:])):
+        return None
+    rnn = model.rnn.model
+    if not isinstance(rnn, nn.RNN) or rnn.mode != "RNN_TANH" or rnn.bidirectional or not rnn.bias or not rnn.batch_first or \
+            getattr(rnn, "proj_size", 0) != 0:
+        return None
+    head = list(model.prediction_head)
+    linears, acts = head[0::2], head[1::2]
+    if not linears or len(acts) != len(linears) - 1 or \
+            not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
+            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or \
+            any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:])) or linears[0].in_features != rnn.hidden_size:
+        return None
+    return dict(convs=convs, k=convs[0].kernel_size[0], rnn=rnn, linears=linears, acts=acts)
+
+
+class SpatialQNet:
+    """A reference ``SpatialDQN`` served by ``susnet_spatial_forward``: the module's EVAL-mode forward (dqn.py:205-301) as two HIP kernels on
+    the featurizers' ``(spatial, non_spatial)`` tensors where they lie.  ``SpatialQNet(env, model)`` is None for anything the kernels do not
+    serve -- another module, a non-square kernel / stride / padding / dilation, kernel sizes other than 1, 3, 5, an RNN that is not a
+    unidirectional tanh ``nn.RNN`` with biases, a per-channel PReLU, a bound of ``include/susnet.h`` exceeded (callers then run the module).
+
+    Like ``DenseQNet`` nothing is packed or cached: every ``forward`` takes the parameters' ``data_ptr()``s afresh, so ``optimizer.step`` and
+    ``load_state_dict`` are followed without a refresh.  The RNN-input workspace ``[n, T, R]`` and the default output buffer are owned and
+    re-made when the shape changes."""
+
+    def __new__(cls, env, model):
+        from . import _lib as L
+
+        stack = _spatial_stack(model)
+        if stack is None:
+            return None
+        convs, k, rnn, linears = stack["convs"], stack["k"], stack["rnn"], stack["linears"]
+        cfg = model.config
+        N, C, Fn = int(cfg["input_image_size"]), convs[0].in_channels, int(cfg["non_spatial_input_size"])
+        if k not in (1, 3, 5) or not 1 <= len(convs) <= L.SPATIAL_MAX_CONV or not 1 <= N <= L.SPATIAL_MAX_N or not 1 <= C <= L.SPATIAL_MAX_C or Fn < 0:
+            return None
+        size = N
+        for m in convs:
+            if not (1 <= m.out_channels <= 32 and 1 <= m.stride[0] <= 4 and 0 <= m.padding[0] <= 8 and 1 <= m.dilation[0] <= 4):
+                return None
+            span = size + 2 * m.padding[0] - m.dilation[0] * (k - 1) - 1
+            if span < 0:
+                return None
+            size = span // m.stride[0] + 1
+        R = convs[-1].out_channels * size * size + Fn
+        H, layers = rnn.hidden_size, rnn.num_layers
+        dims = [H] + [m.out_features for m in linears]
+        if R != rnn.input_size or R > L.SPATIAL_MAX_R or not 1 <= layers <= L.SPATIAL_MAX_RNN_LAYERS or not 1 <= H <= L.MLP_MAX_HIDDEN or \
+                len(linears) > 7 or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or not 1 <= dims[-1] <= L.MLP_MAX_OUT:
+            return None
+        slot0, slot1, s = C * N * N, 0, N  # the convolution kernel's two LDS buffers per image, and the recurrence's rotating hidden buffers
+        for l, m in enumerate(convs[:-1]):
+            s = (s + 2 * m.padding[0] - m.dilation[0] * (k - 1) - 1) // m.stride[0] + 1
+            if l & 1:
+                slot0 = max(slot0, m.out_channels * s * s)
+            else:
+                slot1 = max(slot1, m.out_channels * s * s)
+        if 4 * (slot0 + slot1) > L.SPATIAL_LDS_BYTES or 4 * (layers + 1) * L.MLP_ROW_TILE * max(dims[:-1]) > L.SPATIAL_LDS_BYTES:
+            return None
+        self = super().__new__(cls)
+        self.env, self.model = env, model
+        self.N, self.C, self.Fn, self.R, self.k, self.dims = N, C, Fn, R, k, dims
+        self._convs, self._rnn, self._linears, self._acts = convs, rnn, linears, stack["acts"]
+        self._q = self._rnn_in = None
+        return self
+
+    def _ptr(self, p, device):
+        if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError(f"SpatialQNet: the model's parameters must be contiguous float32 tensors on {device} (got {p.dtype} on {p.device})")
+        return p.data_ptr()
+
+    @staticmethod
+    def _strides(x, inner: int, agents: int, what: str):
+        """(env, agent, timestep) strides in floats of ``x``: ``[B, T, A, *inner]`` (a view per agent) or ``[B, T, *inner]`` (one for all)."""
+        per_agent = x.dim() == inner + 3
+        assert x.dim() in (inner + 2, inner + 3) and x.dtype == torch.float32, f"SpatialQNet: {what} is float32 [B, T, (A,) ...], got {tuple(x.shape)} {x.dtype}"
+        tail = x.shape[-inner:]
+        want, expect = 1, []
+        for d in reversed(tail):
+            expect.insert(0, want)
+            want *= d
+        assert all(d == 1 or s == e for d, s, e in zip(tail, x.stride()[-inner:], expect)), f"SpatialQNet: the last {inner} dimensions of {what} must be contiguous"
+        if per_agent:
+            assert x.shape[2] == agents, f"SpatialQNet: {what} has {x.shape[2]} agent views, agents = {agents}"
+            return x.stride(0), x.stride(2), x.stride(1)
+        return x.stride(0), 0, x.stride(1)
+
+    @torch.no_grad()
+    def forward(self, spatial: torch.Tensor, non_spatial: torch.Tensor, agents: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Q rows ``[B * agents, n_actions]`` (row ``b * agents + i`` = env b, agent i) of the featurizers' tensors as they are:
+        ``spatial`` ``[B, T, A, C, N, N]`` (PerspectiveFeaturizer) or ``[B, T, C, N, N]`` (GlobalFeaturizer's shared planes: every agent
+        reads the same image), ``non_spatial`` ``[B, T, A, Fn]`` or ``[B, T, Fn]``.  ``out``: where they go (default: a buffer this object
+        keeps: a result is valid until the next call).  Two launches, asynchronous."""
+        import ctypes as C
+
+        from . import _lib as L
+
+        env, model, rnn = self.env, self.model, self._rnn
+        if model.training and rnn.dropout > 0 and rnn.num_layers > 1:
+            raise RuntimeError("SpatialQNet: the model is in training mode with rnn_dropout > 0 between its RNN layers; the kernels compute the "
+                               "eval-mode forward (no dropout): call model.eval(), or run the torch module")
+        dev = env.device
+        assert spatial.device == dev and non_spatial.device == dev, f"SpatialQNet: inputs on {dev}"
+        agents = int(agents)
+        sp = self._strides(spatial, 3, agents, "spatial")
+        ns = self._strides(non_spatial, 1, agents, "non_spatial")
+        B, T = spatial.shape[:2]
+        assert tuple(spatial.shape[-3:]) == (self.C, self.N, self.N) and non_spatial.shape[-1] == self.Fn and tuple(non_spatial.shape[:2]) == (B, T), (
+            f"SpatialQNet: spatial [.., {self.C}, {self.N}, {self.N}] and non_spatial [.., {self.Fn}] with the same [B, T], got "
+            f"{tuple(spatial.shape)} and {tuple(non_spatial.shape)}")
+        n, n_out = B * agents, self.dims[-1]
+        if out is None:
+            out = self._q
+            if out is None or out.shape[0] != n:
+                out = self._q = torch.empty(n, n_out, dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and tuple(out.shape) == (n, n_out) and out.is_contiguous() and out.device == dev
+        if self._rnn_in is None or tuple(self._rnn_in.shape) != (n, T, self.R):
+            self._rnn_in = torch.empty(n, T, self.R, dtype=torch.float32, device=dev)
+        io = L.SpatialIO()
+        io.T, io.N, io.C, io.n_conv, io.k, io.Fn = T, self.N, self.C, len(self._convs), self.k, self.Fn
+        for l, m in enumerate(self._convs):
+            io.conv_out[l], io.conv_stride[l], io.conv_padding[l], io.conv_dilation[l] = m.out_channels, m.stride[0], m.padding[0], m.dilation[0]
+            io.conv_weight[l], io.conv_bias[l] = self._ptr(m.weight, dev), self._ptr(m.bias, dev)
+        io.rnn_layers, io.rnn_hidden = rnn.num_layers, rnn.hidden_size
+        for l in range(rnn.num_layers):
+            for name, field in (("weight_ih", io.w_ih), ("weight_hh", io.w_hh), ("bias_ih", io.b_ih), ("bias_hh", io.b_hh)):
+                field[l] = self._ptr(getattr(rnn, f"{name}_l{l}"), dev)
+        io.n_dims = len(self.dims)
+        for i, d in enumerate(self.dims):
+            io.dims[i] = d
+        for l, m in enumerate(self._linears):
+            io.weight[l], io.bias[l] = self._ptr(m.weight, dev), self._ptr(m.bias, dev)
+        for l, m in enumerate(self._acts):
+            io.slope[l] = self._ptr(m.weight, dev)
+        io.spatial, io.non_spatial = spatial.data_ptr(), non_spatial.data_ptr()
+        for d in range(3):
+            io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
+        io.agents, io.n, io.rnn_in, io.q_out = agents, n, self._rnn_in.data_ptr(), out.data_ptr()
+        with env._on_device():
+            L.check(env.lib.susnet_spatial_forward(env._h, C.byref(io), env._stream()))
         return out
 
 
@@ -619,16 +780,51 @@ class WindowedPolicyRollout:
     """
 
     def __init__(self, env, featurizer, imposter_model: nn.Module, crew_model: nn.Module, sequence_length: int = 2,
-                 epsilon: float = 0.0, mask_dead: bool = True, seed: int = 0):
+                 epsilon: float = 0.0, mask_dead: bool = True, seed: int = 0, kernels: bool = False):
         assert env.obs_config.mode == "raw" and env.obs_config.dtype == torch.uint8 and env.auto_reset, (
             "construct the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
         self.env, self.featurizer = env, featurizer
         self.imposter_model, self.crew_model = imposter_model, crew_model
         self.T, self.epsilon, self.mask_dead = int(sequence_length), float(epsilon), mask_dead
+        # kernels=True: a team whose model SpatialQNet serves gets its Q rows for all B * A (env, agent) rows from ONE susnet_spatial_forward
+        # per tick, on the featurizer's buffers in place; a model that is not served keeps the torch modules below, per team.  Off by default
+        self.spatial_imposter = self._spatial(imposter_model, env.n_imposter_actions) if kernels else None
+        self.spatial_crew = self._spatial(crew_model, env.n_crew_actions) if kernels else None
         self._gen = torch.Generator(device=env.device)
         self._gen.manual_seed(seed)
         self.window = None
         self._actions = torch.zeros(env.batch, env.n_agents, dtype=torch.int64, device=env.device)
+
+    def _spatial(self, model, n_actions):
+        from . import _lib as L
+        from .features import GlobalFeaturizer, PerspectiveFeaturizer
+
+        net = SpatialQNet(self.env, model)
+        if net is None or not isinstance(self.featurizer, (GlobalFeaturizer, PerspectiveFeaturizer)) or self.T > L.SPATIAL_MAX_T:
+            return None
+        env, A = self.env, self.env.n_agents
+        # the featurizer's own shapes: planes [.., C, N, N]; non-spatial columns per agent view (the Global featurizer appends onehot(agent))
+        _, planes, non_spatial = env._make_obs(self.featurizer.config, 1, rows=1)
+        Fn = (non_spatial.shape[-1] if non_spatial is not None else 0) + (A if isinstance(self.featurizer, GlobalFeaturizer) else 0)
+        if non_spatial is None:  # (a featurizer without a non-spatial block: forward() takes a real non_spatial tensor)
+            return None
+        if (net.C, net.N, net.Fn, net.dims[-1]) != (planes.shape[-3], planes.shape[-1], Fn, n_actions):
+            return None
+        return net
+
+    def kernel_inputs(self):
+        """``(spatial, non_spatial)`` of the fitted featurizer as ``SpatialQNet.forward`` takes them: the Perspective featurizer's buffers in
+        place; the Global featurizer's shared planes, and its non-spatial row with every agent's one-hot appended
+        (``GlobalFeaturizer.generate_featurized_states``, model_ready.py:291-306) as ``[B, T, A, Fn]``."""
+        from .features import GlobalFeaturizer
+
+        f = self.featurizer
+        if not isinstance(f, GlobalFeaturizer):
+            return f.spatial, f.non_spatial
+        A = self.env.n_agents
+        B, T = f.non_spatial.shape[:2]
+        eye = torch.eye(A, dtype=torch.float32, device=f.non_spatial.device)
+        return f.spatial, torch.cat([f.non_spatial.unsqueeze(2).expand(B, T, A, -1), eye.expand(B, T, A, A)], dim=3)
 
     def reset(self):
         self.env.reset()
@@ -644,10 +840,24 @@ class WindowedPolicyRollout:
             env.refresh_roles()
         self.featurizer.fit(self.window)
         imp_mask = env.imposter_mask  # [B, A]
-        for i, (spatial, non_spatial) in enumerate(self.featurizer.generate_featurized_states()):
-            q_imp = self.imposter_model(spatial, non_spatial).argmax(dim=1)
-            q_crew = self.crew_model(spatial, non_spatial).argmax(dim=1)
-            self._actions[:, i] = torch.where(imp_mask[:, i], q_imp, q_crew)
+        if self.spatial_imposter is None and self.spatial_crew is None:
+            for i, (spatial, non_spatial) in enumerate(self.featurizer.generate_featurized_states()):
+                q_imp = self.imposter_model(spatial, non_spatial).argmax(dim=1)
+                q_crew = self.crew_model(spatial, non_spatial).argmax(dim=1)
+                self._actions[:, i] = torch.where(imp_mask[:, i], q_imp, q_crew)
+        else:
+            B, A = env.batch, env.n_agents
+            views = None
+            if self.spatial_imposter is None or self.spatial_crew is None:
+                views = self.featurizer.generate_featurized_states()
+            spatial, non_spatial = self.kernel_inputs()
+            greedy = []
+            for net, model in ((self.spatial_imposter, self.imposter_model), (self.spatial_crew, self.crew_model)):
+                if net is not None:
+                    greedy.append(net.forward(spatial, non_spatial, A).argmax(dim=1).view(B, A))
+                else:
+                    greedy.append(torch.stack([model(sp, ns).argmax(dim=1) for sp, ns in views], dim=1))
+            torch.where(imp_mask, greedy[0], greedy[1], out=self._actions)
         if self.epsilon > 0.0:
             explore = torch.rand(self._actions.shape, device=env.device, generator=self._gen) <= self.epsilon  # train.py:359,371
             self._actions.copy_(torch.where(explore, env.sample_actions().to(torch.int64), self._actions))
