@@ -476,7 +476,9 @@ int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream);
  *   Served: T in 1 .. 8, N in 1 .. 16, C in 1 .. 32; n_conv in 1 .. 4, conv_out[l] in 1 .. 32, k in {1, 3, 5}, conv_stride[l] in 1 .. 4,
  * conv_padding[l] in 0 .. 8, conv_dilation[l] in 1 .. 4, every layer's output size (size + 2 padding - dilation (k - 1) - 1) / stride + 1 at
  * least 1; Fn >= 0; R <= SUSNET_SPATIAL_MAX_R; rnn_layers in 1 .. 4, rnn_hidden in 1 .. 256; the head n_dims in 2 .. 8 with dims[0] ==
- * rnn_hidden, hidden widths 1 .. 256 and at most 32 outputs; n >= 1, agents >= 1, strides >= 0; every pointer non-NULL and 4-byte aligned;
+ * rnn_hidden, hidden widths 1 .. 256 and at most 32 outputs; n >= 1, agents >= 1, strides >= 0; every pointer non-NULL and 4-byte aligned
+ * (with Fn == 0 nothing is read through non_spatial: NULL is accepted there -- a [B][T][0] tensor has no storage -- a pointer that is given
+ * must still be 4-byte aligned, and non_spatial_stride is not looked at);
  * the LDS of a call within a workgroup's 160 KiB: one image's two activation buffers for the convolutions, and (rnn_layers + 1) x 64 rows x
  * max(rnn_hidden, the head's hidden widths) floats for the recurrence (so rnn_hidden 256 is served with one layer, 128 with up to four).
  * Anything else: SUSNET_E_INVALID, with a message that names the field, before anything is launched.

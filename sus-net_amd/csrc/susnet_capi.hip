@@ -1070,7 +1070,7 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     if (io->agents < 1) return bad("agents = " + S(io->agents) + " (at least one agent per env)");
     for (int d = 0; d < 3; d++) {
         if (io->spatial_stride[d] < 0) return bad("spatial_stride[" + S(d) + "] = " + S(io->spatial_stride[d]) + " (at least 0)");
-        if (io->non_spatial_stride[d] < 0) return bad("non_spatial_stride[" + S(d) + "] = " + S(io->non_spatial_stride[d]) + " (at least 0)");
+        if (io->Fn > 0 && io->non_spatial_stride[d] < 0) return bad("non_spatial_stride[" + S(d) + "] = " + S(io->non_spatial_stride[d]) + " (at least 0)");
     }
     for (int l = 0; l < io->rnn_layers; l++) {
         const std::string at = "[" + S(l) + "]";
@@ -1085,7 +1085,8 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
         if (l < nl - 1 && (!io->slope[l] || misaligned(io->slope[l]))) return bad("slope[" + S(l) + "] is NULL or not 4-byte aligned");
     }
     if (!io->spatial || misaligned(io->spatial)) return bad("spatial is NULL or not 4-byte aligned");
-    if (!io->non_spatial || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
+    // (Fn = 0: nothing is read through non_spatial, so NULL is accepted -- a [B][T][0] tensor has no storage; a pointer that is given is still checked)
+    if ((!io->non_spatial && io->Fn > 0) || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
     if (!io->rnn_in || misaligned(io->rnn_in)) return bad("rnn_in is NULL or not 4-byte aligned");
     if (!io->q_out || misaligned(io->q_out)) return bad("q_out is NULL or not 4-byte aligned");
     ca.T = io->T;
@@ -1099,7 +1100,7 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     ca.non_spatial = io->non_spatial;
     for (int d = 0; d < 3; d++) {
         ca.sp_stride[d] = io->spatial_stride[d];
-        ca.ns_stride[d] = io->non_spatial_stride[d];
+        ca.ns_stride[d] = io->Fn > 0 ? io->non_spatial_stride[d] : 0; // (Fn = 0: the strides are not looked at)
     }
     ca.n = io->n;
     ca.rnn_in = io->rnn_in;

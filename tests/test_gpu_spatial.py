@@ -1,8 +1,8 @@
 """The SpatialDQN forward kernels (susnet_spatial_forward) and their wiring on the MI355X: the convolution stage and the whole network exact
 against a float64 evaluation on integer-valued networks (tanh pinned to 0 / +-1 by pre-activations that are multiples of 32), close to the
 reference's stored outputs and to the torch module on the fixtures, following parameter updates without a refresh, and -- through
-WindowedPolicyRollout(kernels=True) -- acting as the same calls made by hand and as the torch modules wherever their Q gap decides."""
-import ctypes as C
+WindowedPolicyRollout(kernels=True) -- acting as the same calls made by hand and as the torch modules wherever their Q gap decides.  The integer-valued networks, their
+evaluation and the calls through the C ABI are tests/spatial_exact.py; test_gpu_spatial_limits.py goes on where this file stops."""
 import importlib
 import json
 import os
@@ -12,10 +12,10 @@ import pytest
 import torch
 from torch import nn
 
+from spatial_exact import DEV, make_net, run_exact, upload
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-CANARY = 12345.0
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -34,193 +34,6 @@ def handle(pkg):
 
 def tol(want):
     return 2e-5 * float(want.abs().max())  # the project's Q-network tolerance (test_gpu_mlp_dense.py)
-
-
-# ---- an integer-valued network and its float64 evaluation --------------------------------------------------------------------------------
-def conv64(x, W, b, stride, pad, dil):
-    """Conv2d + ReLU in float64 on x [M, Ci, H, H]; also the bound max(sum |w||x| + |b|) that makes float32 exact in any order."""
-    K = W.shape[-1]
-    H = x.shape[-1]
-    Ho = (H + 2 * pad - dil * (K - 1) - 1) // stride + 1
-    xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
-    out = np.zeros((x.shape[0], W.shape[0], Ho, Ho)) + b[None, :, None, None]
-    mag = np.zeros_like(out) + np.abs(b)[None, :, None, None]
-    for ky in range(K):
-        for kx in range(K):
-            patch = xp[:, :, ky * dil:ky * dil + stride * (Ho - 1) + 1:stride, kx * dil:kx * dil + stride * (Ho - 1) + 1:stride]
-            out += np.einsum("mchw,oc->mohw", patch, W[:, :, ky, kx])
-            mag += np.einsum("mchw,oc->mohw", np.abs(patch), np.abs(W[:, :, ky, kx]))
-    assert float(mag.max()) < 2.0 ** 24, float(mag.max())
-    return np.maximum(out, 0.0)
-
-
-def make_net(rng, N, C, k, convs, Fn, L, H, head, variant=None):
-    """convs: [(out channels, stride, padding, dilation)].  Convolution and head parameters from {-1, 0, 1}, RNN weights and summed biases
-    from {-32, 0, 32} (b_ih + b_hh: some as 16 + 16), slopes 0.5."""
-    net = dict(N=N, C=C, k=k, convs=convs, Fn=Fn, L=L, H=H, variant=variant)
-    ci, size = C, N
-    net["cw"], net["cb"] = [], []
-    for co, s, p, d in convs:
-        net["cw"].append(rng.choice([-1.0, 0.0, 1.0], size=(co, ci, k, k), p=[0.25, 0.5, 0.25]))
-        net["cb"].append(rng.choice([-1.0, 0.0, 1.0], size=co))
-        size = (size + 2 * p - d * (k - 1) - 1) // s + 1
-        ci = co
-    net["conv_cols"] = ci * size * size
-    R = net["R"] = net["conv_cols"] + Fn
-    net["w_ih"], net["w_hh"], net["b_ih"], net["b_hh"] = [], [], [], []
-    for l in range(L):
-        w_ih = rng.choice([-32.0, 0.0, 32.0], size=(H, R if l == 0 else H), p=[0.1, 0.8, 0.1])
-        w_hh = rng.choice([-32.0, 0.0, 32.0], size=(H, H), p=[0.15, 0.7, 0.15])
-        if variant == "no_recurrence":
-            w_hh[:] = 0.0
-        if variant == "carry" and l == 0:  # layer 0 reads the non-spatial columns only, and they are zero after t = 0: what the answer
-            w_ih[:, :net["conv_cols"]] = 0.0  # knows of the input it knows through the recurrence
-        b = rng.choice([-32.0, 0.0, 32.0], size=H)
-        split = rng.random(H) < 0.3
-        net["w_ih"].append(w_ih)
-        net["w_hh"].append(w_hh)
-        net["b_ih"].append(np.where(split, b / 2, b))
-        net["b_hh"].append(np.where(split, b / 2, 0.0))
-    dims = net["dims"] = [H] + list(head)
-    net["hw"] = [rng.choice([-1.0, 0.0, 1.0], size=(dims[l + 1], dims[l]), p=[0.3, 0.4, 0.3]) for l in range(len(dims) - 1)]
-    net["hb"] = [rng.choice([-1.0, 0.0, 1.0], size=dims[l + 1]) for l in range(len(dims) - 1)]
-    return net
-
-
-def evaluate64(net, images, ns):
-    """images [n, T, C, N, N], ns [n, T, Fn] (float64) -> (rnn_in [n, T, R], q [n, n_out]) as float32 arrays that hold the exact values."""
-    n, T = images.shape[:2]
-    x = images.reshape(n * T, *images.shape[2:])
-    for (co, s, p, d), W, b in zip(net["convs"], net["cw"], net["cb"]):
-        x = conv64(x, W, b, s, p, d)
-    rnn_in = np.concatenate([x.reshape(n, T, -1), ns], axis=2)
-    assert rnn_in.shape[2] == net["R"]
-    H, L = net["H"], net["L"]
-    h = [np.zeros((n, H)) for _ in range(L)]
-    for t in range(T):
-        below = rnn_in[:, t]
-        for l in range(L):
-            mag = np.abs(below) @ np.abs(net["w_ih"][l]).T + np.abs(h[l]) @ np.abs(net["w_hh"][l]).T + np.abs(net["b_ih"][l]) + np.abs(net["b_hh"][l])
-            assert float(mag.max()) < 2.0 ** 24
-            z = below @ net["w_ih"][l].T + h[l] @ net["w_hh"][l].T + net["b_ih"][l] + net["b_hh"][l]
-            assert np.array_equal(z, np.round(z / 32.0) * 32.0), "every pre-activation is a multiple of 32"
-            h[l] = np.tanh(z)
-            assert np.isin(h[l], (-1.0, 0.0, 1.0)).all()
-            below = h[l]
-    z = h[-1]
-    for l, (W, b) in enumerate(zip(net["hw"], net["hb"])):
-        assert float((np.abs(z) @ np.abs(W).T + np.abs(b)).max()) * 2.0 ** l < 2.0 ** 24
-        z = z @ W.T + b
-        if l < len(net["hw"]) - 1:
-            z = np.where(z > 0, z, 0.5 * z)
-    want_in, want_q = rnn_in.astype(np.float32), z.astype(np.float32)
-    assert np.array_equal(want_in.astype(np.float64), rnn_in) and np.array_equal(want_q.astype(np.float64), z)
-    return want_in, want_q
-
-
-def to_device_at_odd_offsets(arrays):
-    """Every array inside ONE float32 allocation at a 4-byte offset that is no multiple of 8 or 16 bytes more often than not."""
-    total = sum(a.size + 1 for a in arrays) + 1
-    flat = torch.full((total,), CANARY, dtype=torch.float32, device=DEV)
-    views, off = [], 1
-    for a in arrays:
-        v = flat[off:off + a.size].view(a.shape)
-        v.copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)))
-        views.append(v)
-        off += a.size + 1
-    return flat, views
-
-
-def padded(shape, pad):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * pad,), CANARY, dtype=torch.float32, device=DEV)
-    return buf, buf[pad:pad + n].view(*shape)
-
-
-def spatial_forward(pkg, env, net, dev, spatial, sp_strides, non_spatial, ns_strides, agents, n, T, rnn_in, q_out):
-    """susnet_spatial_forward by hand; ``dev``: the network's device tensors as make_net orders them."""
-    L = pkg._lib
-    io = L.SpatialIO()
-    io.T, io.N, io.C, io.n_conv, io.k, io.Fn = T, net["N"], net["C"], len(net["convs"]), net["k"], net["Fn"]
-    for l, (co, s, p, d) in enumerate(net["convs"]):
-        io.conv_out[l], io.conv_stride[l], io.conv_padding[l], io.conv_dilation[l] = co, s, p, d
-        io.conv_weight[l], io.conv_bias[l] = dev["cw"][l].data_ptr(), dev["cb"][l].data_ptr()
-    io.rnn_layers, io.rnn_hidden = net["L"], net["H"]
-    for l in range(net["L"]):
-        io.w_ih[l], io.w_hh[l], io.b_ih[l], io.b_hh[l] = (dev[k][l].data_ptr() for k in ("w_ih", "w_hh", "b_ih", "b_hh"))
-    io.n_dims = len(net["dims"])
-    for i, d in enumerate(net["dims"]):
-        io.dims[i] = d
-    for l in range(len(net["hw"])):
-        io.weight[l], io.bias[l] = dev["hw"][l].data_ptr(), dev["hb"][l].data_ptr()
-    for l in range(len(net["hw"]) - 1):
-        io.slope[l] = dev["slope"][l].data_ptr()
-    io.spatial, io.non_spatial = spatial.data_ptr(), non_spatial.data_ptr()
-    for d in range(3):
-        io.spatial_stride[d], io.non_spatial_stride[d] = sp_strides[d], ns_strides[d]
-    io.agents, io.n, io.rnn_in, io.q_out = agents, n, rnn_in.data_ptr(), q_out.data_ptr()
-    with torch.cuda.device(env.device):
-        L.check(env.lib.susnet_spatial_forward(env._h, C.byref(io), env._stream()))
-
-
-def upload(net):
-    keys = ("cw", "cb", "w_ih", "w_hh", "b_ih", "b_hh", "hw", "hb")
-    arrays = [a for k in keys for a in net[k]] + [np.full(1, 0.5)] * (len(net["hw"]) - 1)
-    flat, views = to_device_at_odd_offsets(arrays)
-    dev, at = {"flat": flat}, 0
-    for k in keys:
-        dev[k] = views[at:at + len(net[k])]
-        at += len(net[k])
-    dev["slope"] = views[at:]
-    return dev
-
-
-# agents per env for n rows: 3 where 3 divides n (33), else 5 (95, 320), and 1 for the single row -- there the shared pattern's agent
-# stride of 0 has nothing to share, so the stride-0 sharing is exercised at n = 33, 95 and 320 only
-def agents_of(n):
-    return next(a for a in (3, 5, 1) if n % a == 0)
-
-
-def run_exact(pkg, env, net, dev, n, T, pattern, rng):
-    """One call on `n` rows in one of the two stride patterns; rnn_in and q_out bit-equal to the float64 evaluation, canaries whole, inputs
-    unchanged."""
-    A = agents_of(n)
-    B = n // A
-    Cc, N, Fn = net["C"], net["N"], net["Fn"]
-    img = lambda *lead: rng.choice([0.0, 1.0, 2.0, 3.0], size=(*lead, Cc, N, N), p=[0.7, 0.2, 0.07, 0.03])
-    ns = rng.choice([0.0, 1.0, 2.0, 3.0], size=(B, T, A, Fn), p=[0.6, 0.3, 0.07, 0.03])
-    if net["variant"] == "carry":
-        ns[:, 1:] = 0.0
-    if pattern == "shared":  # the Global featurizer's planes [B][T][C][N][N], agent stride 0
-        x = img(B, T)
-        rows_x = np.repeat(x[:, None], A, axis=1).reshape(n, T, Cc, N, N)
-        sp_strides = (T * Cc * N * N, 0, Cc * N * N)
-        sp_shape = (B, T, Cc, N, N)
-    else:  # the Perspective featurizer's [B][T][A][C][N][N]
-        x = img(B, T, A)
-        rows_x = x.transpose(0, 2, 1, 3, 4, 5).reshape(n, T, Cc, N, N)
-        sp_strides = (T * A * Cc * N * N, Cc * N * N, A * Cc * N * N)
-        sp_shape = (B, T, A, Cc, N, N)
-    rows_ns = ns.transpose(0, 2, 1, 3).reshape(n, T, Fn)
-    want_in, want_q = evaluate64(net, rows_x, rows_ns)
-    sp_buf, sp = padded(sp_shape, 3)
-    sp.copy_(torch.from_numpy(x.astype(np.float32)))
-    ns_buf, nsd = padded((B, T, A, max(Fn, 1)), 5)
-    if Fn:
-        nsd.copy_(torch.from_numpy(ns.astype(np.float32)))
-    in_buf, rnn_in = padded((n, T, net["R"]), 7)
-    q_buf, q = padded((n, net["dims"][-1]), 5)
-    before = (sp_buf.clone(), ns_buf.clone(), dev["flat"].clone())
-    spatial_forward(pkg, env, net, dev, sp, sp_strides, nsd, (T * A * max(Fn, 1), max(Fn, 1), A * max(Fn, 1)), A, n, T, rnn_in, q)
-    torch.cuda.synchronize()
-    what = (net["convs"], net["H"], net["L"], n, T, pattern)
-    got_in, got_q = rnn_in.cpu().numpy(), q.cpu().numpy()
-    assert np.array_equal(got_in.view(np.int32), want_in.view(np.int32)), (what, "rnn_in", float(np.abs(got_in - want_in).max()))
-    assert np.array_equal(got_q.view(np.int32), want_q.view(np.int32)), (what, "q_out", float(np.abs(got_q - want_q).max()))
-    for buf, pad in ((in_buf, 7), (q_buf, 5)):
-        assert bool((buf[:pad] == CANARY).all()) and bool((buf[-pad:] == CANARY).all()), (what, "canary")
-    assert torch.equal(before[0], sp_buf) and torch.equal(before[1], ns_buf) and torch.equal(before[2], dev["flat"]), (what, "inputs changed")
-    return want_q
 
 
 # ---- 1. the convolution stage, exact -------------------------------------------------------------------------------------------------------

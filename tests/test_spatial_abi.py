@@ -147,6 +147,13 @@ def test_spatial_forward_refusals_name_the_field(pkg):
     for field in ("spatial", "non_spatial", "rnn_in", "q_out"):
         refused(field.encode(), **{field: None})
         refused(field.encode(), **{field: 4097})
+    # Fn = 0: nothing is read through non_spatial, so NULL passes (a [B][T][0] tensor has no storage) and the strides are not looked at --
+    # the call goes on to the NEXT check, which refuses the NULL workspace, so nothing is launched here; a misaligned pointer is still refused
+    refused(b"rnn_in is NULL", Fn=0, non_spatial=None, rnn_in=None, non_spatial_stride=[(0, -1), (1, -1), (2, -1)])
+    assert b"non_spatial" not in lib.susnet_last_error()
+    refused(b"rnn_in is NULL", Fn=0, rnn_in=None)
+    refused(b"non_spatial is NULL or not 4-byte aligned", Fn=0, non_spatial=4097)
+    refused(b"non_spatial is NULL or not 4-byte aligned", Fn=1, non_spatial=None)
     refused(b"LDS", rnn_hidden=256, dims=(0, 256), rnn_layers=2)  # 3 x 64 x 256 floats = 192 KiB
     # one image: 32 KiB in, 32 x 32 x 32 floats = 128 KiB out of layer 0, 32 x 48 x 48 floats out of layer 1
     refused(b"LDS", C=32, N=16, k=1, conv_padding=[(0, 8), (1, 8)], conv_out=[(0, 32), (1, 32)], conv_stride=(2, 4))
