@@ -1,9 +1,10 @@
 """Compile sus-net_amd/csrc/*.hip -> sus-net_amd/libsusnet_hip.so for gfx950 (in-tree).
 
 One object per translation unit (susnet_capi.hip = the handle and the acting side of the C ABI + their small kernels;
-susnet_capi_ring.hip / susnet_capi_train.hip / susnet_capi_episodes.hip = the replay ring, the DQN learners and the episode
-bookkeeping, each entry point with its kernels; inst_*.hip = one compiled-in configuration of the stepping kernels each, the
-Q-network, window and dense-learner kernels), compiled in parallel, then linked into ONE shared library."""
+susnet_capi_nets.hip = the network entry points, host code only; susnet_capi_ring.hip / susnet_capi_train.hip /
+susnet_capi_episodes.hip = the replay ring, the DQN learners and the episode bookkeeping, each entry point with its kernels;
+inst_*.hip = one compiled-in configuration of the stepping kernels each, the Q-network, window and dense-learner kernels), compiled
+in parallel, then linked into ONE shared library."""
 from __future__ import annotations
 
 import glob

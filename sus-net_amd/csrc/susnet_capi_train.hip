@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "susnet_qnet.h" // QNet, QRow1 / QRow3 / QRowC: the pack kernels write susnet_qnet_pack's image
+#include "susnet_dense.h" // kDnMaxHidden / kDnMaxOut: the forward's widths, which the dense learner's must equal
 #include "susnet_train.h"
 #include "susnet_mlp_train.h"
 #include "susnet_host.h"
@@ -235,7 +236,8 @@ struct MlpTrainPlan : TrWorkspace {
 };
 static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, MlpTrainPlan &pl) {
     if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_train_step: null env / io");
-    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
+    static_assert(kMtMaxHidden == kDnMaxHidden && kMtMaxOut == kDnMaxOut, "the dense learner trains what the dense forward serves"); // (one check_stack_dims)
+    const Refuse bad{env, "susnet_mlp_train_step"};
     if (env->c.n_imp != 1)
         return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
                    "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
@@ -249,15 +251,10 @@ static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, 
         const susnet_dqn_team &T = io->team[tm];
         if (!T.enabled) continue;
         const std::string who = "team[" + std::to_string(tm) + "].";
-        if (T.n_dims < 2 || T.n_dims > 8) return bad(who + "n_dims = " + std::to_string(T.n_dims) + " (served: 2 .. 8, i.e. 1 .. 7 Linear layers)");
+        if (int rc = check_stack_n_dims(bad, who, T.n_dims)) return rc;
+        if (int rc = check_feature_width(bad, who, T.dims[0])) return rc;
+        if (int rc = check_stack_dims(bad, who, T.n_dims, T.dims, kMtMaxHidden, kMtMaxOut)) return rc;
         const int nl = T.n_dims - 1;
-        if (T.dims[0] < 1 || T.dims[0] > SUSNET_MLP_MAX_F)
-            return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
-        for (int l = 1; l < nl; l++)
-            if (T.dims[l] < 1 || T.dims[l] > kMtMaxHidden)
-                return bad(who + "dims[" + std::to_string(l) + "] = " + std::to_string(T.dims[l]) + " (hidden widths: 1 .. " + std::to_string(kMtMaxHidden) + ")");
-        if (T.dims[nl] < 1 || T.dims[nl] > kMtMaxOut)
-            return bad(who + "dims[" + std::to_string(nl) + "] = " + std::to_string(T.dims[nl]) + " (n_out: 1 .. " + std::to_string(kMtMaxOut) + ")");
         if (F && T.dims[0] != F)
             return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " but team[0].dims[0] = " + std::to_string(F) + ": both teams read the same feature rows");
         F = T.dims[0];
@@ -294,8 +291,7 @@ extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const sus
 extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
     MlpTrainPlan pl;
     if (int rc = mlp_train_plan(env, io, pl)) return rc;
-    const auto bad = [&](const std::string &what) { return fail(env, SUSNET_E_INVALID, "susnet_mlp_train_step: " + what); };
-    const auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    const Refuse bad{env, "susnet_mlp_train_step"};
     if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
         return bad("workspace missing, smaller than susnet_mlp_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
                    " bytes) or not 256-byte aligned");

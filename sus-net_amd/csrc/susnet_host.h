@@ -76,8 +76,57 @@ inline hipError_t lds_opt_in(const void *kernel, int bytes, LdsOptIn &opted) {
     return hipSuccess;
 }
 
-// the Q-network entry points' own checks (susnet_capi.hip), which the fused learner shares: the compiled-in feature layout of a
-// component list on this handle (0 = none), and whether a layer stack fits QNet<ROW> (instantiated there for QRow1 / QRow3 / QRowC)
+// the Q-network entry points' own checks (susnet_capi_nets.hip), which the one-kernel tick and the fused learner share: the compiled-in
+// feature layout of a component list on this handle (0 = none), and whether a layer stack fits QNet<ROW> (instantiated there for QRow1 /
+// QRow3 / QRowC)
 int qnet_feat(const susnet_env *env, const int32_t *comp, int32_t ncomp);
 template <class ROW>
 bool qnet_dims_ok(const int32_t *dims, int32_t n_dims);
+
+// ---- a Linear / PReLU layer stack at an entry point (susnet_mlp_forward, susnet_spatial_forward's head, susnet_mlp_train_step): the ONE
+// statement of what is checked, in which order and words, and of how an io's stack becomes a kernel's arguments ----
+inline bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; } // (float / int32 arrays: 4-byte)
+// an entry point's refusal: SUSNET_E_INVALID, "<entry point>: <what>"
+struct Refuse {
+    const susnet_env *env;
+    const char *entry;
+    int operator()(const std::string &what) const { return fail(env, SUSNET_E_INVALID, std::string(entry) + ": " + what); }
+};
+// The dims of a stack are checked in three steps, in this order: n_dims, the caller's own rule for dims[0] (an `if` of its own, or
+// check_feature_width), then the hidden widths and n_out.  `prefix` names the struct the fields sit in ("team[0]."), `layers` what n_dims counts
+inline int check_stack_n_dims(const Refuse &bad, const std::string &prefix, int32_t n_dims, const char *layers = "1 .. 7 Linear layers") {
+    if (n_dims < 2 || n_dims > 8) return bad(prefix + "n_dims = " + std::to_string(n_dims) + " (served: 2 .. 8, i.e. " + layers + ")");
+    return SUSNET_OK;
+}
+inline int check_feature_width(const Refuse &bad, const std::string &prefix, int32_t F) { // (dims[0] of a stack that reads feature rows)
+    if (F < 1 || F > SUSNET_MLP_MAX_F)
+        return bad(prefix + "dims[0] = " + std::to_string(F) + " (F: 1 .. SUSNET_MLP_MAX_F = " + std::to_string(SUSNET_MLP_MAX_F) + ")");
+    return SUSNET_OK;
+}
+inline int check_stack_dims(const Refuse &bad, const std::string &prefix, int32_t n_dims, const int32_t *dims, int max_hidden, int max_out) {
+    const auto S = [](long long v) { return std::to_string(v); };
+    const int nl = n_dims - 1;
+    for (int l = 1; l < nl; l++)
+        if (dims[l] < 1 || dims[l] > max_hidden) return bad(prefix + "dims[" + S(l) + "] = " + S(dims[l]) + " (hidden widths: 1 .. " + S(max_hidden) + ")");
+    if (dims[nl] < 1 || dims[nl] > max_out) return bad(prefix + "dims[" + S(nl) + "] = " + S(dims[nl]) + " (n_out: 1 .. " + S(max_out) + ")");
+    return SUSNET_OK;
+}
+// weight[l] / bias[l] of the nl layers, slope[l] of the nl - 1 activations between them: non-NULL and 4-byte aligned, layer by layer
+inline int check_stack_ptrs(const Refuse &bad, const std::string &prefix, int nl, const float *const *weight, const float *const *bias,
+                            const float *const *slope) {
+    const auto at = [&](const char *field, int l) { return prefix + field + "[" + std::to_string(l) + "] is NULL or not 4-byte aligned"; };
+    for (int l = 0; l < nl; l++) { // (the text is made where a pointer is refused: a served call allocates nothing here)
+        if (!weight[l] || misaligned(weight[l])) return bad(at("weight", l));
+        if (!bias[l] || misaligned(bias[l])) return bad(at("bias", l));
+        if (l < nl - 1 && (!slope[l] || misaligned(slope[l]))) return bad(at("slope", l));
+    }
+    return SUSNET_OK;
+}
+// a checked io's stack (n_dims, dims, weight, bias, slope) into a kernel's argument struct (n_dims, d, W, B, A: DenseArgs, SpatialRnnArgs)
+template <class ARGS, class IO>
+inline void fill_stack(ARGS &a, const IO &io) {
+    a.n_dims = io.n_dims;
+    for (int l = 0; l < io.n_dims; l++) a.d[l] = io.dims[l];
+    for (int l = 0; l < io.n_dims - 1; l++) a.W[l] = io.weight[l], a.B[l] = io.bias[l];
+    for (int l = 0; l < io.n_dims - 2; l++) a.A[l] = io.slope[l];
+}

@@ -602,7 +602,7 @@ __global__ __launch_bounds__(256) void k_qnet_step(QStepArgs ka) {
 #undef SUSNET_KARG
 
 // ---- launchers: one translation unit per feature layout (inst_qnet_*.hip: these kernels are the library's largest), declared to the host
-// side (susnet_capi.hip) as extern templates
+// side (susnet_capi.hip, susnet_capi_nets.hip) as extern templates
 template <class ROW>
 hipError_t qnet_launch_k(const Consts &c, const State &s, const float *packed, float *q_out, int n_out, hipStream_t st) {
     using Q = QNet<ROW>;

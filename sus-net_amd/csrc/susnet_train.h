@@ -21,7 +21,7 @@
 //   k_train_adam     thread per parameter: sums the partials in workgroup order (bitwise reproducible), adds them to the step's gradient
 //                    accumulator, applies Adam on the torch-layout parameters; does nothing when the team's count is 0.
 //   per team and step, one launch:
-//   k_train_pack     the team's packed image (susnet_qnet_pack's layout, susnet_capi.hip) from the updated parameters, element for element
+//   k_train_pack     the team's packed image (susnet_qnet_pack's layout, susnet_capi_nets.hip) from the updated parameters, element for element
 //                    the host's arithmetic (tail rows summed in its order): bitwise what the host packer makes.
 //
 // A sweep (susnet_dqn_train_sweep; the notebooks' loops over run_experiment(**config), notebooks/experiment_1v1.ipynb and
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void k_train_sweep_adam(TrainTable tab, TrainN
     tr_adam(net.P, net.Pp, a.counts, agent, team, a.partial, G, a.gacc, a.prm, a.m1, a.m2, a.step, a.lr, a.beta1, a.beta2, a.eps, a.losses);
 }
 
-// ---- k_train_pack: the team's packed image from torch-layout parameters (susnet_capi.hip qnet_pack, element for element) ----
+// ---- k_train_pack: the team's packed image from torch-layout parameters (susnet_capi_nets.hip qnet_pack, element for element) ----
 template <class ROW>
 __device__ __forceinline__ void tr_pack(const TrainNet &net, const float *__restrict__ prm, float *__restrict__ out) {
     using Q = QNet<ROW>;

@@ -485,6 +485,31 @@ class BatchedFourRoomEnv:
                 o.crew_q_out = crew_q_out.data_ptr()
         return C.byref(o)
 
+    def _default_actions_out(self) -> torch.Tensor:
+        """The int64 ``[B, A]`` buffer the env keeps for the policy calls' actions when the caller names none."""
+        if getattr(self, "_policy_actions_buf", None) is None:
+            self._policy_actions_buf = torch.zeros(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
+        return self._policy_actions_buf
+
+    def _after_step(self) -> None:
+        """What follows every stepping call on a handle built with these flags: the host-side mirrors, the error word."""
+        if self.export_state:
+            self._export(full=False)
+        if self.check_errors:
+            self.poll_errors()
+
+    @staticmethod
+    def _qnet_args(net: "PackedQNet"):
+        """The five leading arguments by which the C ABI takes a packed network: components, their count, dims, their count, the image."""
+        return net.components, len(net.components), net.cdims, len(net.dims), net.packed.data_ptr()
+
+    def _qnet_policy_step_call(self, net: "PackedQNet", q_out: Optional[torch.Tensor], opts, io) -> None:
+        """``susnet_qnet_policy_step`` on a filled ``io``, inside ``_on_device()`` (``q_out``: where the Q rows it acted on go, or None)."""
+        if q_out is not None:
+            assert q_out.dtype == torch.float32 and tuple(q_out.shape) == (self.batch, net.dims[-1]) and q_out.is_contiguous()
+        L.check(self.lib.susnet_qnet_policy_step(self._h, *self._qnet_args(net), q_out.data_ptr() if q_out is not None else None, opts, C.byref(io),
+                                                 self._stream()))
+
     def policy_actions(self, q_imposter: torch.Tensor, q_crew: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                        epsilon: float = 0.0, mask_dead: bool = False) -> torch.Tensor:
         """Greedy actions of one tick (visualize.py:547-562): every imposter takes ``argmax(q_imposter[b])``, every crew member
@@ -496,9 +521,7 @@ class BatchedFourRoomEnv:
         if q_crew is not None:
             assert q_crew.dtype == torch.float32 and tuple(q_crew.shape) == (self.batch, self.n_crew_actions) and q_crew.is_contiguous()
         if out is None:
-            if getattr(self, "_policy_actions_buf", None) is None:
-                self._policy_actions_buf = torch.zeros(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-            out = self._policy_actions_buf
+            out = self._default_actions_out()
         dtype, layout, buf = self._describe_actions(out, output=True)
         with self._on_device():
             L.check(self.lib.susnet_policy_actions(self._h, q_imposter.data_ptr(), q_crew.data_ptr() if q_crew is not None else None,
@@ -542,8 +565,7 @@ class BatchedFourRoomEnv:
                 out = net.q_buf[self.batch] = torch.empty(self.batch, net.dims[-1], dtype=torch.float32, device=self.device)
         assert out.dtype == torch.float32 and tuple(out.shape) == (self.batch, net.dims[-1]) and out.is_contiguous()
         with self._on_device():
-            L.check(self.lib.susnet_qnet_forward(self._h, net.components, len(net.components), net.cdims, len(net.dims),
-                                                 net.packed.data_ptr(), out.data_ptr(), self._stream()))
+            L.check(self.lib.susnet_qnet_forward(self._h, *self._qnet_args(net), out.data_ptr(), self._stream()))
         return out
 
     def _describe_actions(self, a: torch.Tensor, output: bool = False):
@@ -586,10 +608,7 @@ class BatchedFourRoomEnv:
         io.actions, io.actions_dtype, io.actions_layout = a.data_ptr(), dtype, layout
         with self._on_device():
             L.check(self.lib.susnet_step(self._h, C.byref(io), self._stream()))
-            if self.export_state:
-                self._export(full=False)
-            if self.check_errors:
-                self.poll_errors()
+            self._after_step()
         return self._state_tuple(), self._rewards_view, self._done, self._trunc, self.metrics.get_metrics()
 
     def policy_step(self, q_imposter: torch.Tensor, q_crew: Optional[torch.Tensor] = None, actions_out: Optional[torch.Tensor] = None,
@@ -601,19 +620,14 @@ class BatchedFourRoomEnv:
         if q_crew is not None:
             assert q_crew.dtype == torch.float32 and tuple(q_crew.shape) == (self.batch, self.n_crew_actions) and q_crew.is_contiguous()
         if actions_out is None:
-            if getattr(self, "_policy_actions_buf", None) is None:
-                self._policy_actions_buf = torch.zeros(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-            actions_out = self._policy_actions_buf
+            actions_out = self._default_actions_out()
         dtype, layout, buf = self._describe_actions(actions_out, output=True)
         io = self._step_io
         io.actions, io.actions_dtype, io.actions_layout = buf.data_ptr(), dtype, layout
         with self._on_device():
             L.check(self.lib.susnet_policy_step(self._h, q_imposter.data_ptr(), q_crew.data_ptr() if q_crew is not None else None,
                                                 self._policy_opts(epsilon, mask_dead), C.byref(io), self._stream()))
-            if self.export_state:
-                self._export(full=False)
-            if self.check_errors:
-                self.poll_errors()
+            self._after_step()
         return self._state_tuple(), self._rewards_view, self._done, self._trunc, self.metrics.get_metrics(), buf
 
     def supports_qnet_policy_step(self, net: "PackedQNet", net_crew: "Optional[PackedQNet]" = None, epsilon: float = 0.0) -> bool:
@@ -637,22 +651,13 @@ class BatchedFourRoomEnv:
         crew's random draws -- or the crew's own network, ``net_crew`` -- and the step.  Returns like ``policy_step``; raises ``RuntimeError``
         where the library does not serve the configuration (callers fall back to ``qnet_forward`` + ``policy_step``)."""
         if actions_out is None:
-            if getattr(self, "_policy_actions_buf", None) is None:
-                self._policy_actions_buf = torch.zeros(self.batch, self.n_agents, dtype=torch.int64, device=self.device)
-            actions_out = self._policy_actions_buf
+            actions_out = self._default_actions_out()
         dtype, layout, buf = self._describe_actions(actions_out, output=True)
-        if q_out is not None:
-            assert q_out.dtype == torch.float32 and tuple(q_out.shape) == (self.batch, net.dims[-1]) and q_out.is_contiguous()
         io = self._step_io
         io.actions, io.actions_dtype, io.actions_layout = buf.data_ptr(), dtype, layout
         with self._on_device():
-            L.check(self.lib.susnet_qnet_policy_step(self._h, net.components, len(net.components), net.cdims, len(net.dims), net.packed.data_ptr(),
-                                                     q_out.data_ptr() if q_out is not None else None, self._policy_opts(epsilon, mask_dead, net_crew, q_crew_out),
-                                                     C.byref(io), self._stream()))
-            if self.export_state:
-                self._export(full=False)
-            if self.check_errors:
-                self.poll_errors()
+            self._qnet_policy_step_call(net, q_out, self._policy_opts(epsilon, mask_dead, net_crew, q_crew_out), io)
+            self._after_step()
         return self._state_tuple(), self._rewards_view, self._done, self._trunc, self.metrics.get_metrics(), buf
 
     # ---- policy-driven collection: the trainer's acting loop (train.py:345-399) writing the replay feed tick by tick -------------------
@@ -708,11 +713,7 @@ class BatchedFourRoomEnv:
         opts = self._policy_opts(epsilon, mask_dead, net_crew if one_kernel else None)
         with self._on_device():
             if one_kernel:
-                if q_out is not None:  # (the one-kernel tick can also emit the Q rows it acted on)
-                    assert q_out.dtype == torch.float32 and tuple(q_out.shape) == (self.batch, net_imposter.dims[-1]) and q_out.is_contiguous()
-                L.check(self.lib.susnet_qnet_policy_step(self._h, net_imposter.components, len(net_imposter.components), net_imposter.cdims,
-                                                         len(net_imposter.dims), net_imposter.packed.data_ptr(), q_out.data_ptr() if q_out is not None else None,
-                                                         opts, C.byref(io), self._stream()))
+                self._qnet_policy_step_call(net_imposter, q_out, opts, io)  # (the one-kernel tick can also emit the Q rows it acted on)
             else:
                 if q_imposter is None:
                     q_imposter = self.qnet_forward(net_imposter)
@@ -740,9 +741,8 @@ class BatchedFourRoomEnv:
             assert q_out.dtype == torch.float32 and tuple(q_out.shape) == (n_ticks, self.batch, net_imposter.dims[-1]) and q_out.is_contiguous()
             io.q = q_out.data_ptr()
         with self._on_device():
-            L.check(self.lib.susnet_qnet_policy_rollout(self._h, net_imposter.components, len(net_imposter.components), net_imposter.cdims,
-                                                        len(net_imposter.dims), net_imposter.packed.data_ptr(),
-                                                        self._policy_opts(epsilon, mask_dead, net_crew, q_crew_out), C.byref(io), int(n_ticks), self._stream()))
+            L.check(self.lib.susnet_qnet_policy_rollout(self._h, *self._qnet_args(net_imposter), self._policy_opts(epsilon, mask_dead, net_crew, q_crew_out),
+                                                        C.byref(io), int(n_ticks), self._stream()))
 
     def policy_block(self, n_ticks: int, net_imposter: "PackedQNet", epsilon: float = 0.0, mask_dead: bool = False,
                      net_crew: "Optional[PackedQNet]" = None) -> None:
@@ -752,16 +752,11 @@ class BatchedFourRoomEnv:
         assert self.auto_reset and self.supports_qnet_policy_step(net_imposter, net_crew, epsilon) and n_ticks >= 1
         io = L.FeedIO()
         with self._on_device():
-            L.check(self.lib.susnet_qnet_policy_rollout(self._h, net_imposter.components, len(net_imposter.components), net_imposter.cdims,
-                                                        len(net_imposter.dims), net_imposter.packed.data_ptr(), self._policy_opts(epsilon, mask_dead, net_crew),
+            L.check(self.lib.susnet_qnet_policy_rollout(self._h, *self._qnet_args(net_imposter), self._policy_opts(epsilon, mask_dead, net_crew),
                                                         C.byref(io), int(n_ticks), self._stream()))
             if self._obs_spec is not None:
                 L.check(self.lib.susnet_observe(self._h, C.byref(self._obs_spec), self._stream()))
-            # once per block: what step() / policy_step() do per tick for a handle built with these flags
-            if self.export_state:
-                self._export(full=False)
-            if self.check_errors:
-                self.poll_errors()
+            self._after_step()  # (once per block: what step() / policy_step() do per tick)
 
     def step4(self, agent_actions):
         """North-star surface ``(obs, rewards, dones, info)``; dones = done | truncated."""

@@ -35,11 +35,14 @@ through stock PyTorch-ROCm -- which is the faster of the two at large batches --
 """
 from __future__ import annotations
 
+import ctypes as C
+from functools import partial
 from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import nn
 
+from . import _lib as L
 from .env import ObsConfig
 
 
@@ -182,32 +185,77 @@ def reference_crew_mlp(env, components: Sequence[str], seed: int = 1) -> MLP:
     return model.to(env.device).eval()
 
 
+def linear_prelu_stack(layers, chained: bool = True, trailing_act: bool = False):
+    """``(linears, activations, dims = [in, out_1, .., out_n])`` of a layer list that is ``make_mlp``'s stack (dqn.py:322-329) -- ``Linear(bias=True)``
+    and single-slope ``nn.PReLU`` alternating, none after the last Linear, the widths chained -- or None: what ``pack_mlp``, ``DenseQNet``,
+    ``SpatialQNet``'s head and the dense learner accept.  ``chained=False`` / ``trailing_act=True`` give a second, wider accept set, that of
+    ``DeviceDQNTeamTrainer._mlp_dims`` alone, which has never asked for either condition (see there)."""
+    layers = list(layers)
+    linears, acts = layers[0::2], layers[1::2]
+    if not linears or not (len(acts) == len(linears) - 1 or (trailing_act and len(acts) == len(linears))) or \
+            not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
+            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or \
+            (chained and any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:]))):
+        return None
+    return linears, acts, [linears[0].in_features] + [m.out_features for m in linears]
+
+
+def stack_within_bounds(dims, max_in: Optional[int] = None) -> bool:
+    """Whether ``dims[1:]`` is what the dense kernels serve (``susnet_mlp_forward``, ``susnet_spatial_forward``'s head, ``susnet_mlp_train_step``:
+    at most 7 Linear layers, hidden widths 1 .. ``MLP_MAX_HIDDEN``, 1 .. ``MLP_MAX_OUT`` outputs) and, with ``max_in``, ``dims[0]`` is in
+    1 .. ``max_in``.  The C side of the same statement: ``check_stack_dims`` (csrc/susnet_host.h)."""
+    return len(dims) - 1 <= 7 and (max_in is None or 1 <= dims[0] <= max_in) and all(1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) and \
+        1 <= dims[-1] <= L.MLP_MAX_OUT
+
+
+def _mlp_stack(model):
+    """``linear_prelu_stack`` of a reference ``MLP``, or None."""
+    return linear_prelu_stack(model.model) if isinstance(model, MLP) else None
+
+
+def dense_stack(model):
+    """``_mlp_stack`` within the dense kernels' bounds (``DenseQNet`` acts with it, ``DeviceDQNTeamTrainer(dense=True)`` trains it), or None."""
+    stack = _mlp_stack(model)
+    return stack if stack is not None and stack_within_bounds(stack[2], L.MLP_MAX_F) else None
+
+
 def pack_mlp(env, model, components: Sequence[str], into=None):
     """``env.qnet_pack`` of a reference ``MLP`` (Linear / nn.PReLU() alternating, dqn.py:322-329), or None if ``model`` is something
     else or the library does not serve its shape on this env.  ``into``: an image of the same stack to overwrite in place."""
-    if not isinstance(model, MLP):
+    stack = _mlp_stack(model)  # (widths that do not chain were left to env.qnet_pack, which returns None for them: the same answer, sooner)
+    if stack is None:
         return None
-    layers = list(model.model)
-    linears, acts = layers[0::2], layers[1::2]
-    if not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
-            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or len(acts) != len(linears) - 1:
-        return None
+    linears, acts, _ = stack
     cpu = lambda t: t.detach().to("cpu", torch.float32).numpy()
     return env.qnet_pack(components, [cpu(m.weight) for m in linears], [cpu(m.bias) for m in linears], [float(m.weight.detach()) for m in acts], into=into)
 
 
-def _mlp_stack(model):
-    """``(linears, activations)`` of a reference ``MLP`` (Linear with bias / single-slope nn.PReLU alternating, dqn.py:322-329), or None."""
-    if not isinstance(model, MLP):
-        return None
-    layers = list(model.model)
-    linears, acts = layers[0::2], layers[1::2]
-    if not linears or len(acts) != len(linears) - 1 or \
-            not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
-            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or \
-            any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:])):
-        return None
-    return linears, acts
+def _param_ptr(device, who: str, p) -> int:
+    """``data_ptr()`` of a parameter the kernels read in place (``who``: the wrapper class, for the message)."""
+    if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
+        raise RuntimeError(f"{who}: the model's parameters must be contiguous float32 tensors on {device} (got {p.dtype} on {p.device})")
+    return p.data_ptr()
+
+
+def fill_stack(io, linears, acts, ptr) -> None:
+    """``n_dims / dims / weight / bias / slope`` of an io struct (``MlpIO``, ``SpatialIO``: the same field names) from a recognised stack."""
+    io.n_dims = len(linears) + 1
+    io.dims[0] = linears[0].in_features
+    for l, m in enumerate(linears):
+        io.dims[l + 1], io.weight[l], io.bias[l] = m.out_features, ptr(m.weight), ptr(m.bias)
+    for l, m in enumerate(acts):
+        io.slope[l] = ptr(m.weight)
+
+
+def _out_rows(net, out, n: int, device):
+    """Where a wrapper's Q rows ``[n, n_out]`` go: the caller's ``out``, checked, or the buffer ``net`` owns (``net._q``, re-made when ``n`` changes)."""
+    n_out = net.dims[-1]
+    if out is None:
+        out = net._q
+        if out is None or out.shape[0] != n:
+            out = net._q = torch.empty(n, n_out, dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, n_out) and out.is_contiguous() and out.device == device
+    return out
 
 
 def window_push_reference(src, fresh, done=None, truncated=None):
@@ -250,56 +298,30 @@ class DenseQNet:
     with -- a replay follows in-place updates, not re-pointing (capture after the trainer is built)."""
 
     def __new__(cls, env, model):
-        from . import _lib as L
-
-        stack = _mlp_stack(model)
+        stack = dense_stack(model)
         if stack is None:
             return None
-        linears, acts = stack
-        dims = [linears[0].in_features] + [m.out_features for m in linears]
-        if len(linears) > 7 or not 1 <= dims[0] <= L.MLP_MAX_F or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or \
-                not 1 <= dims[-1] <= L.MLP_MAX_OUT:
-            return None
         self = super().__new__(cls)
-        self.env, self.model, self.dims = env, model, dims
-        self._linears, self._acts = linears, acts
+        self.env, self.model = env, model
+        self._linears, self._acts, self.dims = stack
         self._q = None  # the [rows][n_out] output buffer this object owns: the one of the most recent row count
         return self
-
-    def _ptr(self, p, device):
-        if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError(f"DenseQNet: the model's parameters must be contiguous float32 tensors on {device} (got {p.dtype} on {p.device})")
-        return p.data_ptr()
 
     @torch.no_grad()
     def forward(self, rows: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Q rows ``[n, n_out]`` of ``rows`` (``[n, F]`` float32 contiguous on the env's device; default: ``env.obs``, the fused flat
         observation).  ``out``: where they go (default: the buffer this object keeps, re-made when ``n`` changes: a result is valid until
         the next call).  One launch, asynchronous."""
-        import ctypes as C
-
-        from . import _lib as L
-
         env = self.env
         if rows is None:
             rows = env.obs
-        F, n_out = self.dims[0], self.dims[-1]
+        F = self.dims[0]
         assert rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == F and rows.is_contiguous() and rows.device == env.device, (
             f"DenseQNet: rows must be a contiguous float32 [n, {F}] tensor on {env.device}")
         n = rows.shape[0]
-        if out is None:
-            out = self._q
-            if out is None or out.shape[0] != n:
-                out = self._q = torch.empty(n, n_out, dtype=torch.float32, device=env.device)
-        assert out.dtype == torch.float32 and tuple(out.shape) == (n, n_out) and out.is_contiguous() and out.device == env.device
+        out = _out_rows(self, out, n, env.device)
         io = L.MlpIO()
-        io.n_dims = len(self.dims)
-        for k, d in enumerate(self.dims):
-            io.dims[k] = d
-        for l, m in enumerate(self._linears):
-            io.weight[l], io.bias[l] = self._ptr(m.weight, env.device), self._ptr(m.bias, env.device)
-        for l, m in enumerate(self._acts):
-            io.slope[l] = self._ptr(m.weight, env.device)
+        fill_stack(io, self._linears, self._acts, partial(_param_ptr, env.device, "DenseQNet"))
         io.rows, io.n, io.q_out = rows.data_ptr(), n, out.data_ptr()
         with env._on_device():
             L.check(env.lib.susnet_mlp_forward(env._h, C.byref(io), env._stream()))
@@ -307,7 +329,7 @@ class DenseQNet:
 
 
 def _spatial_stack(model):
-    """What ``susnet_spatial_forward`` needs to know of a ``SpatialDQN`` -- ``dict(convs, k, rnn, head linears, head activations)`` -- or
+    """What ``susnet_spatial_forward`` needs to know of a ``SpatialDQN`` -- ``dict(convs, k, rnn, head linears, head activations, head dims)`` -- or
     None if the module is something else or has a part the kernels do not compute."""
     if not isinstance(model, SpatialDQN):
         return None
@@ -327,14 +349,10 @@ def _spatial_stack(model):
     if not isinstance(rnn, nn.RNN) or rnn.mode != "RNN_TANH" or rnn.bidirectional or not rnn.bias or not rnn.batch_first or \
             getattr(rnn, "proj_size", 0) != 0:
         return None
-    head = list(model.prediction_head)
-    linears, acts = head[0::2], head[1::2]
-    if not linears or len(acts) != len(linears) - 1 or \
-            not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears) or \
-            not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in acts) or \
-            any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:])) or linears[0].in_features != rnn.hidden_size:
+    head = linear_prelu_stack(model.prediction_head)
+    if head is None or head[0][0].in_features != rnn.hidden_size:
         return None
-    return dict(convs=convs, k=convs[0].kernel_size[0], rnn=rnn, linears=linears, acts=acts)
+    return dict(convs=convs, k=convs[0].kernel_size[0], rnn=rnn, linears=head[0], acts=head[1], dims=head[2])
 
 
 class SpatialQNet:
@@ -348,12 +366,10 @@ class SpatialQNet:
     re-made when the shape changes."""
 
     def __new__(cls, env, model):
-        from . import _lib as L
-
         stack = _spatial_stack(model)
         if stack is None:
             return None
-        convs, k, rnn, linears = stack["convs"], stack["k"], stack["rnn"], stack["linears"]
+        convs, k, rnn, dims = stack["convs"], stack["k"], stack["rnn"], stack["dims"]  # (dims[0] is rnn.hidden_size)
         cfg = model.config
         N, C, Fn = int(cfg["input_image_size"]), convs[0].in_channels, int(cfg["non_spatial_input_size"])
         if k not in (1, 3, 5) or not 1 <= len(convs) <= L.SPATIAL_MAX_CONV or not 1 <= N <= L.SPATIAL_MAX_N or not 1 <= C <= L.SPATIAL_MAX_C or Fn < 0:
@@ -367,10 +383,9 @@ class SpatialQNet:
                 return None
             size = span // m.stride[0] + 1
         R = convs[-1].out_channels * size * size + Fn
-        H, layers = rnn.hidden_size, rnn.num_layers
-        dims = [H] + [m.out_features for m in linears]
-        if R != rnn.input_size or R > L.SPATIAL_MAX_R or not 1 <= layers <= L.SPATIAL_MAX_RNN_LAYERS or not 1 <= H <= L.MLP_MAX_HIDDEN or \
-                len(linears) > 7 or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or not 1 <= dims[-1] <= L.MLP_MAX_OUT:
+        layers = rnn.num_layers
+        if R != rnn.input_size or R > L.SPATIAL_MAX_R or not 1 <= layers <= L.SPATIAL_MAX_RNN_LAYERS or \
+                not stack_within_bounds(dims, L.MLP_MAX_HIDDEN):  # (the head's input is the hidden state: rnn_hidden in 1 .. 256)
             return None
         slot0, slot1, s = C * N * N, 0, N  # the convolution kernel's two LDS buffers per image, and the recurrence's rotating hidden buffers
         for l, m in enumerate(convs[:-1]):
@@ -384,14 +399,9 @@ class SpatialQNet:
         self = super().__new__(cls)
         self.env, self.model = env, model
         self.N, self.C, self.Fn, self.R, self.k, self.dims = N, C, Fn, R, k, dims
-        self._convs, self._rnn, self._linears, self._acts = convs, rnn, linears, stack["acts"]
+        self._convs, self._rnn, self._linears, self._acts = convs, rnn, stack["linears"], stack["acts"]
         self._q = self._rnn_in = None
         return self
-
-    def _ptr(self, p, device):
-        if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
-            raise RuntimeError(f"SpatialQNet: the model's parameters must be contiguous float32 tensors on {device} (got {p.dtype} on {p.device})")
-        return p.data_ptr()
 
     @staticmethod
     def _strides(x, inner: int, agents: int, what: str):
@@ -415,10 +425,6 @@ class SpatialQNet:
         ``spatial`` ``[B, T, A, C, N, N]`` (PerspectiveFeaturizer) or ``[B, T, C, N, N]`` (GlobalFeaturizer's shared planes: every agent
         reads the same image), ``non_spatial`` ``[B, T, A, Fn]`` or ``[B, T, Fn]``.  ``out``: where they go (default: a buffer this object
         keeps: a result is valid until the next call).  Two launches, asynchronous."""
-        import ctypes as C
-
-        from . import _lib as L
-
         env, model, rnn = self.env, self.model, self._rnn
         if model.training and rnn.dropout > 0 and rnn.num_layers > 1:
             raise RuntimeError("SpatialQNet: the model is in training mode with rnn_dropout > 0 between its RNN layers; the kernels compute the "
@@ -432,30 +438,21 @@ class SpatialQNet:
         assert tuple(spatial.shape[-3:]) == (self.C, self.N, self.N) and non_spatial.shape[-1] == self.Fn and tuple(non_spatial.shape[:2]) == (B, T), (
             f"SpatialQNet: spatial [.., {self.C}, {self.N}, {self.N}] and non_spatial [.., {self.Fn}] with the same [B, T], got "
             f"{tuple(spatial.shape)} and {tuple(non_spatial.shape)}")
-        n, n_out = B * agents, self.dims[-1]
-        if out is None:
-            out = self._q
-            if out is None or out.shape[0] != n:
-                out = self._q = torch.empty(n, n_out, dtype=torch.float32, device=dev)
-        assert out.dtype == torch.float32 and tuple(out.shape) == (n, n_out) and out.is_contiguous() and out.device == dev
+        n = B * agents
+        out = _out_rows(self, out, n, dev)
         if self._rnn_in is None or tuple(self._rnn_in.shape) != (n, T, self.R):
             self._rnn_in = torch.empty(n, T, self.R, dtype=torch.float32, device=dev)
+        ptr = partial(_param_ptr, dev, "SpatialQNet")
         io = L.SpatialIO()
         io.T, io.N, io.C, io.n_conv, io.k, io.Fn = T, self.N, self.C, len(self._convs), self.k, self.Fn
         for l, m in enumerate(self._convs):
             io.conv_out[l], io.conv_stride[l], io.conv_padding[l], io.conv_dilation[l] = m.out_channels, m.stride[0], m.padding[0], m.dilation[0]
-            io.conv_weight[l], io.conv_bias[l] = self._ptr(m.weight, dev), self._ptr(m.bias, dev)
+            io.conv_weight[l], io.conv_bias[l] = ptr(m.weight), ptr(m.bias)
         io.rnn_layers, io.rnn_hidden = rnn.num_layers, rnn.hidden_size
         for l in range(rnn.num_layers):
             for name, field in (("weight_ih", io.w_ih), ("weight_hh", io.w_hh), ("bias_ih", io.b_ih), ("bias_hh", io.b_hh)):
-                field[l] = self._ptr(getattr(rnn, f"{name}_l{l}"), dev)
-        io.n_dims = len(self.dims)
-        for i, d in enumerate(self.dims):
-            io.dims[i] = d
-        for l, m in enumerate(self._linears):
-            io.weight[l], io.bias[l] = self._ptr(m.weight, dev), self._ptr(m.bias, dev)
-        for l, m in enumerate(self._acts):
-            io.slope[l] = self._ptr(m.weight, dev)
+                field[l] = ptr(getattr(rnn, f"{name}_l{l}"))
+        fill_stack(io, self._linears, self._acts, ptr)
         io.spatial, io.non_spatial = spatial.data_ptr(), non_spatial.data_ptr()
         for d in range(3):
             io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
@@ -544,8 +541,6 @@ class PolicyRollout:
 
     def _check_window_served(self, asked: bool) -> None:
         """At ``sequence_length`` > 1 there is no torch path in this class: a network the dense kernel does not serve is an error."""
-        from . import _lib as L
-
         env, T = self.env, self.sequence_length
         F = env.obs.shape[-1]
         need = (f"PolicyRollout: sequence_length = {T} is served through the dense kernel only (dense=True): reference MLPs whose input is the "
@@ -593,10 +588,6 @@ class PolicyRollout:
         """The window one tick on (``susnet_window_push``, one launch, asynchronous): ``env.obs`` -- the state AFTER the tick -- enters as the
         newest state, or fills the window where ``done | truncated`` (bool / uint8 ``[B]`` on the env's device, read in place; None: no row
         ended).  The two buffers swap; returns the new ``window_feats``."""
-        import ctypes as C
-
-        from . import _lib as L
-
         assert self._windows is not None, "push: built with sequence_length = 1, there is no window"
         env = self.env
         self._window_current()
@@ -796,7 +787,6 @@ class WindowedPolicyRollout:
         self._actions = torch.zeros(env.batch, env.n_agents, dtype=torch.int64, device=env.device)
 
     def _spatial(self, model, n_actions):
-        from . import _lib as L
         from .features import GlobalFeaturizer, PerspectiveFeaturizer
 
         net = SpatialQNet(self.env, model)

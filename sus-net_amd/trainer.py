@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
-from .policy import MLP, RandomEquiprobable, _mlp_stack, _weights_version
+from .policy import MLP, RandomEquiprobable, _weights_version, dense_stack, linear_prelu_stack
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults (train.py:35-37 passes only lr)
 
@@ -130,7 +130,8 @@ class DeviceDQNTeamTrainer:
         self._owner = ["flat", "flat"]
         self._ws, self._losses = None, None
         # the dense step: each trained team's [F, h.., n_actions] where susnet_mlp_train_step serves it
-        self._dense_dims = [self._stack_dims(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        stacks = [dense_stack(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self._dense_dims = [s and s[2] for s in stacks]
         self.sequence_length = None if sequence_length is None else int(sequence_length)  # (the dense step's T: settled by _dense_served)
         self.dense = (bool(dense) and self.device.type == "cuda" and any(self.trained) and featurizer is None
                       and all(c in L.FLAT_COMPONENTS for c in self.components)
@@ -140,27 +141,23 @@ class DeviceDQNTeamTrainer:
     # ---- configuration ----
     @staticmethod
     def _mlp_dims(model):
+        """``[F, h1, .., h4, n_out]`` of a reference ``MLP`` of five Linear layers (what ``susnet_dqn_train_step`` may serve), or None."""
         if not isinstance(model, MLP):
             return None
-        layers = list(model.model)
-        lin, act = layers[0::2], layers[1::2]
-        if len(lin) != 5 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in lin) or \
-                not all(isinstance(m, nn.PReLU) and m.weight.numel() == 1 for m in act):
-            return None
-        return [lin[0].in_features] + [m.out_features for m in lin]
+        # Kept as it has been since the fused learner was written, and unlike every other caller of the recogniser: the widths are not asked
+        # to chain, and a single-slope PReLU AFTER the fifth Linear is let through (make_mlp builds neither).  susnet_dqn_workspace_bytes sees
+        # dims only, so such a module would still be taken for served: tightening this changes which trainers run on the HIP path
+        stack = linear_prelu_stack(model.model, chained=False, trailing_act=True)
+        return stack[2] if stack is not None and len(stack[0]) == 5 else None
 
-    @staticmethod
-    def _stack_dims(model):
-        """``[F, h.., n_out]`` of a reference ``MLP`` stack within ``susnet_mlp_train_step``'s bounds (those of ``susnet_mlp_forward``), or None."""
-        stack = _mlp_stack(model)
-        if stack is None:
-            return None
-        linears, _ = stack
-        dims = [linears[0].in_features] + [m.out_features for m in linears]
-        if len(linears) > 7 or not 1 <= dims[0] <= L.MLP_MAX_F or any(not 1 <= d <= L.MLP_MAX_HIDDEN for d in dims[1:-1]) or \
-                not 1 <= dims[-1] <= L.MLP_MAX_OUT:
-            return None
-        return dims
+    def _fill_team(self, tm, t: int, dims) -> None:
+        """One trained team's ``susnet_dqn_team``: its stack, the Adam constants and the flat buffers the kernels update."""
+        tm.enabled, tm.n_dims = 1, len(dims)
+        for i, v in enumerate(dims):
+            tm.dims[i] = v
+        tm.lr, tm.beta1, tm.beta2, tm.eps = self.lr, BETAS[0], BETAS[1], EPS
+        tm.params, tm.target_params = self.flat[t].data_ptr(), self.target_flat[t].data_ptr()
+        tm.exp_avg, tm.exp_avg_sq, tm.step = self.exp_avg[t].data_ptr(), self.exp_avg_sq[t].data_ptr(), self.step_count[t].data_ptr()
 
     def _io(self, ring=None, idx=None) -> "L.DqnIO":
         io = L.DqnIO()
@@ -173,12 +170,7 @@ class DeviceDQNTeamTrainer:
             tm = io.team[t]
             if not self.trained[t] or self._dims[t] is None:
                 continue
-            tm.enabled, tm.n_dims = 1, 6
-            for i, v in enumerate(self._dims[t]):
-                tm.dims[i] = v
-            tm.lr, tm.beta1, tm.beta2, tm.eps = self.lr, BETAS[0], BETAS[1], EPS
-            tm.params, tm.target_params = self.flat[t].data_ptr(), self.target_flat[t].data_ptr()
-            tm.exp_avg, tm.exp_avg_sq, tm.step = self.exp_avg[t].data_ptr(), self.exp_avg_sq[t].data_ptr(), self.step_count[t].data_ptr()
+            self._fill_team(tm, t, self._dims[t])  # (n_dims = 6: _mlp_dims)
             net = self._policy_image(t)
             tm.packed = net.packed.data_ptr() if net is not None else None
         if ring is not None:
@@ -220,15 +212,8 @@ class DeviceDQNTeamTrainer:
         io = L.MlpTrainIO()
         io.gamma = self.gamma
         for t in range(2):
-            tm = io.team[t]
-            if not self.trained[t] or self._dense_dims[t] is None:
-                continue
-            tm.enabled, tm.n_dims = 1, len(self._dense_dims[t])
-            for i, v in enumerate(self._dense_dims[t]):
-                tm.dims[i] = v
-            tm.lr, tm.beta1, tm.beta2, tm.eps = self.lr, BETAS[0], BETAS[1], EPS
-            tm.params, tm.target_params = self.flat[t].data_ptr(), self.target_flat[t].data_ptr()
-            tm.exp_avg, tm.exp_avg_sq, tm.step = self.exp_avg[t].data_ptr(), self.exp_avg_sq[t].data_ptr(), self.step_count[t].data_ptr()
+            if self.trained[t] and self._dense_dims[t] is not None:
+                self._fill_team(io.team[t], t, self._dense_dims[t])
         return io
 
     def _dense_served(self) -> bool:
@@ -261,20 +246,23 @@ class DeviceDQNTeamTrainer:
             return self._dense_step(ring, idx)
         return self._torch_step(ring, idx)
 
-    def _hip_io(self, ring, idx) -> "L.DqnIO":
-        """The complete ``susnet_dqn_io`` of one step on ``ring`` at ``idx``: Adam state in the flat buffers, workspace and losses allocated."""
-        env = self.env
-        for t in range(2):
-            self._state_to_flat(t)
-        io = self._io(ring, idx)
+    def _workspace_and_losses(self, io, workspace_bytes) -> None:
+        """``io.workspace`` (grown to what ``workspace_bytes`` -- the learner's own probe -- asks for this io) and ``io.losses_out``."""
         nbytes = C.c_uint64()
-        L.check(env.lib.susnet_dqn_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)))
+        L.check(workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)))
         if self._ws is None or self._ws.numel() < nbytes.value:
             self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
         if self._losses is None:
             self._losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
         io.losses_out = self._losses.data_ptr()
+
+    def _hip_io(self, ring, idx) -> "L.DqnIO":
+        """The complete ``susnet_dqn_io`` of one step on ``ring`` at ``idx``: Adam state in the flat buffers, workspace and losses allocated."""
+        for t in range(2):
+            self._state_to_flat(t)
+        io = self._io(ring, idx)
+        self._workspace_and_losses(io, self.env.lib.susnet_dqn_workspace_bytes)
         return io
 
     def _hip_step(self, ring, idx):
@@ -294,8 +282,6 @@ class DeviceDQNTeamTrainer:
         env, n, T = self.env, int(idx.numel()), ring.trajectory_size
         for t in range(2):
             self._state_to_flat(t)
-        if self._losses is None:
-            self._losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         io = self._dense_io()
         if n > 0:
             if self._dense_bufs is None or self._dense_bufs[0] != n:
@@ -310,12 +296,7 @@ class DeviceDQNTeamTrainer:
         io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
         io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
         io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
-        nbytes = C.c_uint64()
-        L.check(env.lib.susnet_mlp_train_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)))
-        if self._ws is None or self._ws.numel() < nbytes.value:
-            self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        io.workspace, io.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        io.losses_out = self._losses.data_ptr()
+        self._workspace_and_losses(io, env.lib.susnet_mlp_train_workspace_bytes)
         with torch.cuda.device(self.device):
             if n > 0:
                 dt = env._ROW_DTYPES[rows.dtype]
