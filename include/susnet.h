@@ -725,6 +725,77 @@ typedef struct susnet_mlp_train_io {
 int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out);
 int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream);
 
+/* The same train step once more -- DQNTeamTrainer.train_step (src/train.py:50-149) with exactly the semantics of susnet_dqn_train_step and
+ * susnet_mlp_train_step above: agents in order, imposter team then crew team, gradients accumulating over the agents (one zero_grad per
+ * call), y = r + gamma max_a target(s') with y = r on done rows, mean MSE, torch's single-tensor Adam with the step count on the device, no
+ * step for an empty (agent, team) list, out-of-range indices and actions clamped -- for the reference's SpatialDQN (src/models/dqn.py:205-301:
+ * Conv2d + ReLU stack per window step, tanh nn.RNN, PReLU head; the network susnet_spatial_forward computes) in TRAINING mode.
+ *   Inputs are the featurizers' tensors of the batch's states and next states IN BATCH ORDER (row s belongs to indices[s]), addressed as
+ * susnet_spatial_io addresses them, with the three (row, agent, timestep) strides: the Perspective featurizer's buffers are read in place, the
+ * Global featurizer's shared planes have an agent stride of 0.  spatial and next_spatial share spatial_stride, non_spatial and
+ * next_non_spatial share non_spatial_stride.  actions, rewards, dones and imposters are read in place from the ring at clamp(indices[s]).
+ *   team[].params (target_params, exp_avg, exp_avg_sq likewise) is flat in SpatialDQN.parameters() order: cnn.model.{0,2,..}.weight / bias
+ * ([conv_out][C_in][k][k], [conv_out]), then per RNN layer weight_ih_l [H][R or H], weight_hh_l [H][H], bias_ih_l, bias_hh_l, then the head
+ * W0, b0, a0, .., W_last, b_last (as susnet_mlp_train_step); 4-byte alignment is all that is assumed.  team[].n_dims / dims describe the HEAD
+ * ([rnn_hidden, h1, .., n_actions]); net[] the rest of the team's network.  team[].packed must be NULL: susnet_spatial_forward reads params in
+ * place, so the next forward sees the step.
+ *   Training-mode semantics: the kernels compute no dropout (nn.RNN drops out between layers only: callers serve rnn dropout == 0 or one
+ * layer).  ReLU passes the gradient where its output is > 0 and nothing at exactly 0, as torch does; PReLU as susnet_mlp_train_step (z > 0 ? g :
+ * a g, d slope = sum over z <= 0 of z g); tanh backward is (1 - h^2) g on the stored h; bias_ih_l and bias_hh_l receive the same gradient; the
+ * non-spatial columns of the RNN input are inputs, not parameters.
+ *   Served: per enabled team the networks susnet_spatial_forward serves -- T in 1 .. 8, N in 1 .. 16, C in 1 .. 32, n_conv in 1 .. 4,
+ * conv_out in 1 .. 32, k in {1, 3, 5}, conv_stride 1 .. 4, conv_padding 0 .. 8, conv_dilation 1 .. 4, every layer's output size at least 1,
+ * Fn >= 0, R = conv_out * H_out^2 + Fn <= SUSNET_SPATIAL_MAX_R, rnn_layers 1 .. 4, rnn_hidden 1 .. 256, the head n_dims 2 .. 8 with dims[0] ==
+ * rnn_hidden, hidden widths 1 .. 256, at most 32 outputs; none of the forward's bounds is narrowed (no activation is resident in LDS beyond
+ * the head's fixed buffers) --, one imposter, 2 .. 16 agents, n in 0 .. 2^30, both enabled teams with the same T, N, C and Fn (they read the
+ * same inputs), lr >= 0, 0 <= beta < 1, strides >= 0, every pointer non-NULL and 4-byte aligned (Fn == 0: non_spatial / next_non_spatial may
+ * be NULL), the workspace 256-byte aligned and of susnet_spatial_train_workspace_bytes bytes (it grows with n: the RNN inputs of both
+ * networks and the convolutions' saved activations and their gradients, n x T images each).  Anything else: SUSNET_E_INVALID with a message
+ * that names the field, before anything is launched.  The handle supplies the configuration (agents, imposters) and the error conventions only.
+ *   Launches: 1 to split the batch, then 4 per (agent, enabled team) update -- 1 + 4 x agents x enabled teams per call, whatever the data:
+ *     convolutions  (vector ALU) of the update's rows, online network on the states (every layer's output kept in the workspace) and TARGET
+ *                   network on the next states, both RNN input rows written; the target network's Q rows are computed inside the update,
+ *                   never by a launch of their own, and the target network is not updated;
+ *     recurrence    target then online recurrence and head on v_mfma_f32_32x32x2_f32 over tiles of 32 rows, 2 (Q - y) / count back through
+ *                   the head and through time; gradients of the head's and the RNN's parameters as the workgroup's partial, the gradient
+ *                   of the RNN input's convolution columns into the workspace;
+ *     convolutions' backward (vector ALU): through the ReLUs and the transposed convolutions, then every weight's sum over the
+ *                   workgroup's images in a fixed order;
+ *     k_train_adam  as the other two learners: partials summed in workgroup order, accumulated over the agents, Adam.
+ * All on `stream`, no host synchronisation, no parallel branches, no atomics: a call can be captured as a hipGraph, and every sum runs in a
+ * fixed order, so two runs from equal state leave identical bytes.  The gradient kernels run SUSNET_SPATIAL_TRAIN_MAX_GRID workgroups at
+ * most, and fewer where the partial gradients together would exceed 64 MiB. */
+#define SUSNET_SPATIAL_TRAIN_MAX_GRID 256
+typedef struct susnet_spatial_net {
+    int32_t T, N, C, Fn;             /* window steps, image size, input channels, non-spatial features per step */
+    int32_t n_conv, k;               /* as susnet_spatial_io */
+    int32_t conv_out[4], conv_stride[4], conv_padding[4], conv_dilation[4];
+    int32_t rnn_layers, rnn_hidden;
+} susnet_spatial_net;
+typedef struct susnet_spatial_train_io {
+    susnet_spatial_net net[2];       /* [0] imposters, [1] crew: looked at where team[].enabled */
+    susnet_dqn_team team[2];         /* n_dims / dims: the head [rnn_hidden, h.., n_actions]; `packed` must be NULL */
+    const float *spatial;            /* device float32, BATCH order: row s belongs to indices[s] */
+    const float *next_spatial;       /* the same of next_states */
+    int64_t spatial_stride[3];       /* floats: per row, per agent, per timestep; an image [C][N][N] is contiguous */
+    const float *non_spatial;        /* device float32 (Fn == 0: may be NULL) */
+    const float *next_non_spatial;
+    int64_t non_spatial_stride[3];   /* floats: per row, per agent, per timestep; a step's Fn features are contiguous */
+    const int64_t *actions;          /* ring [max_size][A] int64   -- read in place at indices, as susnet_dqn_io */
+    const float *rewards;            /* ring [max_size][A] float32 */
+    const uint8_t *dones;            /* ring [max_size][1] bool */
+    const int16_t *imposters;        /* ring [max_size][n_imposters] int16 */
+    int64_t max_size;
+    const int64_t *indices;          /* [n] device: the sampled ring rows */
+    int64_t n;
+    double gamma;
+    float *losses_out;               /* [2] float32 device: the accumulated losses [imposter, crew] */
+    void *workspace;                 /* device scratch of susnet_spatial_train_workspace_bytes bytes, 256-byte aligned */
+    uint64_t workspace_bytes;
+} susnet_spatial_train_io;
+int susnet_spatial_train_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out);
+int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream);
+
 /* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
  * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.
  * Per tick t and environment b, for every agent: G[a] = (double)rewards[t][b][a] + gamma * G[a] in float64, the product rounded before

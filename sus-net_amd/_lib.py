@@ -22,6 +22,7 @@ WINDOW_MAX_T = 8  # susnet_window_push: states per window
 # the convolution kernel's images per group and grid cap
 SPATIAL_MAX_T, SPATIAL_MAX_N, SPATIAL_MAX_C, SPATIAL_MAX_CONV, SPATIAL_MAX_R, SPATIAL_MAX_RNN_LAYERS = 8, 16, 32, 4, 4096, 4
 SPATIAL_CONV_GROUP, SPATIAL_CONV_MAX_GRID = 16, 1024
+SPATIAL_TRAIN_MAX_GRID = 256  # SUSNET_SPATIAL_TRAIN_MAX_GRID: workgroups of susnet_spatial_train_step's gradient kernels
 SPATIAL_LDS_BYTES = 160 * 1024  # a workgroup's LDS: (rnn_layers + 1) x 64 rows x max(rnn_hidden, head widths) floats must fit
 
 VARIANT_BASE, VARIANT_ITG, VARIANT_TAGGING = 0, 1, 2
@@ -45,7 +46,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -152,6 +153,20 @@ class MlpTrainIO(C.Structure):
     _fields_ = [("feat", C.c_void_p), ("next_feat", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
                 ("imposters", C.c_void_p), ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double),
                 ("team", DqnTeam * 2), ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+class SpatialNet(C.Structure):
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("Fn", C.c_int32), ("n_conv", C.c_int32), ("k", C.c_int32),
+                ("conv_out", C.c_int32 * 4), ("conv_stride", C.c_int32 * 4), ("conv_padding", C.c_int32 * 4), ("conv_dilation", C.c_int32 * 4),
+                ("rnn_layers", C.c_int32), ("rnn_hidden", C.c_int32)]
+
+
+class SpatialTrainIO(C.Structure):
+    _fields_ = [("net", SpatialNet * 2), ("team", DqnTeam * 2), ("spatial", C.c_void_p), ("next_spatial", C.c_void_p),
+                ("spatial_stride", C.c_int64 * 3), ("non_spatial", C.c_void_p), ("next_non_spatial", C.c_void_p),
+                ("non_spatial_stride", C.c_int64 * 3), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+                ("imposters", C.c_void_p), ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double),
+                ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
 
 
 class EpisodeRecord(C.Structure):
@@ -271,6 +286,8 @@ def lib():
     L.susnet_dqn_train_sweep.argtypes = [P(C.c_void_p), P(DqnIO), C.c_int32, C.c_void_p]
     L.susnet_mlp_train_workspace_bytes.argtypes = [C.c_void_p, P(MlpTrainIO), P(C.c_uint64)]
     L.susnet_mlp_train_step.argtypes = [C.c_void_p, P(MlpTrainIO), C.c_void_p]
+    L.susnet_spatial_train_workspace_bytes.argtypes = [C.c_void_p, P(SpatialTrainIO), P(C.c_uint64)]
+    L.susnet_spatial_train_step.argtypes = [C.c_void_p, P(SpatialTrainIO), C.c_void_p]
     L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]
     L.susnet_episode_stats.argtypes = [C.c_void_p, P(EpisodeIO), C.c_void_p]
     for name in EXPORTS:

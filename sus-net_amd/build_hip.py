@@ -3,7 +3,8 @@
 One object per translation unit (susnet_capi.hip = the handle and the acting side of the C ABI + their small kernels;
 susnet_capi_nets.hip = the network entry points, host code only; susnet_capi_ring.hip / susnet_capi_train.hip /
 susnet_capi_episodes.hip = the replay ring, the DQN learners and the episode bookkeeping, each entry point with its kernels;
-inst_*.hip = one compiled-in configuration of the stepping kernels each, the Q-network, window and dense-learner kernels), compiled
+inst_*.hip = one compiled-in configuration of the stepping kernels each, the Q-network, window, dense-learner and SpatialDQN-learner
+kernels -- inst_spatial_train.hip is picked up, like every unit, by the glob of sources() --), compiled
 in parallel, then linked into ONE shared library."""
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-p
 # registers (7 -> 6 waves), k_featurize / k_observe from 83 to 105 (5 -> 4)
 # -- nor for the units carved out of it (susnet_capi_*.hip: ring, learners, episodes).  The dense learner's kernels (inst_mlp_train.hip) are
 # under max-ilp by their unit's name; they were tested and timed in that form and nobody has measured the alternative
+# (so are the SpatialDQN learner's, inst_spatial_train.hip: tested and timed in that form only)
 ILP_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 
 

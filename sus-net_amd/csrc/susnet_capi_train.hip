@@ -1,6 +1,7 @@
 // susnet_capi_train.hip -- the DQN learners of the C ABI: susnet_dqn_train_step and susnet_dqn_train_sweep (the fused learner on the
 // compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step (the dense learner on any served stack;
-// its gradient kernels: inst_mlp_train.hip).  Both end every update with this unit's k_train_adam.
+// its gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step (the SpatialDQN learner; its kernels: inst_spatial_train.hip).  All
+// end every update with this unit's k_train_adam.
 #include <algorithm>
 #include <cstring>
 
@@ -8,6 +9,7 @@
 #include "susnet_dense.h" // kDnMaxHidden / kDnMaxOut: the forward's widths, which the dense learner's must equal
 #include "susnet_train.h"
 #include "susnet_mlp_train.h"
+#include "susnet_spatial_train.h"
 #include "susnet_host.h"
 
 using namespace susnet;
@@ -331,6 +333,217 @@ extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io 
             if (!T.enabled) continue;
             HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, zsave, T.step,
                                           (int)pl.G, st));
+            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
+                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
+            HIP_TRY(hipGetLastError());
+        }
+    return SUSNET_OK;
+}
+
+// ---- the SpatialDQN learner's train step (susnet_spatial_train.h; the kernels: inst_spatial_train.hip) ----
+struct SpTrainPlan : TrWorkspace {
+    SpTrainNet net[2];
+    int64_t G = 1, Gconv = 1;
+    uint64_t off_X = 0, off_Xt = 0, off_act = 0, off_dact = 0, off_dX = 0, off_tact = 0, off_hs = 0, off_ds = 0, off_zs = 0, off_nets = 0, bytes = 0;
+};
+// one enabled team's network: the spatial rules (those of susnet_spatial_forward) stated here, the head's by the shared stack checks
+static int sp_train_net(const Refuse &bad, int t, const susnet_spatial_net &sn, const susnet_dqn_team &tm, SpTrainNet &net) {
+    const auto S = [](long long v) { return std::to_string(v); };
+    const std::string who = "net[" + S(t) + "].", team = "team[" + S(t) + "]."; // where the spatial fields and the head's sit
+    const auto range = [&](const std::string &field, long long v, long long lo, long long hi) {
+        return who + field + " = " + S(v) + " (served: " + S(lo) + " .. " + S(hi) + ")";
+    };
+    if (sn.T < 1 || sn.T > SUSNET_SPATIAL_MAX_T) return bad(range("T", sn.T, 1, SUSNET_SPATIAL_MAX_T));
+    if (sn.N < 1 || sn.N > SUSNET_SPATIAL_MAX_N) return bad(range("N", sn.N, 1, SUSNET_SPATIAL_MAX_N));
+    if (sn.C < 1 || sn.C > SUSNET_SPATIAL_MAX_C) return bad(range("C", sn.C, 1, SUSNET_SPATIAL_MAX_C));
+    if (sn.n_conv < 1 || sn.n_conv > SUSNET_SPATIAL_MAX_CONV) return bad(range("n_conv", sn.n_conv, 1, SUSNET_SPATIAL_MAX_CONV));
+    if (sn.k != 1 && sn.k != 3 && sn.k != 5) return bad(who + "k = " + S(sn.k) + " (served: one square kernel size of 1, 3 or 5)");
+    if (sn.Fn < 0) return bad(who + "Fn = " + S(sn.Fn) + " (at least 0)");
+    net = SpTrainNet{};
+    net.T = sn.T, net.N = sn.N, net.C = sn.C, net.Fn = sn.Fn, net.n_conv = sn.n_conv, net.k = sn.k;
+    net.size[0] = sn.N, net.ch[0] = sn.C, net.sz[0] = sn.C * sn.N * sn.N;
+    int off = 0;
+    for (int l = 0; l < sn.n_conv; l++) {
+        const std::string at = "[" + S(l) + "]";
+        if (sn.conv_out[l] < 1 || sn.conv_out[l] > 32) return bad(range("conv_out" + at, sn.conv_out[l], 1, 32));
+        if (sn.conv_stride[l] < 1 || sn.conv_stride[l] > 4) return bad(range("conv_stride" + at, sn.conv_stride[l], 1, 4));
+        if (sn.conv_padding[l] < 0 || sn.conv_padding[l] > 8) return bad(range("conv_padding" + at, sn.conv_padding[l], 0, 8));
+        if (sn.conv_dilation[l] < 1 || sn.conv_dilation[l] > 4) return bad(range("conv_dilation" + at, sn.conv_dilation[l], 1, 4));
+        const int span = net.size[l] + 2 * sn.conv_padding[l] - sn.conv_dilation[l] * (sn.k - 1) - 1;
+        if (span < 0) return bad(who + "conv layer " + S(l) + ": output size < 1 (input " + S(net.size[l]) + ", k " + S(sn.k) + ", conv_padding" + at + " " +
+                                 S(sn.conv_padding[l]) + ", conv_dilation" + at + " " + S(sn.conv_dilation[l]) + ")");
+        net.size[l + 1] = span / sn.conv_stride[l] + 1;
+        net.ch[l + 1] = sn.conv_out[l];
+        net.sz[l + 1] = net.ch[l + 1] * net.size[l + 1] * net.size[l + 1];
+        net.stride[l] = sn.conv_stride[l], net.pad[l] = sn.conv_padding[l], net.dil[l] = sn.conv_dilation[l];
+        net.oCW[l] = off;
+        off += net.ch[l + 1] * net.ch[l] * sn.k * sn.k;
+        net.oCB[l] = off;
+        off += net.ch[l + 1];
+        net.maxsz = std::max(net.maxsz, net.sz[l + 1]);
+        if (l < sn.n_conv - 1) {
+            net.aoff[l] = net.asz;
+            net.asz += net.sz[l + 1];
+        }
+    }
+    const long long R = (long long)net.sz[sn.n_conv] + sn.Fn;
+    if (R > SUSNET_SPATIAL_MAX_R)
+        return bad(who + "R = conv_out * H_out^2 + Fn = " + S(R) + " (the RNN's input width: at most SUSNET_SPATIAL_MAX_R = " + S(SUSNET_SPATIAL_MAX_R) + ")");
+    net.R = (int32_t)R, net.Rc = net.sz[sn.n_conv];
+    if (sn.rnn_layers < 1 || sn.rnn_layers > SUSNET_SPATIAL_MAX_RNN_LAYERS) return bad(range("rnn_layers", sn.rnn_layers, 1, SUSNET_SPATIAL_MAX_RNN_LAYERS));
+    if (sn.rnn_hidden < 1 || sn.rnn_hidden > kMtMaxHidden) return bad(range("rnn_hidden", sn.rnn_hidden, 1, kMtMaxHidden));
+    net.L = sn.rnn_layers, net.H = sn.rnn_hidden;
+    for (int l = 0; l < net.L; l++) {
+        net.oWih[l] = off;
+        off += net.H * (l == 0 ? net.R : net.H);
+        net.oWhh[l] = off;
+        off += net.H * net.H;
+        net.oBih[l] = off;
+        off += net.H;
+        net.oBhh[l] = off;
+        off += net.H;
+    }
+    if (int rc = check_stack_n_dims(bad, team, tm.n_dims, "a head of 1 .. 7 Linear layers")) return rc;
+    if (tm.dims[0] != sn.rnn_hidden)
+        return bad(team + "dims[0] = " + S(tm.dims[0]) + " (the head reads the hidden state: " + who + "rnn_hidden = " + S(sn.rnn_hidden) + ")");
+    if (int rc = check_stack_dims(bad, team, tm.n_dims, tm.dims, kMtMaxHidden, kMtMaxOut)) return rc;
+    if (tm.packed) return bad(team + "packed must be NULL (susnet_spatial_forward reads params in place: there is no image to rewrite)");
+    if (!(tm.lr >= 0.0) || !(tm.beta1 >= 0.0 && tm.beta1 < 1.0) || !(tm.beta2 >= 0.0 && tm.beta2 < 1.0) || !(tm.eps >= 0.0))
+        return bad(team + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
+    MlpTrainNet &hd = net.head;
+    hd.nl = tm.n_dims - 1;
+    for (int l = 0; l <= hd.nl; l++) hd.d[l] = tm.dims[l];
+    tr_param_layout(hd, hd.nl);
+    for (int l = 0; l < hd.nl; l++) hd.oW[l] += off, hd.oB[l] += off;
+    for (int l = 0; l < hd.nl - 1; l++) {
+        hd.oA[l] += off;
+        hd.zo[l] = hd.Z;
+        hd.Z += hd.d[l + 1] * kTrTS;
+    }
+    net.P = off + hd.P;
+    net.Pp = (net.P + 1 + 3) / 4 * 4;
+    return SUSNET_OK;
+}
+static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *io, SpTrainPlan &pl) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_train_step: null env / io");
+    const Refuse bad{env, "susnet_spatial_train_step"};
+    const auto S = [](long long v) { return std::to_string(v); };
+    if (env->c.n_imp != 1)
+        return bad("n_imposters = " + S(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
+                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + S(env->c.A) + " (served: 2 .. 16)");
+    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + S(io->n) + " (served: 0 .. 2^30)");
+    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
+    int64_t pmax = 4, T = 1, R = 1, Rc = 1, asz = 0, maxsz = 1, slice = 1, Z = 4;
+    int first = -1;
+    for (int tm = 0; tm < 2; tm++) {
+        pl.net[tm] = SpTrainNet{};
+        if (!io->team[tm].enabled) continue;
+        const std::string who = "net[" + S(tm) + "].";
+        if (int rc = sp_train_net(bad, tm, io->net[tm], io->team[tm], pl.net[tm])) return rc;
+        const SpTrainNet &net = pl.net[tm];
+        if (first >= 0) {
+            const susnet_spatial_net &a = io->net[first], &c = io->net[tm];
+            const char *field = a.T != c.T ? "T" : a.N != c.N ? "N" : a.C != c.C ? "C" : a.Fn != c.Fn ? "Fn" : nullptr;
+            if (field) return bad(who + field + " differs from net[" + S(first) + "]." + field + ": both teams read the same inputs");
+        } else first = tm;
+        pmax = std::max<int64_t>(pmax, net.Pp);
+        T = net.T;
+        R = std::max<int64_t>(R, net.R), Rc = std::max<int64_t>(Rc, net.Rc), asz = std::max<int64_t>(asz, net.asz);
+        maxsz = std::max<int64_t>(maxsz, net.maxsz);
+        slice = std::max<int64_t>(slice, (int64_t)net.L * net.T * net.H * kTrTS);
+        Z = std::max<int64_t>(Z, net.head.Z);
+    }
+    for (int d = 0; d < 3; d++) {
+        if (io->spatial_stride[d] < 0) return bad("spatial_stride[" + S(d) + "] = " + S(io->spatial_stride[d]) + " (at least 0)");
+        if (first >= 0 && io->net[first].Fn > 0 && io->non_spatial_stride[d] < 0)
+            return bad("non_spatial_stride[" + S(d) + "] = " + S(io->non_spatial_stride[d]) + " (at least 0)");
+    }
+    const int64_t images = std::max<int64_t>(1, io->n * T);
+    pl.G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kStMaxGrid, images), (int64_t)(kMtMaxPartialBytes / (4ull * (uint64_t)pmax))));
+    pl.Gconv = std::min<int64_t>(kStConvGrid, 2 * images);
+    uint64_t o = tr_workspace_layout(pl, env->c.A, io->n, pl.net[0].Pp, pl.net[1].Pp, pl.G, pmax);
+    const auto take = [&](uint64_t &off, uint64_t floats) {
+        off = o;
+        o = up(o + 4ull * std::max<uint64_t>(floats, 4), 256);
+    };
+    take(pl.off_X, (uint64_t)images * (uint64_t)R);
+    take(pl.off_Xt, (uint64_t)images * (uint64_t)R);
+    take(pl.off_act, (uint64_t)images * (uint64_t)asz);
+    take(pl.off_dact, (uint64_t)images * (uint64_t)asz);
+    take(pl.off_dX, (uint64_t)images * (uint64_t)Rc);
+    take(pl.off_tact, (uint64_t)pl.Gconv * 2ull * (uint64_t)maxsz);
+    take(pl.off_hs, (uint64_t)pl.G * (uint64_t)slice);
+    take(pl.off_ds, (uint64_t)pl.G * (uint64_t)slice);
+    take(pl.off_zs, (uint64_t)pl.G * (uint64_t)Z);
+    take(pl.off_nets, 2 * (sizeof(SpTrainNet) + 3) / 4);
+    pl.bytes = o;
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_spatial_train_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out) {
+    SpTrainPlan pl;
+    if (int rc = sp_train_plan(env, io, pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
+extern "C" int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream) {
+    SpTrainPlan pl;
+    if (int rc = sp_train_plan(env, io, pl)) return rc;
+    const Refuse bad{env, "susnet_spatial_train_step"};
+    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
+        return bad("workspace missing, smaller than susnet_spatial_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
+                   " bytes) or not 256-byte aligned");
+    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
+    if (!io->actions) return bad("actions is NULL");
+    if (!io->rewards) return bad("rewards is NULL");
+    if (!io->dones) return bad("dones is NULL");
+    if (!io->imposters) return bad("imposters is NULL");
+    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
+    const bool any = io->team[0].enabled || io->team[1].enabled;
+    const int Fn = io->team[0].enabled ? io->net[0].Fn : io->team[1].enabled ? io->net[1].Fn : 0;
+    if (io->n > 0 && any) {
+        if (!io->indices) return bad("indices is NULL");
+        if (!io->spatial || misaligned(io->spatial)) return bad("spatial is NULL or not 4-byte aligned");
+        if (!io->next_spatial || misaligned(io->next_spatial)) return bad("next_spatial is NULL or not 4-byte aligned");
+        // (Fn = 0: nothing is read through them, so NULL is accepted, as susnet_spatial_forward does; a pointer that is given is still checked)
+        if ((!io->non_spatial && Fn > 0) || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
+        if ((!io->next_non_spatial && Fn > 0) || misaligned(io->next_non_spatial)) return bad("next_non_spatial is NULL or not 4-byte aligned");
+    } else if (io->n > 0 && !io->indices) return bad("indices is NULL");
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = io->team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
+        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
+        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
+        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
+        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(io->workspace);
+    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
+    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
+    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    const auto at = [&](uint64_t off) { return reinterpret_cast<float *>(ws + off); };
+    const SpTrainWs w{at(pl.off_X), at(pl.off_Xt), at(pl.off_act), at(pl.off_dact), at(pl.off_dX), at(pl.off_tact), at(pl.off_hs), at(pl.off_ds), at(pl.off_zs)};
+    SpTrainBatch b{};
+    b.spatial = io->spatial, b.next_spatial = io->next_spatial, b.non_spatial = io->non_spatial, b.next_non_spatial = io->next_non_spatial;
+    for (int d = 0; d < 3; d++) b.sp_stride[d] = io->spatial_stride[d], b.ns_stride[d] = Fn > 0 ? io->non_spatial_stride[d] : 0;
+    b.actions = io->actions, b.rewards = io->rewards, b.dones = io->dones, b.imposters = io->imposters, b.idx = io->indices;
+    b.max_size = io->max_size, b.n = io->n, b.A = (int32_t)env->c.A, b.n_imp = (int32_t)env->c.n_imp;
+    SpTrainNet *nets = reinterpret_cast<SpTrainNet *>(ws + pl.off_nets);
+    HIP_TRY(sp_train_select_launch(b, pl.net[0], pl.net[1], nets, lists, counts, gacc[0], gacc[1], io->losses_out, st));
+    if (io->n == 0) return SUSNET_OK;
+    for (int agent = 0; agent < env->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            const susnet_dqn_team &T = io->team[tm];
+            if (!T.enabled) continue;
+            HIP_TRY(sp_train_update_launch(b, nets + tm, w, T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, T.step,
+                                           (int)pl.G, (int)pl.Gconv, st));
             hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
                                partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
             HIP_TRY(hipGetLastError());

@@ -1,0 +1,88 @@
+// susnet_spatial_train.h -- susnet_spatial_train_step: the DQN learner's train step (DQNTeamTrainer.train_step, src/train.py:50-149;
+// susnet_train.h has the reference notes) for the reference SpatialDQN (src/models/dqn.py:205-301) -- the network susnet_spatial_forward
+// computes (susnet_spatial.h) -- in training mode without dropout.  The kernels: inst_spatial_train.hip.
+//
+// Per train step, on one stream, no host synchronisation, no atomics:
+//   k_sp_train_select    ONE workgroup: tr_select with batch positions in the lists, as k_mlp_train_select; it also copies the two teams'
+//                        network descriptions (SpTrainNet) into the workspace, where the update's kernels read them.
+//   per (agent, enabled team) update, four launches:
+//   k_sp_train_conv      vector ALU, a workgroup per image (an image = one window step of one row of the update's list; grid-stride over
+//                        2 count T jobs: the online network on the states, then the target network on the next states).  A layer is a loop
+//                        over its outputs, one fmaf chain per output starting as the bias over (c_in, ky, kx) ascending; the online
+//                        network's layer outputs go to the workspace (the backward pass reads them), the target network's ping-pong in the
+//                        workgroup's own slice; the last layer writes the RNN input row, the step's non-spatial features behind it.
+//   k_sp_train_rnn       v_mfma_f32_32x32x2_f32 through susnet_train_core.h's tr_mfma, a workgroup walks tiles of 32 list rows.  The
+//                        recurrence of the target network, its head, max over actions -> y; the online recurrence (every h[l][t] kept in the
+//                        workgroup's slice of the workspace as [unit][32]) and head (pre-activations kept as the dense learner keeps them);
+//                        2 (Q - y) / count back through the head (the dense learner's scheme on the same stride-33 LDS buffers), then
+//                        through time: dz[l][t] = (1 - h^2) (W_ih[l+1]^T dz[l+1][t] + W_hh[l]^T dz[l][t+1] (+ the head's at the top, last
+//                        step)) into a second slice; then W_ih[0]^T dz[0][t] -- its convolution columns -- into the workspace for the
+//                        convolutions' backward, and the weight gradients as products over K = T x 32 (dW_hh: (T - 1) x 32), added into the
+//                        workgroup's partial by read-modify-write, one writer per word (the first tile of a workgroup stores).
+//   k_sp_train_conv_bwd  vector ALU, the same grid: per image of the workgroup's share (image i of workgroup i mod G) the ReLU gate
+//                        (output > 0) and the transposed convolution layer by layer, top down, the gated gradients kept in the workspace;
+//                        then every weight (a thread per weight) sums gradient x input over the share's images and pixels in ascending
+//                        order and is stored once.  A workgroup without an image stores zeros.
+//   k_train_adam         susnet_train.h's, as it is (susnet_capi_train.hip launches it).
+// The two gradient kernels write disjoint parts of the same partial: [0, oWih[0]) the convolutions, [oWih[0], P] the rest and the loss sum.
+// Grid: G = min(SUSNET_SPATIAL_TRAIN_MAX_GRID, n T, 64 MiB / (4 Pp)) workgroups, at least 1, for both.
+// Data a workgroup hands from one thread to another through global memory is separated by a workgroup barrier (release / acquire at
+// workgroup scope); nothing is ever read that another workgroup of the same launch wrote.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/susnet.h"
+#include "susnet_mlp_train.h"
+
+namespace susnet {
+
+constexpr int kStConvThreads = 256;
+constexpr int kStMaxGrid = SUSNET_SPATIAL_TRAIN_MAX_GRID;
+constexpr int kStConvGrid = 1024;
+
+// one team's network: shapes and float offsets into the flat parameter buffer (SpatialDQN.parameters() order)
+struct SpTrainNet {
+    int32_t T, N, C, Fn, n_conv, k, L, H;
+    int32_t R, Rc;                  // the RNN's input width; its convolution columns (R - Fn)
+    int32_t size[5], ch[5], sz[5];  // per activation level 0 .. n_conv: image size, channels, floats (ch * size^2)
+    int32_t stride[4], pad[4], dil[4];
+    int32_t oCW[4], oCB[4];
+    int32_t oWih[4], oWhh[4], oBih[4], oBhh[4];
+    MlpTrainNet head;               // nl, d, oW / oB / oA (offsets into the SAME flat buffer), zo, Z
+    int32_t aoff[4], asz;           // saved output of conv layer l < n_conv - 1 within an image's record; floats per record
+    int32_t maxsz;                  // the widest activation level 1 .. n_conv
+    int32_t P, Pp;
+};
+
+struct SpTrainBatch {
+    const float *spatial, *next_spatial, *non_spatial, *next_non_spatial;
+    int64_t sp_stride[3], ns_stride[3];
+    const int64_t *actions;
+    const float *rewards;
+    const uint8_t *dones;
+    const int16_t *imposters;
+    const int64_t *idx;
+    int64_t max_size, n;
+    int32_t A, n_imp;
+};
+
+// the workspace behind tr_workspace_layout's part
+struct SpTrainWs {
+    float *X, *Xt;       // [n T][R]: RNN input rows of the online / target network, by list slot
+    float *act, *dact;   // [n T][asz]: the online convolutions' saved outputs, and their gated gradients
+    float *dX;           // [n T][Rc]: gradient of the last convolution's output
+    float *tact;         // [conv grid][2 maxsz]: the target network's ping-pong
+    float *hs, *ds;      // [G][L T H 32]: h and dz of the recurrence
+    float *zs;           // [G][head.Z]
+};
+
+// (nets: device, two SpTrainNet -- the select kernel writes them, the update's kernels read their team's: `net` below is a DEVICE pointer)
+hipError_t sp_train_select_launch(const SpTrainBatch &b, const SpTrainNet &net0, const SpTrainNet &net1, SpTrainNet *nets, int32_t *lists,
+                                  int32_t *counts, float *gacc0, float *gacc1, float *losses, hipStream_t st);
+hipError_t sp_train_update_launch(const SpTrainBatch &b, const SpTrainNet *net, const SpTrainWs &ws, const float *prm, const float *tgt,
+                                  const int32_t *lists, const int32_t *counts, int agent, int team, float gamma, float *partial, float *step, int G,
+                                  int Gconv, hipStream_t st);
+
+} // namespace susnet

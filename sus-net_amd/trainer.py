@@ -11,8 +11,13 @@ from a ``DeviceReplayBuffer`` (``ReplayBuffer.sample``, src/replay_memory.py:75-
   gathered and featurized as ``n * T`` rows (the FLAT featurizer kernel) into reused buffers -- ``[n * T, F]`` IS the ``[n][T * F]``
   layout the step reads --, then one call: the same launches per update, no host synchronisation.
   There is no packed image: a ``PolicyRollout(dense=True)`` reads the parameters in place and follows the step without a refresh.
-* torch path (``torch_train_step``): the same algorithm in torch ops for anything else -- ``SpatialDQN``, other layer stacks, longer
-  windows, CPU tensors.
+* spatial HIP path (``susnet_spatial_train_step``, csrc/susnet_spatial_train.h; opt-in: ``DeviceDQNTeamTrainer(..., spatial=True)``):
+  reference ``SpatialDQN``s (CNN, tanh ``nn.RNN``, PReLU head) within ``susnet_spatial_forward``'s bounds on a ``GlobalFeaturizer`` or
+  ``PerspectiveFeaturizer``, one imposter, no dropout between RNN layers.  The batch's windows and next windows are gathered and featurized
+  into reused buffers, then one call: 1 + 4 launches per (agent, trained team), no host synchronisation.  A ``SpatialQNet`` of the same
+  model reads the parameters in place and follows the step without a refresh.
+* torch path (``torch_train_step``): the same algorithm in torch ops for anything else -- a ``SpatialDQN`` without ``spatial=True``, other
+  layer stacks, longer windows, CPU tensors.
 
 The parameters of each trained team live in ONE flat float32 buffer in ``model.parameters()`` order, and the modules' parameters are
 views into it: after a step the ``nn.Module`` holds the new values (``dump_to_checkpoint`` works), whichever path ran.
@@ -27,7 +32,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
-from .policy import MLP, RandomEquiprobable, _weights_version, dense_stack, linear_prelu_stack
+from .policy import MLP, RandomEquiprobable, SpatialQNet, _spatial_stack, _weights_version, dense_stack, linear_prelu_stack
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults (train.py:35-37 passes only lr)
 
@@ -86,11 +91,13 @@ class DeviceDQNTeamTrainer:
     ``components`` by default; a ``SpatialDQN`` needs a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of the same env).
     ``dense=True`` (opt-in): what ``susnet_dqn_train_step`` does not serve goes to ``susnet_mlp_train_step`` where that serves it
     (``uses_dense``), before the torch path.  ``sequence_length``: the window length T the trained networks read (their input is
-    ``T * F`` wide); None (default): T is taken from the networks' input width, ``dims[0] / F``."""
+    ``T * F`` wide); None (default): T is taken from the networks' input width, ``dims[0] / F``.
+    ``spatial=True`` (opt-in): trained ``SpatialDQN``s that ``susnet_spatial_train_step`` serves, with a Global or Perspective
+    ``featurizer``, take that step (``uses_spatial``) -- after ``uses_hip`` and ``uses_dense``, before the torch path."""
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module], components: Sequence[str], lr: float, gamma: float,
                  train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None, dense: bool = False,
-                 sequence_length: Optional[int] = None):
+                 sequence_length: Optional[int] = None, spatial: bool = False):
         if env.n_imposters >= 2:
             raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
                              "(src/train.py:83) has n_imposters * N entries")
@@ -137,6 +144,11 @@ class DeviceDQNTeamTrainer:
                       and all(c in L.FLAT_COMPONENTS for c in self.components)
                       and all(d is not None for d, tr in zip(self._dense_dims, self.trained) if tr) and self._dense_served())
         self._dense_bufs = None  # (n, gathered states, gathered next states, spec + rows of states, spec + rows of next states)
+        # the spatial step: each trained team's SpatialDQN as susnet_spatial_train_step reads it
+        self._spatial_nets = [self._spatial_net(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self.spatial = (bool(spatial) and self.device.type == "cuda" and any(self.trained) and self._spatial_featurizer() is not None
+                        and all(d is not None for d, tr in zip(self._spatial_nets, self.trained) if tr) and self._spatial_served())
+        self._spatial_bufs = None  # (n, T, gathered states, gathered next states, obs of states, obs of next states, Global non-spatial rows x 2)
 
     # ---- configuration ----
     @staticmethod
@@ -230,6 +242,75 @@ class DeviceDQNTeamTrainer:
         nbytes = C.c_uint64()
         return self.env.lib.susnet_mlp_train_workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
 
+    # ---- the spatial step's configuration ----
+    def _spatial_featurizer(self):
+        """"global" / "persp" for a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of this env, else None."""
+        from .features import GlobalFeaturizer, PerspectiveFeaturizer
+
+        f = self._featurizer
+        if isinstance(f, (GlobalFeaturizer, PerspectiveFeaturizer)) and f.env is self.env:
+            return "global" if isinstance(f, GlobalFeaturizer) else "persp"
+        return None
+
+    def _spatial_net(self, model):
+        """What ``susnet_spatial_train_step`` needs to know of a ``SpatialDQN`` that ``SpatialQNet`` serves and whose training-mode forward
+        the kernels compute (no dropout between RNN layers), or None."""
+        stack = _spatial_stack(model)
+        if stack is None or SpatialQNet(self.env, model) is None:
+            return None
+        rnn = stack["rnn"]
+        if rnn.dropout > 0 and rnn.num_layers > 1:
+            return None  # (nn.RNN drops out between layers in training mode: the kernels do not)
+        convs = stack["convs"]
+        # parameters() order must be the flat layout the kernels assume: convolutions, RNN layer by layer, head
+        names = [n for n, _ in model.named_parameters()]
+        want = [f"cnn.model.{2 * l}.{w}" for l in range(len(convs)) for w in ("weight", "bias")]
+        want += [f"rnn.model.{w}_l{l}" for l in range(rnn.num_layers) for w in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        if names[:len(want)] != want or not all(n.startswith("prediction_head.") for n in names[len(want):]):
+            return None
+        cfg = model.config
+        return dict(N=int(cfg["input_image_size"]), C=convs[0].in_channels, Fn=int(cfg["non_spatial_input_size"]), k=stack["k"],
+                    convs=[(m.out_channels, m.stride[0], m.padding[0], m.dilation[0]) for m in convs], layers=rnn.num_layers,
+                    hidden=rnn.hidden_size, dims=stack["dims"])
+
+    def _spatial_io(self, T: int) -> "L.SpatialTrainIO":
+        io = L.SpatialTrainIO()
+        io.gamma = self.gamma
+        for t in range(2):
+            d = self._spatial_nets[t]
+            if not self.trained[t] or d is None:
+                continue
+            self._fill_team(io.team[t], t, d["dims"])
+            net = io.net[t]
+            net.T, net.N, net.C, net.Fn, net.n_conv, net.k = T, d["N"], d["C"], d["Fn"], len(d["convs"]), d["k"]
+            for l, (co, st, pad, dil) in enumerate(d["convs"]):
+                net.conv_out[l], net.conv_stride[l], net.conv_padding[l], net.conv_dilation[l] = co, st, pad, dil
+            net.rnn_layers, net.rnn_hidden = d["layers"], d["hidden"]
+        return io
+
+    def _spatial_served(self) -> bool:
+        env, A = self.env, self.env.n_agents
+        _, planes, non_spatial = env._make_obs(self._featurizer.config, 1, rows=1)
+        if non_spatial is None:
+            return False
+        Fn = non_spatial.shape[-1] + (A if self._spatial_featurizer() == "global" else 0)
+        n_actions = (env.n_imposter_actions, env.n_crew_actions)
+        for t in range(2):
+            d = self._spatial_nets[t]
+            if self.trained[t] and (d["C"], d["N"], d["Fn"], d["dims"][-1]) != (planes.shape[-3], planes.shape[-1], Fn, n_actions[t]):
+                return False  # the networks do not read this featurizer's tensors
+        io = self._spatial_io(1)
+        io.max_size, io.n = 1, 1
+        nbytes = C.c_uint64()
+        return env.lib.susnet_spatial_train_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)) == 0
+
+    def uses_spatial(self, ring) -> bool:
+        """Whether ``ring`` is trained on by ``susnet_spatial_train_step``: a ``spatial=True`` trainer of served ``SpatialDQN``s with a Global
+        or Perspective featurizer, windows of at most ``SPATIAL_MAX_T`` states, cuda tensors -- and neither ``uses_hip`` nor ``uses_dense``
+        holds (those paths go first)."""
+        return (self.spatial and not self.uses_hip(ring) and not self.uses_dense(ring) and 1 <= ring.trajectory_size <= L.SPATIAL_MAX_T
+                and ring.states.device == self.device)
+
     # ---- the train step ----
     def train_step(self, ring, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """Sample ``batch_size`` ring rows uniformly with replacement (replay_memory.py:89) and take one train step.  Returns the
@@ -244,6 +325,8 @@ class DeviceDQNTeamTrainer:
             return self._hip_step(ring, idx)
         if self.uses_dense(ring):
             return self._dense_step(ring, idx)
+        if self.uses_spatial(ring):
+            return self._spatial_step(ring, idx)
         return self._torch_step(ring, idx)
 
     def _workspace_and_losses(self, io, workspace_bytes) -> None:
@@ -307,6 +390,62 @@ class DeviceDQNTeamTrainer:
             L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
         if self.policy is not None and any(self._policy_image(t) is not None for t in range(2)):
             self.policy.refresh_weights(force=True)  # (a fused image of these weights: only where the fused step was switched off by hand)
+        return self._losses.clone()
+
+    def _spatial_step(self, ring, idx):
+        """Gather the batch's ``[n, T, S]`` windows and next windows and featurize them (``n * T`` rows, the featurizer's kernel) into reused
+        buffers, then ``susnet_spatial_train_step`` on the planes where they lie: the Perspective featurizer's per-agent views in place, the
+        Global featurizer's shared planes with an agent stride of 0 and its non-spatial rows with every agent's one-hot appended
+        (``[n, T, A, Fn]``, as ``WindowedPolicyRollout.kernel_inputs`` builds them).  Nothing waits on the host (with ``env.check_errors``
+        the featurizer's row check is polled)."""
+        env, n, T, A = self.env, int(idx.numel()), ring.trajectory_size, self.env.n_agents
+        kind = self._spatial_featurizer()
+        for t in range(2):
+            self._state_to_flat(t)
+        io = self._spatial_io(T)
+        if n > 0:
+            if self._spatial_bufs is None or self._spatial_bufs[:2] != (n, T):
+                oc = self._featurizer.config
+                obs, next_obs = env._make_obs(oc, 1, rows=n * T), env._make_obs(oc, 1, rows=n * T)
+                glob = [None, None]
+                if kind == "global":
+                    Fn = obs[2].shape[-1] + A
+                    glob = [torch.empty(n, T, A, Fn, dtype=torch.float32, device=self.device) for _ in range(2)]
+                    for g in glob:  # (the one-hot columns never change)
+                        g[..., Fn - A:] = torch.eye(A, dtype=torch.float32, device=self.device)
+                self._spatial_bufs = (n, T, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
+                                      torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
+                                      obs, next_obs, glob[0], glob[1])
+            _, _, rows, next_rows, (spec, planes, non), (next_spec, next_planes, next_non), g, next_g = self._spatial_bufs
+            torch.index_select(ring.states, 0, idx, out=rows)
+            torch.index_select(ring.next_states, 0, idx, out=next_rows)
+            img = planes[0].numel() if kind == "global" else planes[0, 0].numel()  # floats of one [C, N, N] image
+            if kind == "global":  # planes [n T, C, N, N], shared by the agents; non-spatial rows built below
+                sp, ns = (T * img, 0, img), (g.stride(0), g.stride(2), g.stride(1))
+                non_ptr, next_non_ptr = g.data_ptr(), next_g.data_ptr()
+            else:                 # planes [n T, A, C, N, N], non-spatial [n T, A, F2]
+                f2 = non.shape[-1]
+                sp, ns = (T * A * img, img, A * img), (T * A * f2, f2, A * f2)
+                non_ptr, next_non_ptr = non.data_ptr(), next_non.data_ptr()
+            io.spatial, io.next_spatial, io.non_spatial, io.next_non_spatial = planes.data_ptr(), next_planes.data_ptr(), non_ptr, next_non_ptr
+            for d in range(3):
+                io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
+        io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
+        io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
+        io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
+        self._workspace_and_losses(io, env.lib.susnet_spatial_train_workspace_bytes)
+        with torch.cuda.device(self.device):
+            if n > 0:
+                dt = env._ROW_DTYPES[rows.dtype]
+                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), dt, n * T, C.byref(spec), env._stream()))
+                L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n * T, C.byref(next_spec), env._stream()))
+                if env.check_errors:
+                    env.poll_errors()
+                if kind == "global":
+                    base = non.shape[-1]
+                    g[..., :base] = non.view(n, T, 1, base)
+                    next_g[..., :base] = next_non.view(n, T, 1, base)
+            L.check(env.lib.susnet_spatial_train_step(env._h, C.byref(io), env._stream()))
         return self._losses.clone()
 
     def _sync_policy_version(self):
