@@ -12,10 +12,12 @@
  *   susnet_reset           FourRoomEnv.reset               src/environment/base.py:251-324 (tagging.py:62-101)
  *   susnet_sample_actions  FourRoomEnv.sample_actions      src/environment/base.py:326-330
  *   susnet_policy_actions  run_game's acting step          src/visualize.py:547-562 (train.py:355-381, epsilon = 0)
+ *   susnet_agent_policy_actions  train()'s acting step with one Q row per agent  src/train.py:351-381 (SpatialDQN on each agent's view)
  *   susnet_qnet_*          MLP.forward on the flat features src/models/dqn.py:72-108, 322-329
  *   susnet_mlp_forward     MLP.forward of any served layer stack on caller-supplied feature rows  src/models/dqn.py:72-108, 322-329
  *   susnet_spatial_forward SpatialDQN.forward (eval mode) on the planes / perspective features     src/models/dqn.py:141-301
  *   susnet_window_push     the acting loop's state window, one tick on (as feature rows)  src/train.py:318-322, 388-389, 441-445
+ *   susnet_state_window_push  the acting loop's RAW state window [B][T][S] uint8, one tick on, in place  src/train.py:388-389, 441-445
  *   susnet_policy_step     argmax per team + env.step        src/visualize.py:547-582
  *   susnet_step            FourRoomEnv.step                src/environment/base.py:332-407 (tagging.py:120-235)
  *                          + _agent_step 462-533, check_win_condition 409-460 (pred_prey.py:78-99),
@@ -400,6 +402,20 @@ typedef struct susnet_policy_opts {
 int susnet_policy_actions(susnet_env *env, const float *q_imposter, const float *q_crew, const susnet_policy_opts *opts /* or NULL */,
                           void *actions_out, int32_t dtype, int32_t layout, void *stream);
 
+/* susnet_policy_actions with one Q row per AGENT -- the acting step of train() for a network that reads each agent's own view
+ * (src/train.py:351-381 with a SpatialDQN: the Perspective featurizer gives every agent its view, the Global one its one-hot):
+ *   actions[b][i] = argmax_k q_imposter[b][i][k]   if agent i is an imposter of environment b
+ *                 = argmax_k q_crew[b][i][k]       otherwise
+ * q_imposter / q_crew: float32 [B][A][n_actions_imposter] / [B][A][n_actions_crew], contiguous -- the [B * A][n] rows
+ * susnet_spatial_forward writes with agents = A; the first maximum wins.  Everything else is susnet_policy_actions': the roles and alive
+ * words, the action stream for the crew's draws and the sampled index, the exploration stream for u <= epsilon (draws for every agent),
+ * mask_dead, q_crew = NULL = a random crew (PHILOX handles only), no draw at all with both networks and epsilon = 0 (TAPE handles are
+ * served there).  With every agent's row equal to its environment's the two calls return the same bytes.  No limit on the number of
+ * actions (rows are n_actions_* of susnet_get_layout long).  SUSNET_E_INVALID, naming the field, before any launch: NULL q_imposter /
+ * actions_out, a dtype / layout outside the enums, a crew network in opts, q_crew = NULL or epsilon > 0 on a handle that is not PHILOX. */
+int susnet_agent_policy_actions(susnet_env *env, const float *q_imposter, const float *q_crew, const susnet_policy_opts *opts /* or NULL */,
+                                void *actions_out, int32_t dtype, int32_t layout, void *stream);
+
 /* The policy loop's Q-network -- the reference's MLP (src/models/dqn.py:72-108: make_mlp 322-329, Linear + nn.PReLU() with ONE
  * slope per layer, no activation after the last Linear) on the FlatFeaturizer observation of the handle's CURRENT environments
  * (model_ready.py:356-367) -- as one kernel: MLP.forward(spatial, env.obs) without the observation or any activation ever
@@ -542,6 +558,18 @@ typedef struct susnet_window_io {
     int64_t n;
 } susnet_window_io;
 int susnet_window_push(susnet_env *env, const susnet_window_io *io, void *stream);
+
+/* The acting loop's RAW state window (src/train.py:388-389, 441-445), one tick on, IN PLACE: window is device uint8 [n][T][S], oldest
+ * state first -- the carried window susnet_ring_append keeps (susnet_ring_io.window).  obs / done / truncated: ONE slot of the replay feed
+ * as the stepping kernel wrote it ([n][S] uint8: the state after the tick, after the auto-reset where the episode ended; [n] flags), read
+ * in place.  Per environment b:
+ *     done[b] | truncated[b]   window[b] = obs[b] repeated T times      (train.py:441-445)
+ *     otherwise                window[b] = window[b][1:] ++ obs[b]      (train.py:388-389: np.roll(-1), the last slot is the new state)
+ * This is susnet_ring_append's own window kernel launched for one tick, so an acting window moved by this call and the ring's carried
+ * window follow the same code.  Served: T in 1 .. 8, S = obs_raw_size of the handle, n = its batch, all four pointers non-NULL; anything
+ * else is SUSNET_E_INVALID naming the field, before the launch.  No environment state is read: the handle need not have its state bound. */
+int susnet_state_window_push(susnet_env *env, uint8_t *window, int32_t T, int32_t S, int64_t n, const uint8_t *obs, const uint8_t *done,
+                             const uint8_t *truncated, void *stream);
 
 int susnet_step(susnet_env *env, const susnet_step_io *io, void *stream);
 /* susnet_policy_actions and susnet_step in ONE launch -- a tick of the acting loop (visualize.py:547-582: argmax per team, env.step):

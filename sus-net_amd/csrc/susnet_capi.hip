@@ -137,26 +137,6 @@ __global__ __launch_bounds__(kBlock) void k_sample_philox(Consts c, State s, voi
 // like torch.argmax), or -- q_crew == NULL -- the crew's draw from the action stream.  The draws are made for EVERY agent and
 // the imposters' are overwritten: the digits of a word depend on the draws before them, so the crew's values are exactly the
 // ones susnet_sample_actions returns.
-struct PolicyActionSink {
-    void *out;
-    int32_t dtype;
-    int64_t sa, k0;
-    uint32_t roles, a_imp, a_crew; // a_crew = ~0u: keep the sampled index
-    float eps;                     // epsilon-greedy / dead mask: as PolicyStepSink (susnet_kernels.h)
-    uint32_t alive, mask_dead;
-    const PhiloxRng *rng;
-    ActionStream *xs;
-    uint64_t xbase;
-    __device__ __forceinline__ void set_act(int i, uint32_t sampled) const {
-        uint32_t a = ((roles >> i) & 1u) ? a_imp : (a_crew != ~0u ? a_crew : sampled);
-        if (eps > 0.0f) {
-            const float u = (float)(xs->word(*rng, xbase + (uint64_t)i) >> 8) * 5.9604644775390625e-08f;
-            a = u <= eps ? sampled : a;
-        }
-        if (mask_dead && !((alive >> i) & 1u)) a = 0u;
-        store_action(out, dtype, (int64_t)i * sa + k0, a);
-    }
-};
 __device__ __forceinline__ uint32_t argmax_row(const float *q, int n) {
     uint32_t best = 0;
     float hi = q[0];
@@ -166,13 +146,42 @@ __device__ __forceinline__ uint32_t argmax_row(const float *q, int n) {
     }
     return best;
 }
-__global__ __launch_bounds__(kBlock) void k_policy_actions(Consts c, State s, const float *q_imp, const float *q_crew, int n_imp_actions,
-                                                           int n_crew_actions, void *out, int32_t dtype, int64_t sa, int64_t sb, uint64_t tick, float epsilon,
-                                                           int mask_dead) {
-    using S = GenericSpec;
-    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; // (< Bp: rows are padded, every lane may load its roles)
-    uint32_t roles = (1u << c.n_imp) - 1u; // fixed roles: the first n_imposters agents (base.py:286-290 without the shuffle)
-    uint32_t alive = ~0u;
+// PER_AGENT (susnet_agent_policy_actions): the greedy index is the argmax of the AGENT's own row of its team's [B][A][n] rows, taken where
+// the agent's action is set; everything else is the per-environment form's
+template <bool PER_AGENT>
+struct PolicyActionSinkT {
+    void *out;
+    int32_t dtype;
+    int64_t sa, k0;
+    uint32_t roles, a_imp, a_crew; // a_crew = ~0u: keep the sampled index
+    float eps;                     // epsilon-greedy / dead mask: as PolicyStepSink (susnet_kernels.h)
+    uint32_t alive, mask_dead;
+    const PhiloxRng *rng;
+    ActionStream *xs;
+    uint64_t xbase;
+    const float *q_imp, *q_crew; // PER_AGENT: the environment's [A][n_imp] / [A][n_crew] rows (q_crew = nullptr: keep the sampled index)
+    int n_imp, n_crew;
+    __device__ __forceinline__ void set_act(int i, uint32_t sampled) const {
+        uint32_t a;
+        if constexpr (PER_AGENT) {
+            if ((roles >> i) & 1u) a = argmax_row(q_imp + (size_t)i * n_imp, n_imp);
+            else a = q_crew ? argmax_row(q_crew + (size_t)i * n_crew, n_crew) : sampled;
+        } else {
+            a = ((roles >> i) & 1u) ? a_imp : (a_crew != ~0u ? a_crew : sampled);
+        }
+        if (eps > 0.0f) {
+            const float u = (float)(xs->word(*rng, xbase + (uint64_t)i) >> 8) * 5.9604644775390625e-08f;
+            a = u <= eps ? sampled : a;
+        }
+        if (mask_dead && !((alive >> i) & 1u)) a = 0u;
+        store_action(out, dtype, (int64_t)i * sa + k0, a);
+    }
+};
+using PolicyActionSink = PolicyActionSinkT<false>;
+// roles and alive bits of environment b (every lane of the padded row may load)
+__device__ __forceinline__ void policy_roles_alive(const Consts &c, const State &s, int64_t b, int mask_dead, uint32_t &roles, uint32_t &alive) {
+    roles = (1u << c.n_imp) - 1u; // fixed roles: the first n_imposters agents (base.py:286-290 without the shuffle)
+    alive = ~0u;
     if (c.shuffle_imp || mask_dead) {
         uint32_t w[SUSNET_MAX_AGENTS];
 #pragma unroll
@@ -186,6 +195,14 @@ __global__ __launch_bounds__(kBlock) void k_policy_actions(Consts c, State s, co
         }
         if (c.shuffle_imp) roles = r2;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_policy_actions(Consts c, State s, const float *q_imp, const float *q_crew, int n_imp_actions,
+                                                           int n_crew_actions, void *out, int32_t dtype, int64_t sa, int64_t sb, uint64_t tick, float epsilon,
+                                                           int mask_dead) {
+    using S = GenericSpec;
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; // (< Bp: rows are padded, every lane may load its roles)
+    uint32_t roles, alive;
+    policy_roles_alive(c, s, b, mask_dead, roles, alive);
     uint64_t tick_word = tick;
     if (c.dev_tick) tick_word = s.tickw[b];
     if (b >= c.B) return;
@@ -197,7 +214,36 @@ __global__ __launch_bounds__(kBlock) void k_policy_actions(Consts c, State s, co
     const uint64_t tk = uniform64(tick_word);
     PolicyActionSink sink = {out, dtype, sa, b * sb, roles, argmax_row(q_imp + b * n_imp_actions, n_imp_actions),
                              q_crew ? argmax_row(q_crew + b * n_crew_actions, n_crew_actions) : ~0u, epsilon, alive, (uint32_t)mask_dead, &rng, &xs,
-                             tk * (uint64_t)c.A};
+                             tk * (uint64_t)c.A, nullptr, nullptr, 0, 0};
+    if (q_crew && !(epsilon > 0.0f)) {
+        for (int i = 0; i < c.A; i++) sink.set_act(i, 0u);
+        return;
+    }
+    Env e = {};
+    e.imp = roles;
+    sample_actions_env<S>(c, sink, e, rng, as, tk);
+}
+// susnet_agent_policy_actions: k_policy_actions with one Q row per (environment, agent) -- q_imp [B][A][n_imp], q_crew [B][A][n_crew] or
+// nullptr; same roles / alive words, same two streams, same early return
+__global__ __launch_bounds__(kBlock) void k_agent_policy_actions(Consts c, State s, const float *q_imp, const float *q_crew, int n_imp_actions,
+                                                                 int n_crew_actions, void *out, int32_t dtype, int64_t sa, int64_t sb, uint64_t tick,
+                                                                 float epsilon, int mask_dead) {
+    using S = GenericSpec;
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint32_t roles, alive;
+    policy_roles_alive(c, s, b, mask_dead, roles, alive);
+    uint64_t tick_word = tick;
+    if (c.dev_tick) tick_word = s.tickw[b];
+    if (b >= c.B) return; // (the Q rows exist for b < B only)
+    PhiloxRng rng;
+    rng.init(c.seed, c.env_id_base + (uint64_t)b, 0ull);
+    ActionStream as, xs;
+    as.init();
+    xs.init(kExploreStreamTag);
+    const uint64_t tk = uniform64(tick_word);
+    PolicyActionSinkT<true> sink = {out, dtype, sa, b * sb, roles, 0u, 0u, epsilon, alive, (uint32_t)mask_dead, &rng, &xs, tk * (uint64_t)c.A,
+                                    q_imp + (size_t)b * c.A * n_imp_actions, q_crew ? q_crew + (size_t)b * c.A * n_crew_actions : nullptr,
+                                    n_imp_actions, n_crew_actions};
     if (q_crew && !(epsilon > 0.0f)) {
         for (int i = 0; i < c.A; i++) sink.set_act(i, 0u);
         return;
@@ -854,6 +900,31 @@ extern "C" int susnet_policy_actions(susnet_env *env, const float *q_imposter, c
     int64_t sa, sb;
     if (int rc = strides_for(env, layout, sa, sb)) return rc;
     hipLaunchKernelGGL(k_policy_actions, grid_for(env), dim3(kBlock), 0, static_cast<hipStream_t>(stream), env->c, env->s, q_imposter, q_crew,
+                       (int)env->layout.n_actions_imposter, (int)env->layout.n_actions_crew, actions_out, dtype, sa, sb, env->ticks, eps, mask_dead);
+    HIP_TRY(hipGetLastError());
+    return SUSNET_OK;
+}
+
+extern "C" int susnet_agent_policy_actions(susnet_env *env, const float *q_imposter, const float *q_crew, const susnet_policy_opts *opts, void *actions_out,
+                                           int32_t dtype, int32_t layout, void *stream) {
+    // (the argument checks come before the handle's: they need no bound state)
+    if (!env) return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: null env");
+    if (!q_imposter) return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: null q_imposter");
+    if (!actions_out) return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: null actions_out");
+    if (dtype != SUSNET_U8 && dtype != SUSNET_I32 && dtype != SUSNET_I64)
+        return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: actions dtype must be U8/I32/I64, got dtype = " + std::to_string(dtype));
+    if (layout != SUSNET_LAYOUT_AB && layout != SUSNET_LAYOUT_BA)
+        return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: unknown layout = " + std::to_string(layout));
+    if (int rc = no_crew_network(opts, "susnet_agent_policy_actions")) return rc;
+    if (!q_crew && env->cfg.rng_mode != SUSNET_RNG_PHILOX)
+        return fail(SUSNET_E_INVALID, "susnet_agent_policy_actions: a random crew (q_crew = NULL) draws from the production stream: PHILOX handles only");
+    float eps;
+    int mask_dead;
+    if (int rc = policy_opts(env, opts, eps, mask_dead)) return rc;
+    if (int rc = check_bound(env)) return rc;
+    int64_t sa, sb;
+    if (int rc = strides_for(env, layout, sa, sb)) return rc;
+    hipLaunchKernelGGL(k_agent_policy_actions, grid_for(env), dim3(kBlock), 0, static_cast<hipStream_t>(stream), env->c, env->s, q_imposter, q_crew,
                        (int)env->layout.n_actions_imposter, (int)env->layout.n_actions_crew, actions_out, dtype, sa, sb, env->ticks, eps, mask_dead);
     HIP_TRY(hipGetLastError());
     return SUSNET_OK;

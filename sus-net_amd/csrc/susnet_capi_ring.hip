@@ -595,3 +595,32 @@ extern "C" int susnet_ring_append(susnet_env *env, const susnet_ring_io *io, voi
     HIP_TRY(hipGetLastError());
     return SUSNET_OK;
 }
+
+// susnet_state_window_push: the acting loop's raw window one tick on, in place -- k_ring_window<false> for ONE tick on a feed slot's
+// pointers (it reads of RingArgs only io.window / obs / done / truncated / trajectory_size / n_ticks, B and S)
+extern "C" int susnet_state_window_push(susnet_env *env, uint8_t *window, int32_t T, int32_t S, int64_t n, const uint8_t *obs, const uint8_t *done,
+                                        const uint8_t *truncated, void *stream) {
+    const std::string who = "susnet_state_window_push: ";
+    if (!env) return fail(SUSNET_E_INVALID, who + "null env");
+    if (T < 1 || T > 8) return fail(SUSNET_E_INVALID, who + "T = " + std::to_string(T) + ": windows of 1 .. 8 states are served");
+    if (S != env->layout.obs_raw_size)
+        return fail(SUSNET_E_INVALID, who + "S = " + std::to_string(S) + ": the handle's flattened state has " + std::to_string(env->layout.obs_raw_size) + " bytes (obs_raw_size)");
+    if (n != env->c.B) return fail(SUSNET_E_INVALID, who + "n = " + std::to_string(n) + ": one window per environment of the handle (batch = " + std::to_string(env->c.B) + ")");
+    if (!window) return fail(SUSNET_E_INVALID, who + "null window");
+    if (!obs) return fail(SUSNET_E_INVALID, who + "null obs");
+    if (!done) return fail(SUSNET_E_INVALID, who + "null done");
+    if (!truncated) return fail(SUSNET_E_INVALID, who + "null truncated");
+    RingArgs r = {};
+    r.io.window = window;
+    r.io.obs = obs;
+    r.io.done = done;
+    r.io.truncated = truncated;
+    r.io.trajectory_size = T;
+    r.io.n_ticks = 1;
+    r.B = n;
+    r.A = env->c.A;
+    r.S = S;
+    hipLaunchKernelGGL(k_ring_window<false>, dim3((unsigned)((r.B + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), r);
+    HIP_TRY(hipGetLastError());
+    return SUSNET_OK;
+}

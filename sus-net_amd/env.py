@@ -528,6 +528,26 @@ class BatchedFourRoomEnv:
                                                    self._policy_opts(epsilon, mask_dead), buf.data_ptr(), dtype, layout, self._stream()))
         return buf
 
+    def agent_policy_actions(self, q_imposter: torch.Tensor, q_crew: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                             epsilon: float = 0.0, mask_dead: bool = False) -> torch.Tensor:
+        """``policy_actions`` with one Q row per (env, agent) -- networks that read each agent's own view (a ``SpatialDQN``,
+        train.py:351-381): ``q_imposter`` ``[B, A, n_imposter_actions]`` (or ``[B * A, n]``, row ``b * A + i``), ``q_crew`` likewise or None =
+        a random crew.  Roles, draws, exploration and ``mask_dead`` are ``policy_actions``' own.  One launch
+        (``susnet_agent_policy_actions``); returns ``out`` (default: an int64 ``[B, A]`` buffer the env keeps)."""
+        n = self.batch * self.n_agents
+        assert q_imposter.dtype == torch.float32 and q_imposter.numel() == n * self.n_imposter_actions and q_imposter.is_contiguous() and \
+            q_imposter.shape[-1] == self.n_imposter_actions
+        if q_crew is not None:
+            assert q_crew.dtype == torch.float32 and q_crew.numel() == n * self.n_crew_actions and q_crew.is_contiguous() and \
+                q_crew.shape[-1] == self.n_crew_actions
+        if out is None:
+            out = self._default_actions_out()
+        dtype, layout, buf = self._describe_actions(out, output=True)
+        with self._on_device():
+            L.check(self.lib.susnet_agent_policy_actions(self._h, q_imposter.data_ptr(), q_crew.data_ptr() if q_crew is not None else None,
+                                                         self._policy_opts(epsilon, mask_dead), buf.data_ptr(), dtype, layout, self._stream()))
+        return buf
+
     def qnet_pack(self, components: Sequence[str], weights, biases, slopes, into: Optional["PackedQNet"] = None) -> Optional["PackedQNet"]:
         """Pack a reference ``MLP`` (dqn.py:72-108: ``weights[l]`` ``[out, in]`` float32, ``biases[l]``, one PReLU slope per hidden
         layer) for ``qnet_forward``.  Returns ``None`` when the library does not serve this handle / feature layout / layer stack
@@ -672,19 +692,11 @@ class BatchedFourRoomEnv:
                 # one susnet_episode_info (16 bytes = 4 int32 words) per slot, written only where an episode ended: its info counters
                 "ep_info": z(T, B, 4, dtype=torch.int32)}
 
-    def policy_tick_into(self, feed: Dict[str, torch.Tensor], t: int, net_imposter: "PackedQNet" = None, net_crew: "PackedQNet" = None,
-                         q_imposter: Optional[torch.Tensor] = None, q_crew: Optional[torch.Tensor] = None, epsilon: float = 0.0,
-                         mask_dead: bool = True, q_out: Optional[torch.Tensor] = None) -> None:
-        """ONE tick of the trainer's acting loop (train.py:345-399: act on the current state, step, keep what ``replay_buffer.add``
-        needs) written into slot ``t`` of ``feed``: the actions taken, rewards, done / truncated, the raw uint8 state after the step (after
-        the auto-reset where the episode ended), the true terminal state and the episode's info counters (``ep_info``) there, and the acting
-        episode's roles.  The teams' Q rows come
-        from packed reference MLPs (``net_*``: the Q-network kernel reads the state itself) or from the caller (``q_*``).  With
-        ``net_imposter`` alone on a compiled-in game and the production stream the whole tick is ONE kernel
-        (``susnet_qnet_policy_step``: network, argmax / exploration, the random crew's draws, step, feed); else the network launch(es) +
-        ``susnet_policy_step``.  Asynchronous; nothing is exported to the host-side mirrors."""
+    def _feed_slot_io(self, feed: Dict[str, torch.Tensor], t: int):
+        """``(io, slot, bounce)``: the feed's ``susnet_step_io`` pointed at slot ``t`` (actions U8 ``LAYOUT_BA``, rewards, flags, the raw uint8
+        observation, ``term_obs``, roles, ``ep_info``), the slot's observation tensor and -- where that does not start on a 16-byte boundary
+        -- the aligned bounce buffer the kernel writes instead (the caller copies it into the slot)."""
         assert self.auto_reset, "collection needs an auto-resetting env"
-        A, S = self.n_agents, self.flattened_state_size
         io = feed.get("_io")
         if io is None:
             io = feed["_io"] = L.StepIO()
@@ -708,6 +720,20 @@ class BatchedFourRoomEnv:
         io.done, io.truncated = feed["done"][t].data_ptr(), feed["truncated"][t].data_ptr()
         io.term_obs, io.roles = feed["term_obs"][t].data_ptr(), feed["roles"][t].data_ptr()
         io.ep_info = feed["ep_info"][t].data_ptr() if "ep_info" in feed else None
+        return io, slot, bounce
+
+    def policy_tick_into(self, feed: Dict[str, torch.Tensor], t: int, net_imposter: "PackedQNet" = None, net_crew: "PackedQNet" = None,
+                         q_imposter: Optional[torch.Tensor] = None, q_crew: Optional[torch.Tensor] = None, epsilon: float = 0.0,
+                         mask_dead: bool = True, q_out: Optional[torch.Tensor] = None) -> None:
+        """ONE tick of the trainer's acting loop (train.py:345-399: act on the current state, step, keep what ``replay_buffer.add``
+        needs) written into slot ``t`` of ``feed``: the actions taken, rewards, done / truncated, the raw uint8 state after the step (after
+        the auto-reset where the episode ended), the true terminal state and the episode's info counters (``ep_info``) there, and the acting
+        episode's roles.  The teams' Q rows come
+        from packed reference MLPs (``net_*``: the Q-network kernel reads the state itself) or from the caller (``q_*``).  With
+        ``net_imposter`` alone on a compiled-in game and the production stream the whole tick is ONE kernel
+        (``susnet_qnet_policy_step``: network, argmax / exploration, the random crew's draws, step, feed); else the network launch(es) +
+        ``susnet_policy_step``.  Asynchronous; nothing is exported to the host-side mirrors."""
+        io, slot, bounce = self._feed_slot_io(feed, t)
         one_kernel = (net_imposter is not None and q_imposter is None and q_crew is None and
                       self.supports_qnet_policy_step(net_imposter, net_crew, epsilon))
         opts = self._policy_opts(epsilon, mask_dead, net_crew if one_kernel else None)
@@ -721,6 +747,27 @@ class BatchedFourRoomEnv:
                     q_crew = self.qnet_forward(net_crew)
                 L.check(self.lib.susnet_policy_step(self._h, q_imposter.data_ptr(), q_crew.data_ptr() if q_crew is not None else None, opts,
                                                     C.byref(io), self._stream()))
+            if bounce is not None:
+                slot.copy_(bounce)
+
+    def agent_policy_tick_into(self, feed: Dict[str, torch.Tensor], t: int, q_imposter: torch.Tensor, q_crew: Optional[torch.Tensor] = None,
+                               epsilon: float = 0.0, mask_dead: bool = True) -> None:
+        """``policy_tick_into`` for networks that give one Q row per (env, agent) -- a ``SpatialDQN`` on every agent's own view
+        (train.py:351-381): ``q_imposter`` ``[B * A, n_imposter_actions]`` / ``q_crew`` ``[B * A, n_crew_actions]`` (or None: a random crew) as
+        ``SpatialQNet.forward(..., agents=A)`` writes them.  ``susnet_agent_policy_actions`` writes the actions taken into slot ``t`` of
+        ``feed``, ``susnet_step`` reads them there and writes the rest of the slot.  Two launches, asynchronous; nothing is exported to the
+        host-side mirrors."""
+        B, A = self.batch, self.n_agents
+        assert q_imposter.dtype == torch.float32 and q_imposter.is_contiguous() and q_imposter.numel() == B * A * self.n_imposter_actions and \
+            q_imposter.shape[-1] == self.n_imposter_actions, f"q_imposter: float32 [B * A, {self.n_imposter_actions}], contiguous"
+        if q_crew is not None:
+            assert q_crew.dtype == torch.float32 and q_crew.is_contiguous() and q_crew.numel() == B * A * self.n_crew_actions and \
+                q_crew.shape[-1] == self.n_crew_actions, f"q_crew: float32 [B * A, {self.n_crew_actions}], contiguous"
+        io, slot, bounce = self._feed_slot_io(feed, t)
+        with self._on_device():
+            L.check(self.lib.susnet_agent_policy_actions(self._h, q_imposter.data_ptr(), q_crew.data_ptr() if q_crew is not None else None,
+                                                         self._policy_opts(epsilon, mask_dead), io.actions, L.U8, L.LAYOUT_BA, self._stream()))
+            L.check(self.lib.susnet_step(self._h, C.byref(io), self._stream()))
             if bounce is not None:
                 slot.copy_(bounce)
 

@@ -469,11 +469,21 @@ def _weights_version(model) -> int:
 
 def served_by_kernels(policy):
     """``(imposters served, crew served, any dense)`` of a policy object: whether each team's Q rows come from one of the library's network
-    kernels (``fused_*``: the compiled-in layouts; ``dense_*``: ``susnet_mlp_forward``) -- a crew without a model is random, which is served."""
+    kernels (``fused_*``: the compiled-in layouts; ``dense_*``: ``susnet_mlp_forward``; ``spatial_*``: ``susnet_spatial_forward``, a
+    ``WindowedPolicyRollout(kernels=True)`` -- ``acts_per_agent`` tells that kind apart) -- a crew without a model is random, which is
+    served."""
     dense_imp, dense_crew = getattr(policy, "dense_imposter", None), getattr(policy, "dense_crew", None)
+    if acts_per_agent(policy):
+        return policy.spatial_imposter is not None, policy.crew_model is None or policy.spatial_crew is not None, False
     imp = policy.fused_imposter is not None or dense_imp is not None
     crew = policy.crew_model is None or policy.fused_crew is not None or dense_crew is not None
     return imp, crew, dense_imp is not None or dense_crew is not None
+
+
+def acts_per_agent(policy) -> bool:
+    """Whether ``policy`` gives one Q row per (env, agent) -- a ``WindowedPolicyRollout``: its ticks go through
+    ``env.agent_policy_tick_into`` -- and not one per env (``PolicyRollout``: ``env.policy_tick_into``)."""
+    return isinstance(policy, WindowedPolicyRollout)
 
 
 class PolicyRollout:
@@ -770,7 +780,7 @@ class WindowedPolicyRollout:
     supplies it).
     """
 
-    def __init__(self, env, featurizer, imposter_model: nn.Module, crew_model: nn.Module, sequence_length: int = 2,
+    def __init__(self, env, featurizer, imposter_model: nn.Module, crew_model: Optional[nn.Module], sequence_length: int = 2,
                  epsilon: float = 0.0, mask_dead: bool = True, seed: int = 0, kernels: bool = False):
         assert env.obs_config.mode == "raw" and env.obs_config.dtype == torch.uint8 and env.auto_reset, (
             "construct the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
@@ -785,6 +795,11 @@ class WindowedPolicyRollout:
         self._gen.manual_seed(seed)
         self.window = None
         self._actions = torch.zeros(env.batch, env.n_agents, dtype=torch.int64, device=env.device)
+        self._q_bufs = None  # q_rows(): (featurize spec, planes, non-spatial rows, the Global rows with the one-hot columns)
+
+    @property
+    def sequence_length(self) -> int:
+        return self.T
 
     def _spatial(self, model, n_actions):
         from .features import GlobalFeaturizer, PerspectiveFeaturizer
@@ -821,9 +836,86 @@ class WindowedPolicyRollout:
         self.window = self.env.obs.unsqueeze(1).repeat(1, self.T, 1)  # train.py:318-322: the first state T times
         return self.window
 
+    # ---- the collection loop's side (DeviceReplayBuffer.collect, evaluate): the window moved in place by the library, Q rows per agent ----
+    def reset_window(self) -> torch.Tensor:
+        """The acting window of the env's CURRENT state: that state T times (train.py:318-322)."""
+        from .env import ObsConfig
+
+        first = self.env.observe(ObsConfig("raw", dtype=torch.uint8))
+        self.window = first.unsqueeze(1).repeat(1, self.T, 1).contiguous()
+        return self.window
+
+    def load_window(self, raw_window: torch.Tensor) -> torch.Tensor:
+        """The acting window := a copy of ``raw_window`` (``[B, T, S]`` uint8: e.g. the window a ring carries between ``collect`` calls)."""
+        B, T, S = self.env.batch, self.T, self.env.flattened_state_size
+        assert raw_window.dtype == torch.uint8 and tuple(raw_window.shape) == (B, T, S), f"load_window: uint8 [{B}, {T}, {S}]"
+        if self.window is None or self.window.data_ptr() == raw_window.data_ptr() or not self.window.is_contiguous():
+            self.window = torch.empty(B, T, S, dtype=torch.uint8, device=self.env.device)
+        self.window.copy_(raw_window)
+        return self.window
+
+    def push(self, done: torch.Tensor, truncated: torch.Tensor, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The acting window one tick on, in place (``susnet_state_window_push``; train.py:388-389, 441-445): ``obs`` ``[B, S]`` uint8 is the
+        state after the tick (default ``env.obs``), ``done`` / ``truncated`` ``[B]`` its flags -- e.g. a feed slot, read where the stepping
+        kernel wrote it.  Asynchronous."""
+        env = self.env
+        obs = env.obs if obs is None else obs
+        B, S = env.batch, env.flattened_state_size
+        assert self.window is not None and self.window.is_contiguous(), "push: no window yet (reset_window / load_window)"
+        assert obs.dtype == torch.uint8 and tuple(obs.shape) == (B, S) and obs.is_contiguous(), f"push: obs is uint8 [{B}, {S}]"
+        for name, f in (("done", done), ("truncated", truncated)):
+            assert f.dtype in (torch.bool, torch.uint8) and tuple(f.shape) == (B,) and f.is_contiguous(), f"push: {name} is bool [{B}]"
+        with env._on_device():
+            L.check(env.lib.susnet_state_window_push(env._h, self.window.data_ptr(), self.T, S, B, obs.data_ptr(), done.data_ptr(),
+                                                     truncated.data_ptr(), env._stream()))
+        return self.window
+
+    def refresh_weights(self, force: bool = False) -> bool:
+        """Nothing to do: ``SpatialQNet`` reads the modules' parameters in place at every forward."""
+        return False
+
+    @torch.no_grad()
+    def q_rows(self):
+        """``(q_imposter [B * A, n], q_crew [B * A, n] or None)`` of the acting window: ONE ``susnet_featurize`` launch over its ``B * T`` rows
+        into reused buffers, the Global featurizer's non-spatial rows with every agent's one-hot appended (the one-hot columns written
+        once, as ``DeviceDQNTeamTrainer._spatial_step`` does), and one ``SpatialQNet.forward`` per team that has a model.  Row
+        ``b * A + i`` = env b, agent i; a result is valid until the next call."""
+        from .features import GlobalFeaturizer
+
+        env, T = self.env, self.T
+        B, A = env.batch, env.n_agents
+        assert self.spatial_imposter is not None and (self.crew_model is None or self.spatial_crew is not None), (
+            "q_rows: susnet_spatial_forward does not serve this policy (WindowedPolicyRollout(kernels=True) with SpatialDQN models)")
+        assert self.window is not None, "q_rows: no window yet (reset_window / load_window)"
+        glob = isinstance(self.featurizer, GlobalFeaturizer)
+        if self._q_bufs is None:
+            spec, planes, non = env._make_obs(self.featurizer.config, 1, rows=B * T)
+            g = None
+            if glob:
+                Fn = non.shape[-1] + A
+                g = torch.empty(B, T, A, Fn, dtype=torch.float32, device=env.device)
+                g[..., Fn - A:] = torch.eye(A, dtype=torch.float32, device=env.device)
+            self._q_bufs = (spec, planes, non, g)
+        spec, planes, non, g = self._q_bufs
+        rows = self.window
+        with env._on_device():
+            # (the window's rows were written by the stepping kernel: valid by construction, the featurizer's row check is not polled)
+            L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], B * T, C.byref(spec), env._stream()))
+        if glob:
+            base = non.shape[-1]
+            g[..., :base] = non.view(B, T, 1, base)
+            spatial, non_spatial = planes.view(B, T, *planes.shape[1:]), g
+        else:
+            spatial, non_spatial = planes.view(B, T, *planes.shape[1:]), non.view(B, T, *non.shape[1:])
+        q_imp = self.spatial_imposter.forward(spatial, non_spatial, A)
+        q_crew = self.spatial_crew.forward(spatial, non_spatial, A) if self.spatial_crew is not None else None
+        return q_imp, q_crew
+
     @torch.no_grad()
     def act(self) -> torch.Tensor:
         env = self.env
+        if self.crew_model is None:
+            raise ValueError("WindowedPolicyRollout.act: a random crew (crew_model=None) acts through q_rows() + env.agent_policy_tick_into")
         if self.window is None:
             self.reset()
         if not env.export_state:

@@ -166,19 +166,31 @@ class DeviceReplayBuffer:
         carried raw window (ONE ``susnet_featurize`` launch over its ``B * T`` rows), so it follows the raw window under every rule above;
         per tick after the first, ``susnet_window_push`` moves it one tick on, reading the flags ``policy_tick_into`` wrote into the feed in
         place (tests/golden/window/wcollect_*.npz pin the ring against the reference's at T = 2 and 3).  Returns the number of
-        transitions added."""
+        transitions added.
+
+        ``policy`` a ``WindowedPolicyRollout(kernels=True)`` whose ``SpatialDQN``s ``susnet_spatial_forward`` serves (a crew without a model is
+        random): the env is ``ObsConfig('raw', torch.uint8)``, ``policy.T == trajectory_size`` for every T.  At the start of a call the
+        policy's acting window is loaded from the carried raw window (its own buffer); per tick ``susnet_state_window_push`` moves it on from
+        the previous slot, ``policy.q_rows()`` gives one Q row per (env, agent), and ``env.agent_policy_tick_into`` writes the slot
+        (``susnet_agent_policy_actions`` + ``susnet_step``).  With ``batch=1``, ``rng='numpy'`` and two networks the ring equals the
+        reference's (tests/golden/spatial_collect/*.npz)."""
         import ctypes as C
 
         from . import _lib as L
         from .env import ObsConfig
 
-        from .policy import served_by_kernels
+        from .policy import acts_per_agent, served_by_kernels
 
         imp_served, crew_served, dense = served_by_kernels(policy)
+        per_agent = acts_per_agent(policy)  # a WindowedPolicyRollout: one Q row per (env, agent), susnet_spatial_forward
         assert policy.env is env and imp_served, ("collect: the imposters' model must be a reference MLP one of the network kernels "
-                                                              "serves (PolicyRollout.fused_imposter, or dense_imposter: dense=True)")
+                                                              "serves (PolicyRollout.fused_imposter, or dense_imposter: dense=True), or a "
+                                                              "SpatialDQN susnet_spatial_forward serves (WindowedPolicyRollout(kernels=True))")
         assert crew_served, ("collect: the crew's model must be a reference MLP one of the network kernels serves "
-                                    "(PolicyRollout.fused_crew / dense_crew), or None: random crew")
+                                    "(PolicyRollout.fused_crew / dense_crew), a SpatialDQN susnet_spatial_forward serves "
+                                    "(WindowedPolicyRollout(kernels=True)), or None: random crew")
+        if per_agent and policy.crew_model is None and env.rng_kind != "philox":
+            raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
         if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
             raise ValueError(f"collect: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
                              f"{env.n_crew_actions}: only the compiled-in games are collected from at that size")
@@ -186,7 +198,9 @@ class DeviceReplayBuffer:
             raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
         assert env.flattened_state_size == self.state_size and env.n_agents == self.n_agents and env.n_imposters == self.n_imposters
         T, B = self.trajectory_size, env.batch
-        windowed = getattr(policy, "sequence_length", 1) > 1
+        windowed = not per_agent and getattr(policy, "sequence_length", 1) > 1
+        if per_agent:  # (every T, 1 included: the recurrent network reads the window as a sequence)
+            assert policy.T == T, f"collect: the policy acts on windows of {policy.T} states, the ring stores windows of {T} (trajectory_size)"
         if windowed:
             assert dense, "collect: a policy with sequence_length > 1 acts through the dense kernel"
             assert policy.sequence_length == T, (f"collect: the policy acts on windows of {policy.sequence_length} states, the ring stores "
@@ -213,9 +227,11 @@ class DeviceReplayBuffer:
             rows = self._collect_window
             with torch.cuda.device(env.device):
                 L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], B * T, C.byref(spec), env._stream()))
+        if per_agent:  # the policy's own acting window: the ring append needs the carried one as it stood at the block's start
+            policy.load_window(self._collect_window)
         last = None  # the feed slot of the previous tick of this call
         # one launch per BLOCK where the env serves the whole tick in one kernel and the block's observation slots are 16-byte aligned
-        fused_block = (one_launch_per_block and not dense and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
+        fused_block = (one_launch_per_block and not dense and not per_agent and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
                        and (n_block == 1 or (B * self.state_size) % 16 == 0))
         done_ticks = 0
         while done_ticks < num_steps:
@@ -223,6 +239,13 @@ class DeviceReplayBuffer:
             policy.refresh_weights(force=False)  # (the optimizer may have stepped since the last block)
             if fused_block:  # the whole block in ONE launch (susnet_qnet_policy_rollout)
                 env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
+            elif per_agent:  # the acting window one tick on (from the previous slot), both spatial forwards on it, actions + step into the slot
+                for t in range(n):
+                    if last is not None:
+                        policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
+                    q_imp, q_crew = policy.q_rows()
+                    env.agent_policy_tick_into(feed, t, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                    last = t
             elif dense:  # a game / layer stack without a fused path: the dense forward(s) on the current flat observation, then the tick
                 for t in range(n):
                     env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
@@ -241,7 +264,7 @@ class DeviceReplayBuffer:
             self.size = min(self.size + n * B, self.max_size)
             done_ticks += n
             self._collect_feed_ticks = n
-        if dense:
+        if dense or per_agent:
             env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
         return num_steps * B
 

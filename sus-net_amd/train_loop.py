@@ -27,7 +27,7 @@ import torch
 from . import _lib as L
 from .episodes import EpisodeLog
 from .metrics import EpisodicMetricHandler, SusMetrics
-from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, served_by_kernels
+from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, SpatialQNet, WindowedPolicyRollout, acts_per_agent, served_by_kernels
 from .replay import DeviceReplayBuffer
 from .scheduler import ExponentialSchedule
 from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer
@@ -113,8 +113,11 @@ class _Run:
         imp_served, crew_served, dense = served_by_kernels(policy)
         if not imp_served or not crew_served:
             raise ValueError(f"{who}: served are reference MLPs a network kernel runs (PolicyRollout.fused_imposter / fused_crew on the compiled-in "
-                             "feature layouts, dense_imposter / dense_crew elsewhere: PolicyRollout(..., dense=True)); a crew model of None acts "
-                             "randomly")
+                             "feature layouts, dense_imposter / dense_crew elsewhere: PolicyRollout(..., dense=True)) and SpatialDQNs "
+                             "susnet_spatial_forward runs (spatial_imposter / spatial_crew: WindowedPolicyRollout(..., kernels=True)); a crew "
+                             "model of None acts randomly")
+        if acts_per_agent(policy) and policy.crew_model is None and env.rng_kind != "philox":
+            raise ValueError(f"{who}: a random crew draws from the production stream: build the env with rng='philox'")
         if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
             raise ValueError(f"{who}: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
                              f"{env.n_crew_actions}")
@@ -184,7 +187,9 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
     """``train()`` of src/train.py:284-471.  ``num_steps`` counts lockstep ticks: each adds ``env.batch`` transitions.  ``policy``: the
     ``PolicyRollout`` the teams act by (reference MLPs a network kernel serves -- the fused kernels on the compiled-in layouts, the dense
     kernel on every other game / component set / layer stack, where the learner is ``torch_train_step``; a crew model of None = random crew); ``trainer``: the
-    ``DeviceDQNTeamTrainer`` over the same models (built with ``policy=policy``, so that acting follows the trained weights);
+    ``DeviceDQNTeamTrainer`` over the same models (built with ``policy=policy``, so that acting follows the trained weights).  ``policy`` may
+    also be a ``WindowedPolicyRollout(kernels=True)`` over ``SpatialDQN``s that ``susnet_spatial_forward`` serves, with a trainer built
+    ``featurizer=..., spatial=True``: the reference's default model (train.py:152-176);
     ``generator``: draws the replay samples.  ``metrics`` receives what the reference's handler holds after its ``train()``: the teams'
     returns with one entry per episode, the loss per train step, and the nine info counters -- with ``per_episode_info=True`` one entry
     per episode, in episode order (what ``metrics.step(info)`` appends at every episode end, train.py:419-427; ``run_experiment`` asks for
@@ -235,12 +240,12 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
 
 def _experiment_config(env, imposter_model, crew_model, components, base, *, num_steps, sequence_length, replay_buffer_size,
                        replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter,
-                       train_crew, learning_rate, train_step_interval, target_update_interval) -> dict:
+                       train_crew, learning_rate, train_step_interval, target_update_interval, featurizer_type=None) -> dict:
     """What ``run_experiment`` writes into ``config.json`` (train.py:185-211), in its key order."""
     return {
         "num_steps": num_steps, "batch": env.batch, "imposter_model_args": getattr(imposter_model, "config", None),
         "crew_model_args": getattr(crew_model, "config", None), "imposter_model_type": model_type(imposter_model),
-        "crew_model_type": model_type(crew_model), "featurizer_type": "flat:" + "+".join(components), "sequence_length": sequence_length,
+        "crew_model_type": model_type(crew_model), "featurizer_type": featurizer_type or "flat:" + "+".join(components), "sequence_length": sequence_length,
         "replay_buffer_size": replay_buffer_size, "replay_prepopulate_steps": replay_prepopulate_steps, "batch_size": batch_size, "gamma": gamma,
         "scheduler_start_eps": scheduler_start_eps, "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps,
         "train_imposter": train_imposter, "train_crew": train_crew, "experiment_base_dir": str(base), "optimizer_type": "adam",
@@ -254,7 +259,7 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
                    generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
-                   dense_train: bool = False) -> EpisodicMetricHandler:
+                   dense_train: bool = False, featurizer=None) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: writes ``config.json``, builds ring, policy, trainer
     and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
     entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
@@ -262,9 +267,22 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     ``susnet_mlp_train_step`` instead of the torch loop.  ``sequence_length`` = T > 1 (the reference's default is 2, train.py:160): the
     networks read the flattened window of the last T states, ``T * F`` inputs (dqn.py:86-90); acting, collecting and the train step
     then all go through the dense kernels (the trainer is built ``dense=True`` whatever ``dense_train`` says), and a network that is not
-    dense-served at that T is a ``ValueError``."""
+    dense-served at that T is a ``ValueError``.
+
+    ``featurizer``: a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env`` with ``SpatialDQN`` models (the reference's default,
+    train.py:152-176; the crew may be None) -- ``env`` is then built ``obs=ObsConfig('raw', torch.uint8), auto_reset=True`` and ``components``
+    is not read.  The teams act through ``WindowedPolicyRollout(kernels=True, sequence_length=T)`` (``susnet_spatial_forward`` +
+    ``susnet_agent_policy_actions``), the trainer is built ``featurizer=featurizer, spatial=True`` (a trained team
+    ``susnet_spatial_train_step`` does not serve takes ``torch_train_step``), the ring has ``trajectory_size=T``; ``config.json`` names
+    ``spatial_dqn`` and ``global`` / ``perspective`` and, as ``train_step``, the learner the run takes; the checkpoints are ``<team>_spatial_dqn_<p>.pt``.  A ``SpatialDQN`` the kernels do not
+    act for is a ``ValueError`` that says which bound failed."""
     components = list(components)
     sequence_length = int(sequence_length)
+    if featurizer is not None:
+        return _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size,
+                                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps,
+                                       train_imposter, train_crew, experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves,
+                                       target_update_interval, generator, episode_log)
     if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
         raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
     if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
@@ -291,6 +309,79 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
     metrics = EpisodicMetricHandler()
     ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
+    if replay_prepopulate_steps > 0:
+        ring.populate_fused(env, replay_prepopulate_steps)
+    train(env, metrics, num_steps, ring, policy, trainer, scheduler, experiment_dir, train_step_interval=train_step_interval,
+          batch_size=batch_size, num_saves=num_checkpoint_saves, target_update_interval=target_update_interval, generator=generator,
+          episode_log=episode_log, per_episode_info=True)
+    metrics.save_metrics(save_file_path=experiment_dir / "metrics.json")
+    return metrics
+
+
+def spatial_unserved_reason(env, featurizer, model, n_actions: int, T: int) -> Optional[str]:
+    """Why ``WindowedPolicyRollout(kernels=True)`` does not act for ``model`` on ``featurizer``'s tensors -- the bound that failed -- or None
+    if it does."""
+    from .features import GlobalFeaturizer, PerspectiveFeaturizer
+
+    if not isinstance(model, SpatialDQN):
+        return f"a SpatialDQN is served, got {type(model).__name__}"
+    if not isinstance(featurizer, (GlobalFeaturizer, PerspectiveFeaturizer)) or featurizer.env is not env:
+        return "the featurizer must be a GlobalFeaturizer / PerspectiveFeaturizer over the env that is trained on"
+    if not 1 <= T <= L.SPATIAL_MAX_T:
+        return f"sequence_length = {T}: windows of 1 .. {L.SPATIAL_MAX_T} states are served (SUSNET_SPATIAL_MAX_T)"
+    net = SpatialQNet(env, model)
+    if net is None:
+        return ("susnet_spatial_forward does not serve this module: square 1 / 3 / 5 kernels, at most "
+                f"{L.SPATIAL_MAX_CONV} convolutions of at most 32 channels on images of at most {L.SPATIAL_MAX_N} x {L.SPATIAL_MAX_N} x "
+                f"{L.SPATIAL_MAX_C}, an RNN input of at most {L.SPATIAL_MAX_R}, at most {L.SPATIAL_MAX_RNN_LAYERS} unidirectional tanh RNN layers "
+                f"with biases, a Linear + single-slope PReLU head of widths up to {L.MLP_MAX_HIDDEN}")
+    _, planes, non_spatial = env._make_obs(featurizer.config, 1, rows=1)
+    if non_spatial is None:
+        return "the featurizer has no non-spatial block"
+    Fn = non_spatial.shape[-1] + (env.n_agents if isinstance(featurizer, GlobalFeaturizer) else 0)
+    want = (planes.shape[-3], planes.shape[-1], Fn, n_actions)
+    if (net.C, net.N, net.Fn, net.dims[-1]) != want:
+        return (f"the network reads (channels, image size, non-spatial width, actions) = {(net.C, net.N, net.Fn, net.dims[-1])}, the "
+                f"featurizer and the game give {want}")
+    return None
+
+
+def _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size, replay_prepopulate_steps,
+                            batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter, train_crew,
+                            experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves, target_update_interval, generator,
+                            episode_log) -> EpisodicMetricHandler:
+    """``run_experiment`` for ``SpatialDQN`` models on a Global / Perspective featurizer (see there)."""
+    from .features import GlobalFeaturizer
+
+    T = sequence_length
+    if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
+        raise ValueError("run_experiment: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
+    for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
+        if team == "crew" and model is None:
+            continue
+        why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
+        if why is not None:
+            raise ValueError(f"run_experiment: the {team} model is not served by the spatial kernels: {why}")
+    if crew_model is None and env.rng_kind != "philox":
+        raise ValueError("run_experiment: a random crew draws from the production stream: build the env with rng='philox'")
+    policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
+    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
+    experiment_dir = base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+    experiment_dir.mkdir(parents=True, exist_ok=True)
+    config = _experiment_config(env, imposter_model, crew_model, [], base, num_steps=num_steps, sequence_length=T,
+                                replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
+                                gamma=gamma, scheduler_start_eps=scheduler_start_eps, scheduler_end_eps=scheduler_end_eps,
+                                scheduler_time_steps=scheduler_time_steps, train_imposter=train_imposter, train_crew=train_crew,
+                                learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval,
+                                featurizer_type="global" if isinstance(featurizer, GlobalFeaturizer) else "perspective")
+    trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, [], lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
+                                   train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True)
+    scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
+    metrics = EpisodicMetricHandler()
+    ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
+    # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
+    config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
+    (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
     if replay_prepopulate_steps > 0:
         ring.populate_fused(env, replay_prepopulate_steps)
     train(env, metrics, num_steps, ring, policy, trainer, scheduler, experiment_dir, train_step_interval=train_step_interval,
@@ -340,7 +431,8 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     too.  Each member gets ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values),
     the checkpoints and ``metrics.json`` exactly as ``run_experiment`` writes them, so plotting over one directory per gamma keeps
     working.  ``dense_train`` is ``run_experiment``'s: members whose step the sweep call does not serve then take their dense steps one
-    after another.  Returns the members' metric handlers."""
+    after another.  Returns the members' metric handlers.  MLP-only: ``SpatialDQN`` members (``run_experiment(..., featurizer=...)``) are
+    not swept -- ``susnet_dqn_train_sweep`` steps reference MLPs."""
     components = list(components)
     variants = check_variants(variants)
     if sequence_length != 1:
@@ -390,7 +482,7 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
 
 @torch.no_grad()
 def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, block_ticks: int = 64,
-             mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None, sequence_length: int = 1) -> dict:
+             mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None, sequence_length: int = 1, featurizer=None) -> dict:
     """How a pair of models plays: ``env.reset()``, then the acting loop for ``n_ticks`` lockstep ticks in blocks of ``block_ticks`` (one
     policy rollout launch into a feed + one ``EpisodeLog.update`` per block; no ring, no trainer), and ONE read-back at the end.
     ``crew_model=None``: a random crew.  Returns ``episodes``, ``imposter_win_rate``, ``crew_win_rate``, ``truncation_rate``,
@@ -398,9 +490,14 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     counter per finished episode (``mean_<counter>``), plus ``dropped`` (episodes beyond ``capacity``, not in the means) and ``ticks``.
     Rates and means of zero episodes are NaN.  ``sequence_length`` = T > 1: models that read the window of the last T states (``T * F``
     inputs), acting as in ``DeviceReplayBuffer.collect``: the dense kernel on the policy's feature window, ``susnet_window_push`` between
-    ticks."""
+    ticks.  ``featurizer`` (a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env``, which then fuses ``ObsConfig('raw', torch.uint8)``):
+    ``SpatialDQN`` models acting as in ``collect`` through ``WindowedPolicyRollout(kernels=True, sequence_length=T)``; ``components`` is not
+    read."""
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
+    if featurizer is not None:
+        return _evaluate_spatial(env, imposter_model, crew_model, featurizer, int(n_ticks), epsilon, block_ticks, mask_dead, gamma, capacity,
+                                 int(sequence_length))
     components = list(components)
     policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead, dense=True,
                            sequence_length=sequence_length)
@@ -453,6 +550,41 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     return summarize_episodes(rec, ticks=n_ticks)
 
 
+def _evaluate_spatial(env, imposter_model, crew_model, featurizer, n_ticks, epsilon, block_ticks, mask_dead, gamma, capacity, T) -> dict:
+    """``evaluate`` for ``SpatialDQN`` models: ``collect``'s acting loop into a feed + ``EpisodeLog``, without a ring."""
+    if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8:
+        raise ValueError("evaluate: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
+    for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
+        if team == "crew" and model is None:
+            continue
+        why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
+        if why is not None:
+            raise ValueError(f"evaluate: the {team} model is not served by the spatial kernels: {why}")
+    if crew_model is None and env.rng_kind != "philox":
+        raise ValueError("evaluate: a random crew draws from the production stream: build the env with rng='philox'")
+    policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, epsilon=epsilon, mask_dead=mask_dead, kernels=True)
+    n_block = max(1, min(int(block_ticks), n_ticks))
+    env.reset()
+    if capacity is None:
+        capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
+    log = EpisodeLog(env, gamma=gamma, capacity=capacity)
+    feed = env.alloc_feed(n_block)
+    policy.reset_window()  # train.py:318-322: the fresh state T times
+    t, last = 0, None
+    while t < n_ticks:
+        n = min(n_block, n_ticks - t)
+        for k in range(n):
+            if last is not None:
+                policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
+            q_imp, q_crew = policy.q_rows()
+            env.agent_policy_tick_into(feed, k, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
+            last = k
+        log.update(feed, n, tick_base=t)
+        t += n
+    env.refresh_obs()
+    return summarize_episodes(log.records(), ticks=n_ticks)
+
+
 def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:
     """The evaluation summary of ``EpisodeLog.records()`` (a log fed with ``ep_info``): see ``evaluate``."""
     n = int(rec["count"])
@@ -469,20 +601,27 @@ def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:
 
 
 def evaluate_checkpoints(experiment_dir, env, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, **kw) -> dict:
-    """``evaluate`` for every checkpoint pair ``imposter_mlp_<p>.pt`` / ``crew_mlp_<p>.pt`` that ``run_experiment`` wrote into
+    """``evaluate`` for every checkpoint pair ``imposter_mlp_<p>.pt`` / ``crew_mlp_<p>.pt`` (or ``imposter_spatial_dqn_<p>.pt`` /
+    ``crew_spatial_dqn_<p>.pt``, loaded with ``SpatialDQN.load_from_checkpoint``; pass ``featurizer=...``) that ``run_experiment`` wrote into
     ``experiment_dir`` (a run without a crew model: the imposters against a random crew), as a table ``{<p>: summary}`` in the order of
     training progress (``"0"``, ..., ``"100%"``).  Further keywords go to ``evaluate`` (``sequence_length=T`` for a run trained on
     windows)."""
     d = pathlib.Path(experiment_dir)
     found = {}
-    for path in d.glob("imposter_mlp_*.pt"):
-        found[path.stem[len("imposter_mlp_"):]] = path
+    for kind, cls in (("mlp", MLP), ("spatial_dqn", SpatialDQN)):
+        for path in d.glob(f"imposter_{kind}_*.pt"):
+            found[path.stem[len(f"imposter_{kind}_"):]] = (path, cls)
     if not found:
-        raise FileNotFoundError(f"evaluate_checkpoints: no imposter_mlp_<p>.pt under {d}")
+        raise FileNotFoundError(f"evaluate_checkpoints: no imposter_mlp_<p>.pt / imposter_spatial_dqn_<p>.pt under {d}")
     table = {}
     for p in sorted(found, key=lambda s: float(s.rstrip("%"))):
-        imp = MLP.load_from_checkpoint(found[p], map_location="cpu").to(env.device)
-        crew_path = d / f"crew_mlp_{p}.pt"
-        crew = MLP.load_from_checkpoint(crew_path, map_location="cpu").to(env.device) if crew_path.exists() else None
+        path, cls = found[p]
+        imp = cls.load_from_checkpoint(path, map_location="cpu").to(env.device)
+        crew = None
+        for kind, crew_cls in (("mlp", MLP), ("spatial_dqn", SpatialDQN)):
+            crew_path = d / f"crew_{kind}_{p}.pt"
+            if crew_path.exists():
+                crew = crew_cls.load_from_checkpoint(crew_path, map_location="cpu").to(env.device)
+                break
         table[p] = evaluate(env, imp, crew, components, n_ticks, epsilon=epsilon, **kw)
     return table

@@ -204,10 +204,11 @@ class DeviceDQNTeamTrainer:
         p = self.policy
         if p is None:
             return None
+        # (a WindowedPolicyRollout has no packed image: SpatialQNet reads the parameters in place)
         if team == 0 and p.imposter_model is self.models[0]:
-            return p.fused_imposter
+            return getattr(p, "fused_imposter", None)
         if team == 1 and p.crew_model is self.models[1]:
-            return p.fused_crew
+            return getattr(p, "fused_crew", None)
         return None
 
     def uses_hip(self, ring) -> bool:
