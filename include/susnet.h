@@ -824,6 +824,50 @@ typedef struct susnet_spatial_train_io {
 int susnet_spatial_train_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out);
 int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream);
 
+/* Dropout between the layers of the SpatialDQN's nn.RNN in the TRAIN STEP (training mode, rnn_dropout = p > 0, rnn_layers = L > 1), opt-in:
+ * the three entry points below.  susnet_spatial_train_step and its kernels are as they were (no dropout); susnet_spatial_forward stays the
+ * EVAL-mode forward (no dropout form of it exists: a model acts in eval mode on the device).
+ *   What torch computes (nn.RNN, batch_first, training): the output sequence of every layer l < L - 1 is multiplied elementwise by a mask m_l of
+ * values 0 (probability p) and 1 / (1 - p), and the product feeds layer l + 1 ONLY: layer l's own recurrence W_hh h_l[t-1] reads the
+ * undropped h_l, and the last layer's output -- what the head reads -- is not dropped.  torch's mask stream cannot be reproduced on the
+ * device (and its own CPU and GPU streams differ), so parity is "equal given equal masks", and the library hands its masks out:
+ * susnet_rnn_dropout_mask.
+ *   The mask.  m(net, agent, row, t, layer, unit) is 0 or s = 1.0f / (1.0f - p) in float32, a pure function of its eight inputs (seed and
+ * offset besides those six) -- never of the grid, the tile, the wave or the order of a list.  One Philox4x32-10 block per four consecutive
+ * units, G = row_base + row:
+ *     key      = (seed & 0xffffffff, seed >> 32)
+ *     counter  = (unit / 4 | layer << 8 | t << 12 | net << 16 | agent << 20,  G & 0xffffffff,  (G >> 32) & 0xff | (offset >> 32) << 8,
+ *                 offset & 0xffffffff)
+ *     word j of the block (j = 0 .. 3, the order of the counter words after the ten rounds) belongs to unit 4 (unit / 4) + j;
+ *     the element is KEPT (m = s) iff word >= floor(p * 2^32), computed in float64 from the float32 p; floor(p * 2^32) == 0
+ *     (p == 0, or a positive p below 2^-32) keeps everything with m = 1.0f.
+ *   net: 0 the online network, 1 the target network.  layer: the layer whose OUTPUT is masked, 0 .. L - 2.  agent = the update's agent,
+ * row = the position s in the sampled batch (not the slot in the (agent, team) list).  A caller advances `offset` between calls that must
+ * not repeat their masks (a captured graph replays its masks: capture is the caller's decision).  Refused (SUSNET_E_INVALID, the field
+ * named, before any launch): drop NULL, p outside [0, 1) or NaN, offset >= 2^56, row_base < 0 or row_base + rows > 2^40, and everything the
+ * plain call refuses.
+ *
+ * susnet_spatial_train_step_dropout: susnet_spatial_train_step with the online network's forward and backward pass and the target
+ * network's forward under their masks: forward in[l+1][t] = m[l][t] * h[l][t]; dz[l][t] = (1 - h^2) (m[l][t] * (W_ih[l+1]^T dz[l+1][t]) +
+ * W_hh[l]^T dz[l][t+1] (+ the head's term)); dW_ih[l+1] += dz[l+1][t] (m[l][t] * h[l][t])^T.  drop: TWO structs, [0] imposters, [1] crew
+ * (looked at where team[].enabled): drop[team].p[0] masks the online network, drop[team].p[1] the target network.  The same launch count,
+ * no atomics, no host wait, bitwise reproducible for equal (state, seed, offset).  The multipliers of a tile are kept in the workspace,
+ * which is therefore larger than the plain step's: susnet_spatial_train_dropout_workspace_bytes is its query (the plain query does NOT
+ * serve the dropout step).  With every p of the enabled teams 0 the call runs susnet_spatial_train_step's kernels.
+ * susnet_rnn_dropout_mask: the multipliers out[layers - 1][n][T][H] (device float32, 4-byte aligned) that the call above uses for the
+ * same `drop`, `net` (p = drop->p[net]) and `agent`, rows row_base .. row_base + n - 1.  Served: net 0 / 1, agent 0 .. 4095, layers 2 .. 4,
+ * n >= 1, T 1 .. 8, H 1 .. 256.  One launch. */
+typedef struct susnet_rnn_dropout {
+    float p[2];                      /* [0] the online network, [1] the target network; 0 switches that net's mask off */
+    uint64_t seed;
+    uint64_t offset;                 /* below 2^56: the caller's call counter */
+    int64_t row_base;                /* added to every row index */
+} susnet_rnn_dropout;
+int susnet_spatial_train_dropout_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out);
+int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream);
+int susnet_rnn_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agent, int32_t layers, int64_t n, int32_t T,
+                            int32_t H, float *out, void *stream);
+
 /* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
  * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.
  * Per tick t and environment b, for every agent: G[a] = (double)rewards[t][b][a] + gamma * G[a] in float64, the product rounded before

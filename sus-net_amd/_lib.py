@@ -46,7 +46,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_agent_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_window_push", "susnet_state_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_episode_stats_bytes", "susnet_episode_stats",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_spatial_train_dropout_workspace_bytes", "susnet_spatial_train_step_dropout", "susnet_rnn_dropout_mask", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -167,6 +167,10 @@ class SpatialTrainIO(C.Structure):
                 ("non_spatial_stride", C.c_int64 * 3), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
                 ("imposters", C.c_void_p), ("max_size", C.c_int64), ("indices", C.c_void_p), ("n", C.c_int64), ("gamma", C.c_double),
                 ("losses_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64)]
+
+
+class RnnDropout(C.Structure):  # susnet_rnn_dropout: p[0] the online network, p[1] the target network
+    _fields_ = [("p", C.c_float * 2), ("seed", C.c_uint64), ("offset", C.c_uint64), ("row_base", C.c_int64)]
 
 
 class EpisodeRecord(C.Structure):
@@ -290,6 +294,10 @@ def lib():
     L.susnet_mlp_train_step.argtypes = [C.c_void_p, P(MlpTrainIO), C.c_void_p]
     L.susnet_spatial_train_workspace_bytes.argtypes = [C.c_void_p, P(SpatialTrainIO), P(C.c_uint64)]
     L.susnet_spatial_train_step.argtypes = [C.c_void_p, P(SpatialTrainIO), C.c_void_p]
+    L.susnet_spatial_train_dropout_workspace_bytes.argtypes = [C.c_void_p, P(SpatialTrainIO), P(C.c_uint64)]
+    L.susnet_spatial_train_step_dropout.argtypes = [C.c_void_p, P(SpatialTrainIO), P(RnnDropout), C.c_void_p]
+    L.susnet_rnn_dropout_mask.argtypes = [C.c_void_p, P(RnnDropout), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p]
     L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]
     L.susnet_episode_stats.argtypes = [C.c_void_p, P(EpisodeIO), C.c_void_p]
     for name in EXPORTS:

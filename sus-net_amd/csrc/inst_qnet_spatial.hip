@@ -2,6 +2,7 @@
 // other Q-network units
 #include "susnet_spatial.h"
 
+#include "susnet_dropout.h"
 #include "susnet_host.h" // lds_opt_in
 
 namespace susnet {
@@ -174,6 +175,23 @@ __global__ __launch_bounds__(kDnThreads) void k_spatial_rnn(SpatialRnnArgs a) {
     }
 }
 
+// susnet_rnn_dropout_mask: a thread per (layer, row, t, four units) writes the multipliers the dropout train step generates for itself
+__global__ __launch_bounds__(256) void k_rnn_dropout_mask(SpDrop dr, int net, int layers, int64_t n, int T, int H, float *__restrict__ out) {
+    const int HQ = (H + 3) >> 2;
+    const int64_t total = (int64_t)(layers - 1) * n * T * HQ;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int q = (int)(e % HQ), t = (int)(e / HQ % T);
+        const int64_t row = e / HQ / T % n;
+        const int layer = (int)(e / HQ / T / n);
+        float m[4];
+        sp_drop4(dr, net, row, t, layer, q, m);
+        float *dst = out + (((int64_t)layer * n + row) * T + t) * H;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (4 * q + j < H) dst[4 * q + j] = m[j];
+    }
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------------------
 size_t spatial_conv_lds(SpatialConvArgs &a) {
     int s0 = a.C * a.size[0] * a.size[0], s1 = 0; // buffer 0: the input and what layers 1, 3 write; buffer 1: layers 0, 2; the last layer writes rnn_in
@@ -235,6 +253,12 @@ hipError_t spatial_rnn_launch(SpatialRnnArgs a, hipStream_t st) {
     }
     const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
     hipLaunchKernelGGL(k_spatial_rnn, dim3((unsigned)(tiles < kDnMaxGrid ? tiles : kDnMaxGrid)), dim3(kDnThreads), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t rnn_dropout_mask_launch(const SpDrop &d, int net, int layers, int64_t n, int T, int H, float *out, hipStream_t st) {
+    const int64_t total = (int64_t)(layers - 1) * n * T * ((H + 3) >> 2), blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_rnn_dropout_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, d, net, layers, n, T, H, out);
     return hipGetLastError();
 }
 

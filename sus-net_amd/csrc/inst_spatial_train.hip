@@ -1,6 +1,7 @@
 // the SpatialDQN learner's kernels (susnet_spatial_train.h: susnet_spatial_train_step) -- a translation unit of its own
 #include "susnet_spatial_train.h"
 
+#include "susnet_dropout.h"
 #include "susnet_host.h" // lds_opt_in
 #include "susnet_train_core.h"
 
@@ -89,8 +90,11 @@ __global__ __launch_bounds__(kStConvThreads) void k_sp_train_conv(SpTrainBatch b
 
 // one step of the recurrence on a tile: h[l][t] = tanh(b_ih + b_hh + W_ih in + W_hh h[l][t-1]), in = the RNN input rows X (l = 0; a column
 // past nvalid is a zero operand) or h[l-1][t].  hs: the workgroup's slice, [l][t][unit][32]
+// DROP: in = m[l-1][t] h[l-1][t], the multipliers read from ms ([l][t][unit][32], l < L - 1), and the step writes its own m[l][t] there
+// (susnet_dropout.h: net `dnet`, the row = the batch position list[j0 + s])
+template <bool DROP>
 __device__ __forceinline__ void st_rnn_step(const SpTrainNet &net, const float *__restrict__ P, int l, int t, const float *X, int64_t j0, int nvalid,
-                                            float *hs, int wave, int lane) {
+                                            float *hs, int wave, int lane, const SpDrop *dr, int dnet, const int32_t *list, int64_t bn, float *ms) {
     const int H = net.H, R = net.R, T = net.T, s = lane & 31;
     const bool svalid = s < nvalid;
     const float *Wih = P + net.oWih[l], *Whh = P + net.oWhh[l], *bih = P + net.oBih[l], *bhh = P + net.oBhh[l];
@@ -98,6 +102,12 @@ __device__ __forceinline__ void st_rnn_step(const SpTrainNet &net, const float *
     const float *hin = hs + ((size_t)((l > 0 ? l - 1 : 0) * T + t) * H) * kTrTS;
     const float *hprev = hs + ((size_t)(l * T + (t > 0 ? t - 1 : 0)) * H) * kTrTS;
     float *hout = hs + ((size_t)(l * T + t) * H) * kTrTS;
+    [[maybe_unused]] const float *msin = nullptr;
+    [[maybe_unused]] float *mout = nullptr;
+    if constexpr (DROP) {
+        msin = ms + ((size_t)((l > 0 ? l - 1 : 0) * T + t) * H) * kTrTS;
+        mout = ms + ((size_t)(l * T + t) * H) * kTrTS;
+    }
     const int nt_count = (H + 31) / 32;
     for (int nt = wave; nt < nt_count; nt += kTrWaves) {
         const int n0 = nt * 32;
@@ -105,6 +115,9 @@ __device__ __forceinline__ void st_rnn_step(const SpTrainNet &net, const float *
         if (l == 0)
             acc = tr_mfma([&](int i, int p) { return n0 + i < H ? Wih[(size_t)(n0 + i) * R + p] : 0.0f; },
                           [&](int p, int j) { return svalid ? xrow[p] : 0.0f; }, R, acc, lane);
+        else if constexpr (DROP)
+            acc = tr_mfma([&](int i, int p) { return n0 + i < H ? Wih[(size_t)(n0 + i) * H + p] : 0.0f; },
+                          [&](int p, int j) { return msin[p * kTrTS + j] * hin[p * kTrTS + j]; }, H, acc, lane);
         else
             acc = tr_mfma([&](int i, int p) { return n0 + i < H ? Wih[(size_t)(n0 + i) * H + p] : 0.0f; },
                           [&](int p, int j) { return hin[p * kTrTS + j]; }, H, acc, lane);
@@ -116,18 +129,34 @@ __device__ __forceinline__ void st_rnn_step(const SpTrainNet &net, const float *
             const int n = n0 + tr_row(r, lane);
             if (n < H) hout[n * kTrTS + s] = st_tanh(acc[r] + (bih[n] + bhh[n]));
         }
+        if constexpr (DROP) {
+            if (l < net.L - 1) {
+                const int64_t row = st_clamp(svalid ? list[j0 + s] : 0, bn);
+#pragma unroll
+                for (int q = 0; q < 4; q++) { // registers 4 q .. 4 q + 3: four consecutive units, one Philox block
+                    float m[4];
+                    sp_drop4(*dr, dnet, row, t, l, (n0 + tr_row(4 * q, lane)) >> 2, m);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int n = n0 + tr_row(4 * q + j, lane);
+                        if (n < H) mout[n * kTrTS + s] = m[j];
+                    }
+                }
+            }
+        }
     }
 }
 
 // the whole network behind the convolutions on one tile: recurrence into hs, then the head on LDS (layer l writes buffer l & 1; layer 0
 // reads the top layer's last hidden state, copied into buffer 1).  SAVE: the head's hidden pre-activations also go to zsave, as
 // inst_mlp_train.hip's mt_forward keeps them
-template <bool SAVE>
+template <bool SAVE, bool DROP>
 __device__ __forceinline__ void st_forward(const SpTrainNet &net, const float *__restrict__ P, const float *X, int64_t j0, int nvalid, float *hs,
-                                           float *lds, float *zsave, int tid, int wave, int lane) {
+                                           float *lds, float *zsave, int tid, int wave, int lane, const SpDrop *dr, int dnet, const int32_t *list,
+                                           int64_t bn, float *ms) {
     for (int t = 0; t < net.T; t++)
         for (int l = 0; l < net.L; l++) {
-            st_rnn_step(net, P, l, t, X, j0, nvalid, hs, wave, lane);
+            st_rnn_step<DROP>(net, P, l, t, X, j0, nvalid, hs, wave, lane, dr, dnet, list, bn, ms);
             __syncthreads();
         }
     const float *htop = hs + ((size_t)((net.L - 1) * net.T + net.T - 1) * net.H) * kTrTS;
@@ -151,246 +180,19 @@ __global__ __launch_bounds__(kTrThreads) void k_sp_train_rnn(SpTrainBatch b, con
                                                              const float *__restrict__ tgt, const int32_t *__restrict__ lists,
                                                              const int32_t *__restrict__ counts, int agent, int team, float gamma,
                                                              float *__restrict__ partial, float *step) {
-    extern __shared__ float lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int count = counts[2 * agent + team];
-    if (count == 0) return; // an empty team takes no step (train.py:101): k_train_adam does nothing either
-    const int32_t *list = lists + ((int64_t)agent * 2 + team) * b.n;
-    if (blockIdx.x == 0 && tid == 0) step[0] += 1.0f; // (k_train_adam reads it after this launch)
-    const SpTrainNet &net = *netp;
-    const MlpTrainNet &hd = net.head;
-    const int nl = hd.nl, n_out = hd.d[nl], H = net.H, L = net.L, T = net.T, R = net.R, Rc = net.Rc;
-    float *out = partial + (size_t)blockIdx.x * net.Pp;
-    const size_t slice = (size_t)L * T * H * kTrTS;
-    float *hs = ws.hs + (size_t)blockIdx.x * slice, *ds = ws.ds + (size_t)blockIdx.x * slice;
-    float *zsave = ws.zs + (size_t)blockIdx.x * hd.Z;
-    float lacc = 0.0f;
-    float *red = lds + kStORed;
-    const float inv_n = 2.0f / (float)count; // mse_loss backward: 2 (x - y) / numel
-    int32_t *rid = reinterpret_cast<int32_t *>(lds + kStORow);
-    int32_t *act = reinterpret_cast<int32_t *>(lds + kStOAct);
-    const float *zq = lds + (((nl - 1) & 1) ? kStOH1 : kStOH0); // the last layer's output
-    if ((int64_t)blockIdx.x * kTrTS >= count) // no tile: an all-zero partial behind the convolutions' part (slopes and loss below)
-        for (int p = net.oWih[0] + tid; p < net.P; p += kTrThreads) out[p] = 0.0f;
-    for (int tile = blockIdx.x; (int64_t)tile * kTrTS < count; tile += gridDim.x) {
-        const bool first = tile == (int)blockIdx.x;
-        const int base = tile * kTrTS, nvalid = count - base < kTrTS ? count - base : kTrTS;
-        const int64_t j0 = base;
-        if (tid < kTrTS) {
-            const int64_t s = st_clamp(tid < nvalid ? list[base + tid] : 0, b.n);
-            rid[tid] = (int32_t)st_clamp(b.idx[s], b.max_size);
-        }
-        __syncthreads();
-        // target network on the next states: y = r + gamma max_a Q'(s', a); y = r where done (train.py:121-134)
-        st_forward<false>(net, tgt, ws.Xt, j0, nvalid, hs, lds, nullptr, tid, wave, lane);
-        if (tid < kTrTS) {
-            float y = 0.0f;
-            int a = 0;
-            if (tid < nvalid) {
-                const int64_t r = rid[tid];
-                float m = zq[tid];
-                for (int j = 1; j < n_out; j++) m = fmaxf(m, zq[j * kTrSP + tid]);
-                const float rew = b.rewards[r * b.A + agent];
-                y = b.dones[r] ? rew : rew + gamma * m;
-                a = (int)b.actions[r * b.A + agent];
-                a = a < 0 ? 0 : (a >= n_out ? n_out - 1 : a);
-            }
-            lds[kStOY + tid] = y;
-            act[tid] = a;
-        }
-        __syncthreads();
-        // online network on the states: every h[l][t] in hs, the head's hidden pre-activations in zsave
-        st_forward<true>(net, prm, ws.X, j0, nvalid, hs, lds, zsave, tid, wave, lane);
-        { // dL/dQ into the last layer's dZ buffer: 2 (Q - y) / n at the taken action, 0 elsewhere and on padding columns
-            float *dq = lds + (((nl - 1) & 1) ? kStODA : kStODB);
-            for (int e = tid; e < n_out * kTrTS; e += kTrThreads) {
-                const int j = e / kTrTS, s = e % kTrTS;
-                float g = 0.0f;
-                if (s < nvalid && j == act[s]) g = inv_n * (zq[j * kTrSP + s] - lds[kStOY + s]);
-                dq[j * kTrSP + s] = g;
-            }
-            if (tid < nvalid) {
-                const float diff = zq[act[tid] * kTrSP + tid] - lds[kStOY + tid];
-                lacc += diff * diff;
-            }
-        }
-        __syncthreads();
-        // the head's backward, last layer .. first, as k_mlp_train_grad: dz of layer l in DA (l odd) or DB (l even), dh into the other;
-        // layer 0's input is the top hidden state (no activation in front of it), and its dh -- left in DA -- is the recurrence's
-        for (int l = nl - 1; l >= 0; l--) {
-            {
-                const float *dz = lds + ((l & 1) ? kStODA : kStODB);
-                float *dh = lds + ((l & 1) ? kStODB : kStODA);
-                float *zin = lds + ((l & 1) ? kStOH0 : kStOH1);
-                const int dk = hd.d[l], dn = hd.d[l + 1];
-                const float slope_in = l > 0 ? prm[hd.oA[l - 1]] : 1.0f;
-                {
-                    const float *src = l > 0 ? zsave + hd.zo[l - 1] : hs + ((size_t)((L - 1) * T + T - 1) * H) * kTrTS;
-                    for (int e = tid; e < dk * kTrTS; e += kTrThreads) zin[(e >> 5) * kTrSP + (e & 31)] = src[e];
-                    __syncthreads();
-                }
-                const int KT = (dk + 31) / 32, tiles = ((dn + 31) / 32) * KT;
-                for (int g = wave; g < tiles; g += kTrWaves) {
-                    const int n0 = (g / KT) * 32, k0 = (g % KT) * 32;
-                    const int k = k0 + (lane & 31), kc = k < dk ? k : dk - 1;
-                    tr_f32x16 acc = {};
-                    acc = tr_mfma([&](int i, int p) { return n0 + i < dn ? dz[(n0 + i) * kTrSP + p] : 0.0f; },
-                                  [&](int p, int j) {
-                                      const float z = zin[kc * kTrSP + p];
-                                      return k < dk ? (l == 0 ? z : tr_prelu(z, slope_in)) : 0.0f;
-                                  },
-                                  kTrTS, acc, lane);
-                    float *wg = out + hd.oW[l];
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int n = n0 + tr_row(r, lane);
-                        if (n < dn && k < dk) {
-                            float *w = wg + (size_t)n * dk + k;
-                            *w = first ? acc[r] : *w + acc[r];
-                        }
-                    }
-                }
-                if (tid < dn) { // bias gradient
-                    float s = 0.0f;
-                    for (int j = 0; j < kTrTS; j++) s += dz[tid * kTrSP + j];
-                    float *w = out + hd.oB[l] + tid;
-                    *w = first ? s : *w + s;
-                }
-                tr_backward_layer(prm + hd.oW[l], dk, dn, dz, dh, wave, lane);
-                __syncthreads();
-                if (l > 0) { // through the PReLU of layer l's input (torch's prelu backward); the slope's gradient: a fixed-shape tree sum per tile
-                    float sl = 0.0f;
-                    for (int e = tid; e < dk * kTrTS; e += kTrThreads) {
-                        const int k = e / kTrTS, s = e % kTrTS;
-                        const float z = zin[k * kTrSP + s], g = dh[k * kTrSP + s];
-                        const bool pz = z > 0.0f;
-                        dh[k * kTrSP + s] = pz ? g : slope_in * g;
-                        sl += pz ? 0.0f : z * g;
-                    }
-                    tr_block_sum(sl, red, tid);
-                    if (tid == 0) {
-                        float *w = out + hd.oA[l - 1];
-                        *w = first ? red[0] : *w + red[0];
-                    }
-                    __syncthreads();
-                }
-            }
-        }
-        const float *dhead = lds + kStODA; // [H][kTrSP]
-        // back through time: dz[l][t] = (1 - h^2) (W_ih[l+1]^T dz[l+1][t] + W_hh[l]^T dz[l][t+1] (+ dhead at the top, last step))
-        const int kt_count = (H + 31) / 32;
-        for (int t = T - 1; t >= 0; t--) {
-            for (int l = L - 1; l >= 0; l--) {
-                const float *Wup = prm + net.oWih[l < L - 1 ? l + 1 : l], *Whh = prm + net.oWhh[l];
-                const float *dzup = ds + ((size_t)((l < L - 1 ? l + 1 : l) * T + t) * H) * kTrTS;
-                const float *dzfut = ds + ((size_t)(l * T + (t < T - 1 ? t + 1 : t)) * H) * kTrTS;
-                const float *h = hs + ((size_t)(l * T + t) * H) * kTrTS;
-                float *dzo = ds + ((size_t)(l * T + t) * H) * kTrTS;
-                const bool top = l == L - 1 && t == T - 1;
-                for (int kt = wave; kt < kt_count; kt += kTrWaves) {
-                    const int k0 = kt * 32;
-                    tr_f32x16 acc = {};
-                    if (l < L - 1)
-                        acc = tr_mfma([&](int i, int p) { return k0 + i < H ? Wup[(size_t)p * H + k0 + i] : 0.0f; },
-                                      [&](int p, int j) { return dzup[p * kTrTS + j]; }, H, acc, lane);
-                    if (t < T - 1)
-                        acc = tr_mfma([&](int i, int p) { return k0 + i < H ? Whh[(size_t)p * H + k0 + i] : 0.0f; },
-                                      [&](int p, int j) { return dzfut[p * kTrTS + j]; }, H, acc, lane);
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int k = k0 + tr_row(r, lane), s = lane & 31;
-                        if (k < H) {
-                            const float g = acc[r] + (top ? dhead[k * kTrSP + s] : 0.0f);
-                            const float hv = h[k * kTrTS + s];
-                            dzo[k * kTrTS + s] = (1.0f - hv * hv) * g;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        { // gradient of the RNN input's convolution columns: dX[s][t][k] = sum_n W_ih[0][n][k] dz[0][t][n][s], k < Rc
-            const float *W0 = prm + net.oWih[0];
-            const int KT = (Rc + 31) / 32;
-            for (int g = wave; g < T * KT; g += kTrWaves) {
-                const int t = g / KT, k0 = (g % KT) * 32;
-                const float *dz0 = ds + ((size_t)t * H) * kTrTS;
-                tr_f32x16 acc = {};
-                acc = tr_mfma([&](int i, int p) { return k0 + i < Rc ? W0[(size_t)p * R + k0 + i] : 0.0f; }, [&](int p, int j) { return dz0[p * kTrTS + j]; },
-                              H, acc, lane);
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int k = k0 + tr_row(r, lane), s = lane & 31;
-                    if (k < Rc && s < nvalid) ws.dX[((size_t)(j0 + s) * T + t) * Rc + k] = acc[r];
-                }
-            }
-        }
-        // the recurrence's weight gradients, one product over all steps and the tile's rows per 32 x 32 block: p = 32 t + s
-        for (int l = 0; l < L; l++) {
-            const int dk = l == 0 ? R : H;
-            const float *dzl = ds + ((size_t)(l * T) * H) * kTrTS;
-            const float *hbelow = hs + ((size_t)((l > 0 ? l - 1 : 0) * T) * H) * kTrTS;
-            const float *hown = hs + ((size_t)(l * T) * H) * kTrTS;
-            const int KT = (dk + 31) / 32, HT = (H + 31) / 32;
-            for (int g = wave; g < HT * KT; g += kTrWaves) { // dW_ih[n][k] = sum_{t, s} dz[l][t][n][s] in[l][t][k][s]
-                const int n0 = (g / KT) * 32, k0 = (g % KT) * 32;
-                const int k = k0 + (lane & 31), kc = k < dk ? k : dk - 1;
-                tr_f32x16 acc = {};
-                acc = tr_mfma([&](int i, int p) { return n0 + i < H ? dzl[((size_t)(p >> 5) * H + n0 + i) * kTrTS + (p & 31)] : 0.0f; },
-                              [&](int p, int j) {
-                                  const int t = p >> 5, s = p & 31;
-                                  float x;
-                                  if (l == 0) x = s < nvalid ? ws.X[((size_t)(j0 + (s < nvalid ? s : 0)) * T + t) * R + kc] : 0.0f;
-                                  else x = hbelow[((size_t)t * H + kc) * kTrTS + s];
-                                  return k < dk ? x : 0.0f;
-                              },
-                              T * kTrTS, acc, lane);
-                float *wg = out + net.oWih[l];
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int n = n0 + tr_row(r, lane);
-                    if (n < H && k < dk) {
-                        float *w = wg + (size_t)n * dk + k;
-                        *w = first ? acc[r] : *w + acc[r];
-                    }
-                }
-            }
-            for (int g = wave; g < HT * HT; g += kTrWaves) { // dW_hh[n][k] = sum_{t >= 1, s} dz[l][t][n][s] h[l][t-1][k][s]
-                const int n0 = (g / HT) * 32, k0 = (g % HT) * 32;
-                const int k = k0 + (lane & 31), kc = k < H ? k : H - 1;
-                tr_f32x16 acc = {};
-                acc = tr_mfma([&](int i, int p) { return n0 + i < H ? dzl[((size_t)((p >> 5) + 1) * H + n0 + i) * kTrTS + (p & 31)] : 0.0f; },
-                              [&](int p, int j) {
-                                  const float x = hown[((size_t)(p >> 5) * H + kc) * kTrTS + (p & 31)];
-                                  return k < H ? x : 0.0f;
-                              },
-                              (T - 1) * kTrTS, acc, lane);
-                float *wg = out + net.oWhh[l];
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int n = n0 + tr_row(r, lane);
-                    if (n < H && k < H) {
-                        float *w = wg + (size_t)n * H + k;
-                        *w = first ? acc[r] : *w + acc[r];
-                    }
-                }
-            }
-            if (tid < H) { // bias_ih and bias_hh: the same gradient
-                float s = 0.0f;
-                for (int p = 0; p < T * kTrTS; p++) s += dzl[((size_t)(p >> 5) * H + tid) * kTrTS + (p & 31)];
-                float *w1 = out + net.oBih[l] + tid, *w2 = out + net.oBhh[l] + tid;
-                const float v = first ? s : *w1 + s;
-                *w1 = v;
-                *w2 = v;
-            }
-        }
-        __syncthreads(); // (the next tile rewrites rid, the slices and the LDS buffers)
-    }
-    // the loss: a fixed-shape tree sum over the workgroup
-    __syncthreads();
-    tr_block_sum(lacc, red, tid);
-    if (tid == 0) out[net.P] = red[0];
+#define SP_TRAIN_DROPOUT 0
+#include "susnet_spatial_train_rnn_body.h"
+#undef SP_TRAIN_DROPOUT
+}
+// the dropout form (susnet_spatial_train_step_dropout): dr.agent == agent; ms: [G][(L - 1) T H 32] floats
+__global__ __launch_bounds__(kTrThreads) void k_sp_train_rnn_dropout(SpTrainBatch b, const SpTrainNet *__restrict__ netp, SpTrainWs ws,
+                                                                     const float *__restrict__ prm, const float *__restrict__ tgt,
+                                                                     const int32_t *__restrict__ lists, const int32_t *__restrict__ counts, int agent,
+                                                                     int team, float gamma, float *__restrict__ partial, float *step, SpDrop dr,
+                                                                     float *ms) {
+#define SP_TRAIN_DROPOUT 1
+#include "susnet_spatial_train_rnn_body.h"
+#undef SP_TRAIN_DROPOUT
 }
 
 // ---- k_sp_train_conv_bwd: the convolutions' backward of one update; workgroup blockIdx.x of gridDim.x owns images blockIdx.x + i gridDim.x ----
@@ -481,14 +283,22 @@ hipError_t sp_train_select_launch(const SpTrainBatch &b, const SpTrainNet &net0,
 
 hipError_t sp_train_update_launch(const SpTrainBatch &b, const SpTrainNet *net, const SpTrainWs &ws, const float *prm, const float *tgt,
                                   const int32_t *lists, const int32_t *counts, int agent, int team, float gamma, float *partial, float *step, int G,
-                                  int Gconv, hipStream_t st) {
+                                  int Gconv, hipStream_t st, const SpDrop *dr, float *ms) {
     // the recurrence kernel's dynamic-LDS ceiling, set once per device (not repeated inside a capture after the first eager step)
-    static LdsOptIn opted;
-    if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_sp_train_rnn), kStLdsBytes, opted)) return e;
+    static LdsOptIn opted, opted_drop;
+    if (hipError_t e = dr ? lds_opt_in(reinterpret_cast<const void *>(&k_sp_train_rnn_dropout), kStLdsBytes, opted_drop)
+                          : lds_opt_in(reinterpret_cast<const void *>(&k_sp_train_rnn), kStLdsBytes, opted))
+        return e;
     hipLaunchKernelGGL(k_sp_train_conv, dim3((unsigned)Gconv), dim3(kStConvThreads), 0, st, b, net, ws, prm, tgt, lists, counts, agent, team);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_sp_train_rnn, dim3((unsigned)G), dim3(kTrThreads), kStLdsBytes, st, b, net, ws, prm, tgt, lists, counts, agent, team, gamma,
-                       partial, step);
+    if (dr) { // (the update's agent goes into the mask's counter)
+        SpDrop d = *dr;
+        d.agent = agent;
+        hipLaunchKernelGGL(k_sp_train_rnn_dropout, dim3((unsigned)G), dim3(kTrThreads), kStLdsBytes, st, b, net, ws, prm, tgt, lists, counts, agent,
+                           team, gamma, partial, step, d, ms);
+    } else
+        hipLaunchKernelGGL(k_sp_train_rnn, dim3((unsigned)G), dim3(kTrThreads), kStLdsBytes, st, b, net, ws, prm, tgt, lists, counts, agent, team,
+                           gamma, partial, step);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_sp_train_conv_bwd, dim3((unsigned)G), dim3(kStConvThreads), 0, st, b, net, ws, prm, lists, counts, agent, team, partial);
     return hipGetLastError();

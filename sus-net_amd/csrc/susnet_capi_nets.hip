@@ -7,6 +7,7 @@
 #include "susnet_qnet.h"
 #include "susnet_dense.h"
 #include "susnet_spatial.h"
+#include "susnet_dropout.h"
 #include "susnet_window.h"
 #include "susnet_host.h"
 
@@ -255,6 +256,29 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
                    S((long long)kSpLdsBudget));
     HIP_TRY(spatial_conv_launch(ca, static_cast<hipStream_t>(stream)));
     HIP_TRY(spatial_rnn_launch(ra, static_cast<hipStream_t>(stream)));
+    return SUSNET_OK;
+}
+
+// susnet_rnn_dropout_mask: the multipliers susnet_spatial_train_step_dropout applies, written out (the kernel: inst_qnet_spatial.hip)
+extern "C" int susnet_rnn_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agent, int32_t layers, int64_t n,
+                                       int32_t T, int32_t H, float *out, void *stream) {
+    if (!env) return fail(SUSNET_E_INVALID, "susnet_rnn_dropout_mask: null env");
+    const Refuse bad{env, "susnet_rnn_dropout_mask"};
+    const auto range = [&](const char *field, long long v, long long lo, long long hi) {
+        return std::string(field) + " = " + std::to_string(v) + " (served: " + std::to_string(lo) + " .. " + std::to_string(hi) + ")";
+    };
+    if (!drop) return bad("drop is NULL");
+    if (net < 0 || net > 1) return bad(range("net", net, 0, 1));
+    if (agent < 0 || agent > 4095) return bad(range("agent", agent, 0, 4095));
+    if (layers < 2 || layers > kSpMaxRnn) return bad(range("layers", layers, 2, kSpMaxRnn));
+    if (n < 1 || n > (1ll << 40)) return bad(range("n", n, 1, 1ll << 40));
+    if (T < 1 || T > SUSNET_SPATIAL_MAX_T) return bad(range("T", T, 1, SUSNET_SPATIAL_MAX_T));
+    if (H < 1 || H > kDnMaxHidden) return bad(range("H", H, 1, kDnMaxHidden));
+    SpDrop dr{};
+    if (int rc = drop_check(bad, "drop->", *drop, n, dr)) return rc;
+    if (!out || misaligned(out)) return bad("out is NULL or not 4-byte aligned");
+    dr.agent = agent;
+    HIP_TRY(rnn_dropout_mask_launch(dr, net, layers, n, T, H, out, static_cast<hipStream_t>(stream)));
     return SUSNET_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "susnet_train.h"
 #include "susnet_mlp_train.h"
 #include "susnet_spatial_train.h"
+#include "susnet_dropout.h"
 #include "susnet_host.h"
 
 using namespace susnet;
@@ -344,7 +345,7 @@ extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io 
 struct SpTrainPlan : TrWorkspace {
     SpTrainNet net[2];
     int64_t G = 1, Gconv = 1;
-    uint64_t off_X = 0, off_Xt = 0, off_act = 0, off_dact = 0, off_dX = 0, off_tact = 0, off_hs = 0, off_ds = 0, off_zs = 0, off_nets = 0, bytes = 0;
+    uint64_t off_X = 0, off_Xt = 0, off_act = 0, off_dact = 0, off_dX = 0, off_tact = 0, off_hs = 0, off_ds = 0, off_zs = 0, off_nets = 0, off_ms = 0, bytes = 0;
 };
 // one enabled team's network: the spatial rules (those of susnet_spatial_forward) stated here, the head's by the shared stack checks
 static int sp_train_net(const Refuse &bad, int t, const susnet_spatial_net &sn, const susnet_dqn_team &tm, SpTrainNet &net) {
@@ -424,9 +425,11 @@ static int sp_train_net(const Refuse &bad, int t, const susnet_spatial_net &sn, 
     net.Pp = (net.P + 1 + 3) / 4 * 4;
     return SUSNET_OK;
 }
-static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *io, SpTrainPlan &pl) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_train_step: null env / io");
-    const Refuse bad{env, "susnet_spatial_train_step"};
+// `dropout`: the plan of susnet_spatial_train_step_dropout (`entry` its name) -- the multipliers' slices behind everything else
+static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *io, SpTrainPlan &pl, bool dropout = false,
+                         const char *entry = "susnet_spatial_train_step") {
+    if (!env || !io) return fail(SUSNET_E_INVALID, std::string(entry) + ": null env / io");
+    const Refuse bad{env, entry};
     const auto S = [](long long v) { return std::to_string(v); };
     if (env->c.n_imp != 1)
         return bad("n_imposters = " + S(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
@@ -434,7 +437,7 @@ static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *i
     if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + S(env->c.A) + " (served: 2 .. 16)");
     if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + S(io->n) + " (served: 0 .. 2^30)");
     if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
-    int64_t pmax = 4, T = 1, R = 1, Rc = 1, asz = 0, maxsz = 1, slice = 1, Z = 4;
+    int64_t pmax = 4, T = 1, R = 1, Rc = 1, asz = 0, maxsz = 1, slice = 1, mslice = 1, Z = 4;
     int first = -1;
     for (int tm = 0; tm < 2; tm++) {
         pl.net[tm] = SpTrainNet{};
@@ -452,6 +455,7 @@ static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *i
         R = std::max<int64_t>(R, net.R), Rc = std::max<int64_t>(Rc, net.Rc), asz = std::max<int64_t>(asz, net.asz);
         maxsz = std::max<int64_t>(maxsz, net.maxsz);
         slice = std::max<int64_t>(slice, (int64_t)net.L * net.T * net.H * kTrTS);
+        mslice = std::max<int64_t>(mslice, (int64_t)(net.L - 1) * net.T * net.H * kTrTS);
         Z = std::max<int64_t>(Z, net.head.Z);
     }
     for (int d = 0; d < 3; d++) {
@@ -477,6 +481,7 @@ static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *i
     take(pl.off_ds, (uint64_t)pl.G * (uint64_t)slice);
     take(pl.off_zs, (uint64_t)pl.G * (uint64_t)Z);
     take(pl.off_nets, 2 * (sizeof(SpTrainNet) + 3) / 4);
+    if (dropout) take(pl.off_ms, (uint64_t)pl.G * (uint64_t)mslice);
     pl.bytes = o;
     return SUSNET_OK;
 }
@@ -489,14 +494,32 @@ extern "C" int susnet_spatial_train_workspace_bytes(const susnet_env *env, const
     return SUSNET_OK;
 }
 
-// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
-extern "C" int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream) {
+extern "C" int susnet_spatial_train_dropout_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out) {
     SpTrainPlan pl;
-    if (int rc = sp_train_plan(env, io, pl)) return rc;
-    const Refuse bad{env, "susnet_spatial_train_step"};
+    if (int rc = sp_train_plan(env, io, pl, true, "susnet_spatial_train_step_dropout")) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_dropout_workspace_bytes: null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only.
+// `drop` (susnet_spatial_train_step_dropout): two structs, [0] imposters, [1] crew; a team with a mask (a p > 0 and more than one RNN layer)
+// takes k_sp_train_rnn_dropout, any other the plain kernel
+static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream) {
+    const char *entry = drop ? "susnet_spatial_train_step_dropout" : "susnet_spatial_train_step";
+    SpTrainPlan pl;
+    if (int rc = sp_train_plan(env, io, pl, drop != nullptr, entry)) return rc;
+    const Refuse bad{env, entry};
+    SpDrop dr[2] = {};
+    bool masked[2] = {false, false};
+    for (int tm = 0; drop && tm < 2; tm++) {
+        if (!io->team[tm].enabled) continue;
+        if (int rc = drop_check(bad, "drop[" + std::to_string(tm) + "].", drop[tm], io->n, dr[tm])) return rc;
+        masked[tm] = (dr[tm].thr[0] != 0u || dr[tm].thr[1] != 0u) && pl.net[tm].L > 1;
+    }
     if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
-        return bad("workspace missing, smaller than susnet_spatial_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
-                   " bytes) or not 256-byte aligned");
+        return bad(std::string("workspace missing, smaller than ") + (drop ? "susnet_spatial_train_dropout_workspace_bytes (" : "susnet_spatial_train_workspace_bytes (") +
+                   std::to_string((unsigned long long)pl.bytes) + " bytes) or not 256-byte aligned");
     if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
     if (!io->actions) return bad("actions is NULL");
     if (!io->rewards) return bad("rewards is NULL");
@@ -543,10 +566,17 @@ extern "C" int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_t
             const susnet_dqn_team &T = io->team[tm];
             if (!T.enabled) continue;
             HIP_TRY(sp_train_update_launch(b, nets + tm, w, T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, T.step,
-                                           (int)pl.G, (int)pl.Gconv, st));
+                                           (int)pl.G, (int)pl.Gconv, st, masked[tm] ? &dr[tm] : nullptr, masked[tm] ? at(pl.off_ms) : nullptr));
             hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
                                partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
             HIP_TRY(hipGetLastError());
         }
     return SUSNET_OK;
+}
+extern "C" int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream) {
+    return spatial_train_step(env, io, nullptr, stream);
+}
+extern "C" int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream) {
+    if (env && io && !drop) return Refuse{env, "susnet_spatial_train_step_dropout"}("drop is NULL");
+    return spatial_train_step(env, io, drop, stream);
 }

@@ -26,6 +26,9 @@
 //   k_train_adam         susnet_train.h's, as it is (susnet_capi_train.hip launches it).
 // The two gradient kernels write disjoint parts of the same partial: [0, oWih[0]) the convolutions, [oWih[0], P] the rest and the loss sum.
 // Grid: G = min(SUSNET_SPATIAL_TRAIN_MAX_GRID, n T, 64 MiB / (4 Pp)) workgroups, at least 1, for both.
+// susnet_spatial_train_step_dropout is the same step with k_sp_train_rnn_dropout in k_sp_train_rnn's place (one body text, compiled twice:
+// susnet_spatial_train_rnn_body.h): both recurrences under nn.RNN's inter-layer dropout, masks from susnet_dropout.h, the multipliers of a
+// tile kept in a third slice per workgroup ([l][t][unit][32], l < L - 1) behind the plain step's workspace.
 // Data a workgroup hands from one thread to another through global memory is separated by a workgroup barrier (release / acquire at
 // workgroup scope); nothing is ever read that another workgroup of the same launch wrote.
 #pragma once
@@ -37,6 +40,8 @@
 #include "susnet_mlp_train.h"
 
 namespace susnet {
+
+struct SpDrop; // susnet_dropout.h: with one (and `ms`, [G][(L - 1) T H 32] floats) the update's recurrence kernel is k_sp_train_rnn_dropout
 
 constexpr int kStConvThreads = 256;
 constexpr int kStMaxGrid = SUSNET_SPATIAL_TRAIN_MAX_GRID;
@@ -83,6 +88,6 @@ hipError_t sp_train_select_launch(const SpTrainBatch &b, const SpTrainNet &net0,
                                   int32_t *counts, float *gacc0, float *gacc1, float *losses, hipStream_t st);
 hipError_t sp_train_update_launch(const SpTrainBatch &b, const SpTrainNet *net, const SpTrainWs &ws, const float *prm, const float *tgt,
                                   const int32_t *lists, const int32_t *counts, int agent, int team, float gamma, float *partial, float *step, int G,
-                                  int Gconv, hipStream_t st);
+                                  int Gconv, hipStream_t st, const SpDrop *dr = nullptr, float *ms = nullptr);
 
 } // namespace susnet

@@ -259,7 +259,7 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
                    generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
-                   dense_train: bool = False, featurizer=None) -> EpisodicMetricHandler:
+                   dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: writes ``config.json``, builds ring, policy, trainer
     and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
     entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
@@ -275,14 +275,19 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     ``susnet_agent_policy_actions``), the trainer is built ``featurizer=featurizer, spatial=True`` (a trained team
     ``susnet_spatial_train_step`` does not serve takes ``torch_train_step``), the ring has ``trajectory_size=T``; ``config.json`` names
     ``spatial_dqn`` and ``global`` / ``perspective`` and, as ``train_step``, the learner the run takes; the checkpoints are ``<team>_spatial_dqn_<p>.pt``.  A ``SpatialDQN`` the kernels do not
-    act for is a ``ValueError`` that says which bound failed."""
+    act for is a ``ValueError`` that says which bound failed.  ``rnn_dropout_seed`` (with ``featurizer``; None: models with dropout between
+    their RNN layers train through ``torch_train_step``): the trainer is built with it, so such models -- the reference's own
+    ``rnn_layers: 3, rnn_dropout: 0.2`` -- LEARN under the library's dropout masks (``susnet_spatial_train_step_dropout``), online and target
+    network; they ACT in eval mode (put them there with ``model.eval()``: ``susnet_spatial_forward`` is the eval-mode forward and refuses a
+    training-mode model with dropout, as before; the device train step does not put them back into training mode).  The seed is written
+    into ``config.json``."""
     components = list(components)
     sequence_length = int(sequence_length)
     if featurizer is not None:
         return _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size,
                                        replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps,
                                        train_imposter, train_crew, experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves,
-                                       target_update_interval, generator, episode_log)
+                                       target_update_interval, generator, episode_log, rnn_dropout_seed)
     if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
         raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
     if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
@@ -349,7 +354,7 @@ def spatial_unserved_reason(env, featurizer, model, n_actions: int, T: int) -> O
 def _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size, replay_prepopulate_steps,
                             batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter, train_crew,
                             experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves, target_update_interval, generator,
-                            episode_log) -> EpisodicMetricHandler:
+                            episode_log, rnn_dropout_seed=None) -> EpisodicMetricHandler:
     """``run_experiment`` for ``SpatialDQN`` models on a Global / Perspective featurizer (see there)."""
     from .features import GlobalFeaturizer
 
@@ -375,12 +380,13 @@ def _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featuriz
                                 learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval,
                                 featurizer_type="global" if isinstance(featurizer, GlobalFeaturizer) else "perspective")
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, [], lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
-                                   train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True)
+                                   train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True, rnn_dropout_seed=rnn_dropout_seed)
     scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
     metrics = EpisodicMetricHandler()
     ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
     # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
     config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
+    config["rnn_dropout_seed"] = rnn_dropout_seed
     (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
     if replay_prepopulate_steps > 0:
         ring.populate_fused(env, replay_prepopulate_steps)

@@ -93,11 +93,17 @@ class DeviceDQNTeamTrainer:
     (``uses_dense``), before the torch path.  ``sequence_length``: the window length T the trained networks read (their input is
     ``T * F`` wide); None (default): T is taken from the networks' input width, ``dims[0] / F``.
     ``spatial=True`` (opt-in): trained ``SpatialDQN``s that ``susnet_spatial_train_step`` serves, with a Global or Perspective
-    ``featurizer``, take that step (``uses_spatial``) -- after ``uses_hip`` and ``uses_dense``, before the torch path."""
+    ``featurizer``, take that step (``uses_spatial``) -- after ``uses_hip`` and ``uses_dense``, before the torch path.
+    ``rnn_dropout_seed`` (opt-in, with ``spatial=True``): ``SpatialDQN``s with ``rnn_dropout > 0`` between several RNN layers are served
+    too, by ``susnet_spatial_train_step_dropout``: the online network always under dropout (``train_step`` puts it in training mode,
+    train.py:104), the target network iff its module is in training mode (it is after ``create_copy()``, as in the reference); the masks
+    are the library's (include/susnet.h), keyed by the seed and ``dropout_steps`` (the count of such steps: the next step's ``offset``).
+    The two teams share seed and offset: an update's masks are drawn per (agent, batch row), and for one agent the teams' lists are
+    disjoint rows of the batch (a row is the imposter's or the crew's), so no two updates of a step read the same mask elements."""
 
     def __init__(self, env, imposter_model: nn.Module, crew_model: Optional[nn.Module], components: Sequence[str], lr: float, gamma: float,
                  train_imposter: bool = True, train_crew: bool = True, policy=None, featurizer=None, dense: bool = False,
-                 sequence_length: Optional[int] = None, spatial: bool = False):
+                 sequence_length: Optional[int] = None, spatial: bool = False, rnn_dropout_seed: Optional[int] = None):
         if env.n_imposters >= 2:
             raise ValueError("one imposter is served: the reference's train_step fails on two or more, `(batch.imposters == agent_idx).view(-1)` "
                              "(src/train.py:83) has n_imposters * N entries")
@@ -145,7 +151,10 @@ class DeviceDQNTeamTrainer:
                       and all(d is not None for d, tr in zip(self._dense_dims, self.trained) if tr) and self._dense_served())
         self._dense_bufs = None  # (n, gathered states, gathered next states, spec + rows of states, spec + rows of next states)
         # the spatial step: each trained team's SpatialDQN as susnet_spatial_train_step reads it
-        self._spatial_nets = [self._spatial_net(m) if tr else None for m, tr in zip(self.models, self.trained)]
+        self.rnn_dropout_seed = None if rnn_dropout_seed is None else int(rnn_dropout_seed) & (2**64 - 1)
+        self.dropout_steps = 0
+        self._spatial_nets = [self._spatial_net(m, dropout=self.rnn_dropout_seed is not None) if tr else None
+                              for m, tr in zip(self.models, self.trained)]
         self.spatial = (bool(spatial) and self.device.type == "cuda" and any(self.trained) and self._spatial_featurizer() is not None
                         and all(d is not None for d, tr in zip(self._spatial_nets, self.trained) if tr) and self._spatial_served())
         self._spatial_bufs = None  # (n, T, gathered states, gathered next states, obs of states, obs of next states, Global non-spatial rows x 2)
@@ -253,15 +262,15 @@ class DeviceDQNTeamTrainer:
             return "global" if isinstance(f, GlobalFeaturizer) else "persp"
         return None
 
-    def _spatial_net(self, model):
+    def _spatial_net(self, model, dropout: bool = False):
         """What ``susnet_spatial_train_step`` needs to know of a ``SpatialDQN`` that ``SpatialQNet`` serves and whose training-mode forward
-        the kernels compute (no dropout between RNN layers), or None."""
+        the kernels compute (no dropout between RNN layers; with ``dropout``: ``susnet_spatial_train_step_dropout`` computes it), or None."""
         stack = _spatial_stack(model)
         if stack is None or SpatialQNet(self.env, model) is None:
             return None
         rnn = stack["rnn"]
-        if rnn.dropout > 0 and rnn.num_layers > 1:
-            return None  # (nn.RNN drops out between layers in training mode: the kernels do not)
+        if rnn.dropout > 0 and rnn.num_layers > 1 and not dropout:
+            return None  # (nn.RNN drops out between layers in training mode: the plain kernels do not)
         convs = stack["convs"]
         # parameters() order must be the flat layout the kernels assume: convolutions, RNN layer by layer, head
         names = [n for n, _ in model.named_parameters()]
@@ -272,7 +281,21 @@ class DeviceDQNTeamTrainer:
         cfg = model.config
         return dict(N=int(cfg["input_image_size"]), C=convs[0].in_channels, Fn=int(cfg["non_spatial_input_size"]), k=stack["k"],
                     convs=[(m.out_channels, m.stride[0], m.padding[0], m.dilation[0]) for m in convs], layers=rnn.num_layers,
-                    hidden=rnn.hidden_size, dims=stack["dims"])
+                    hidden=rnn.hidden_size, dims=stack["dims"], p=float(rnn.dropout) if rnn.num_layers > 1 else 0.0)
+
+    def _spatial_dropout(self):
+        """The two ``susnet_rnn_dropout`` ([imposter, crew]) of the next dropout step, or None where no trained team has dropout to apply."""
+        if self.rnn_dropout_seed is None or not any(d is not None and d["p"] > 0 for d, tr in zip(self._spatial_nets, self.trained) if tr):
+            return None
+        drop = (L.RnnDropout * 2)()
+        for t in range(2):
+            d = self._spatial_nets[t]
+            if self.trained[t] and d is not None:
+                target = self.targets[t]
+                drop[t].p[0] = d["p"]  # train_step: model.train() (train.py:104)
+                drop[t].p[1] = d["p"] if target is not None and target.training else 0.0
+            drop[t].seed, drop[t].offset, drop[t].row_base = self.rnn_dropout_seed, self.dropout_steps, 0
+        return drop
 
     def _spatial_io(self, T: int) -> "L.SpatialTrainIO":
         io = L.SpatialTrainIO()
@@ -434,7 +457,9 @@ class DeviceDQNTeamTrainer:
         io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
         io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
         io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
-        self._workspace_and_losses(io, env.lib.susnet_spatial_train_workspace_bytes)
+        drop = self._spatial_dropout()
+        self._workspace_and_losses(io, env.lib.susnet_spatial_train_workspace_bytes if drop is None
+                                   else env.lib.susnet_spatial_train_dropout_workspace_bytes)
         with torch.cuda.device(self.device):
             if n > 0:
                 dt = env._ROW_DTYPES[rows.dtype]
@@ -446,7 +471,11 @@ class DeviceDQNTeamTrainer:
                     base = non.shape[-1]
                     g[..., :base] = non.view(n, T, 1, base)
                     next_g[..., :base] = next_non.view(n, T, 1, base)
-            L.check(env.lib.susnet_spatial_train_step(env._h, C.byref(io), env._stream()))
+            if drop is None:
+                L.check(env.lib.susnet_spatial_train_step(env._h, C.byref(io), env._stream()))
+            else:
+                L.check(env.lib.susnet_spatial_train_step_dropout(env._h, C.byref(io), drop, env._stream()))
+                self.dropout_steps += 1  # (after the check: a refused call does not use up an offset)
         return self._losses.clone()
 
     def _sync_policy_version(self):
