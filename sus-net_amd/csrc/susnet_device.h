@@ -436,7 +436,7 @@ __device__ __forceinline__ float lds_reward_lookup(uint32_t byte_index) { return
 
 // The byte-parallel rollouts (susnet_swar.h GroupWords) stage the action-stream words of one GROUP of ticks behind the tables:
 // at most 20 words x 64 environments (12 agents in a shuffled order: 5 words per tick, 4 ticks; cfg4: 3 words per tick -- with two lanes per
-// environment 24 words x 32)
+// environment 24 words x 32); tagging with 11 / 12 shuffled agents needs 24 x 64 and borrows the rest from the rank tables (kGroupWordsWord below)
 constexpr uint32_t kGroupWords = 1280;
 // ... and, in the fused rollouts of those kernels, the per-environment cell -> job map behind the group words (susnet_swar.h JobMap:
 // one 64-byte row per cell value x | y << 4 of an N x N grid)
@@ -446,8 +446,17 @@ __host__ __device__ inline uint32_t lds_core_words(int A, int J, bool generic, b
 }
 
 // first LDS word of the group-words area (carve_lds: behind the tables; compiled-in configurations have no store columns)
+// (tagging with 11 / 12 agents in a shuffled order: ranges of 17 / 18 pack three action draws into a word -- SIX words per tick, 24 x 64 per
+// group.  The 256 words the area lacks are the tail of the turn-rank tables right below it, which only games of at most 8 agents build:
+// susnet_swar.h RankLut::kOk)
 template <class S>
-__device__ __forceinline__ constexpr uint32_t kGroupWordsWord() { static_assert(!S::kGeneric, "compiled-in configurations"); return kTableWords; }
+constexpr uint32_t kGroupWordsNeeded() { return (uint32_t)S::kAw.W * 4u * 64u; }
+template <class S>
+__device__ __forceinline__ constexpr uint32_t kGroupWordsWord() {
+    static_assert(!S::kGeneric, "compiled-in configurations");
+    static_assert(kGroupWordsNeeded<S>() <= kGroupWords || (S::kA > 8 && kGroupWordsNeeded<S>() <= kGroupWords + 672u), "group words: the area, or the area and the unused rank table 2");
+    return kGroupWordsNeeded<S>() <= kGroupWords ? kTableWords : kTableWords + kGroupWords - kGroupWordsNeeded<S>();
+}
 
 // generic flavour: [index][lane] columns in LDS (cell in bits 0-7, tag count in bits 8-15 of one word)
 struct LdsStore {
@@ -496,17 +505,24 @@ struct PackedBytes<N_, 2> { // 9..12 bytes: the pair + one more VGPR (the byte-p
     }
 };
 
-template <int A, int J>
+// WIDE_CNT: tag counts of 9 .. 12 agents (tagging games of that size: 48 bits; every other game keeps the one word)
+template <int A, int J, bool WIDE_CNT = false>
 struct RegStore {
     static_assert(A <= 12 && J <= 8, "RegStore packs at most 12 agents / 8 jobs");
     PackedBytes<A> xyw, actw;
     PackedBytes<(J > 0 ? J : 1)> jobw;
-    uint32_t cntw = 0; // 4 bits per agent (tag counts: tagging games have at most 8 agents here)
+    typename std::conditional<WIDE_CNT, uint64_t, uint32_t>::type cntw = 0; // 4 bits per agent (tag counts)
     __device__ __forceinline__ void init(uint32_t *, int, int, int) {}
     __device__ __forceinline__ uint32_t xy(int i) const { return xyw.get(i); }
     __device__ __forceinline__ void set_xy(int i, uint32_t cell) { xyw.set(i, cell); }
-    __device__ __forceinline__ uint32_t cnt(int i) const { return i < 8 ? (cntw >> (4 * (i & 7))) & 15u : 0u; }
-    __device__ __forceinline__ void set_cnt(int i, uint32_t v) { cntw = i < 8 ? (cntw & ~(15u << (4 * (i & 7)))) | ((v & 15u) << (4 * (i & 7))) : cntw; }
+    __device__ __forceinline__ uint32_t cnt(int i) const {
+        if constexpr (WIDE_CNT) return (uint32_t)(cntw >> (4 * (i & 15))) & 15u;
+        else return i < 8 ? (cntw >> (4 * (i & 7))) & 15u : 0u;
+    }
+    __device__ __forceinline__ void set_cnt(int i, uint32_t v) {
+        if constexpr (WIDE_CNT) cntw = (cntw & ~((uint64_t)15u << (4 * (i & 15)))) | ((uint64_t)(v & 15u) << (4 * (i & 15)));
+        else cntw = i < 8 ? (cntw & ~(15u << (4 * (i & 7)))) | ((v & 15u) << (4 * (i & 7))) : cntw;
+    }
     __device__ __forceinline__ void set_agent(int i, uint32_t cell, uint32_t c) { set_xy(i, cell); set_cnt(i, c); }
     __device__ __forceinline__ uint32_t job(int j) const { return jobw.get(j); }
     __device__ __forceinline__ void set_job(int j, uint32_t v) { jobw.set(j, v); }
@@ -516,7 +532,7 @@ struct RegStore {
 
 // compiled-in agent count: packed VGPR tables; a run-time job count gets the 8-slot table
 template <class S>
-struct StoreFor { using type = RegStore<S::kA, (S::kJ >= 0 ? S::kJ : 8)>; };
+struct StoreFor { using type = RegStore<S::kA, (S::kJ >= 0 ? S::kJ : 8), (S::kA > 8 && S::kVar == SUSNET_VARIANT_TAGGING)>; };
 template <>
 struct StoreFor<GenericSpec> { using type = LdsStore; };
 

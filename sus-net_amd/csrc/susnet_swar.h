@@ -1,4 +1,4 @@
-// susnet_swar.h -- index-order step for the compiled-in multi-agent games (3..8 agents, up to 8 jobs, FourRoomEnv /
+// susnet_swar.h -- index-order step for the compiled-in multi-agent games (3..12 agents, up to 8 jobs, FourRoomEnv /
 // ImposterTrainingGround / FourRoomEnvWithTagging rules): one lane per environment, every per-agent quantity a BYTE of a
 // packed 32-bit word, the whole step written as byte-parallel (SWAR) arithmetic over all agents at once.
 //
@@ -40,10 +40,10 @@ template <class S>
 struct UseSwar {
     // (kJ = -1: the job count is read at run time -- at most 8 -- : the FAMILY of byte-parallel kernels, one instantiation per agent
     // count, variant, order and imposter count, serving every job count: susnet_kernels.h SpecFam)
-    // (9 .. 12 agents -- three words of agent bytes: FourRoomEnv / ImposterTrainingGround rules; the tag section pairs words by v_perm and stays at 8)
-    static constexpr bool value = !S::kGeneric && S::kA >= 3 && S::kJ >= -1 && S::kJ <= 8 && S::kOrd >= 0 &&
-                                  ((S::kA <= 8 && (S::kVar == SUSNET_VARIANT_BASE || S::kVar == SUSNET_VARIANT_ITG || S::kVar == SUSNET_VARIANT_TAGGING)) ||
-                                   (S::kA <= 12 && (S::kVar == SUSNET_VARIANT_BASE || S::kVar == SUSNET_VARIANT_ITG))) &&
+    // (9 .. 12 agents -- three words of agent bytes: all three rule sets; the tag section looks a target up in the pair {word 1, word 0}
+    // and in word 2, see step_swar)
+    static constexpr bool value = !S::kGeneric && S::kA >= 3 && S::kJ >= -1 && S::kJ <= 8 && S::kOrd >= 0 && S::kA <= 12 &&
+                                  (S::kVar == SUSNET_VARIANT_BASE || S::kVar == SUSNET_VARIANT_ITG || S::kVar == SUSNET_VARIANT_TAGGING) &&
                                   (S::kNI >= 1 && S::kNI <= 3);
 };
 
@@ -112,7 +112,8 @@ struct JobMap {
 template <int W_, bool PAIR>
 struct GroupWords {
     static constexpr int W = W_, G = PAIR ? 8 : 4, NBLK = W * G / 4, kCols = PAIR ? 32 : 64;
-    static_assert(W * G * kCols <= (int)kGroupWords && (W * G) % (PAIR ? 8 : 4) == 0, "group size");
+    // (past kGroupWords: six-word ticks reach down into the unused rank table 2 -- kGroupWordsWord, susnet_device.h, checks the spec)
+    static_assert(W * G * kCols <= (int)kGroupWords + 672 && (W * G) % (PAIR ? 8 : 4) == 0, "group size");
     typedef __attribute__((address_space(3))) uint32_t *lds_u32_wptr;
     uint32_t col; // LDS byte address of word 0 of my environment's column
     uint32_t h;   // PAIR: which half of the pair I am
@@ -281,7 +282,7 @@ __device__ __forceinline__ uint32_t swar_is_imp(const Swar<S> &w, int i) { retur
 // len(agent_action_map[i]): kept per agent, or (kLean) the role list's length from the imposter flag (base.py:82-99, pred_prey.py:4-19)
 template <class S>
 __device__ __forceinline__ uint32_t swar_nact(const Consts &c, const Swar<S> &w, int i) {
-    if constexpr (Swar<S>::kLean) return S::nr_crew(c) + swar_is_imp(w, i);
+    if constexpr (Swar<S>::kLean) return S::nr_crew(c) + swar_is_imp(w, i) + (Swar<S>::kTag ? (uint32_t)(Swar<S>::A - 1) : 0u); // (+ the tag actions, tagging.py:68-75)
     else return w.nact[i];
 }
 template <class S>
@@ -534,7 +535,6 @@ __device__ __forceinline__ void step_swar(const Consts &c, const Tables &T, Swar
     using W = Swar<S>;
     constexpr int A = W::A, J = W::JMAX, NW = W::NW, NI = W::NI; // (J: job SLOTS; the job count itself is Jn)
     const int Jn = S::J(c);
-    static_assert(!W::kTag || NW <= 2, "the tag section pairs the two agent words by v_perm");
     constexpr uint32_t kLive[3] = {A >= 4 ? 0xffffffffu : (1u << (8 * (A & 3))) - 1u, A >= 8 ? 0xffffffffu : (A > 4 ? (1u << (8 * (A & 3))) - 1u : 0u),
                                    A >= 12 ? 0xffffffffu : (A > 8 ? (1u << (8 * (A & 3))) - 1u : 0u)};
     e.m_steps += 1; // base.py:366
@@ -952,12 +952,26 @@ __device__ __forceinline__ void step_swar(const Consts &c, const Tables &T, Swar
             // k-th OTHER agent ascending: target = action - len(role list), + 1 from the actor's own index on (tagging.py:68-75)
             const uint32_t nrb = 0x06060606u + (w.im80[q] >> 7);
             uint32_t t = ((act[q] | k80) - nrb) & k7f; // (meaningful where tag80 is set)
-            const uint32_t idxb = q == 0 ? 0x03020100u : 0x07060504u;
+            const uint32_t idxb = NW > 2 ? 0x03020100u + 0x04040404u * (uint32_t)q : (q == 0 ? 0x03020100u : 0x07060504u);
             t += (((t | k80) - idxb) & k80) >> 7;
-            tgt[q] = t & 0x07070707u;
+            tgt[q] = t & (NW > 2 ? 0x0f0f0f0fu : 0x07070707u);
         }
 #pragma unroll
         for (int q = 0; q < NW; q++) {
+            if constexpr (NW > 2) {
+                // twelve agent bytes: a target below 8 is looked up in the pair {word 1, word 0}, one from 8 on in word 2 -- two v_perm whose
+                // selectors yield zero for the other half (0x0c; a selector byte of 13 and up would yield 0xff: the low bits are cleared)
+                const uint32_t ge8 = tgt[q] & 0x08080808u, lt8 = ge8 ^ 0x08080808u, low = ge8 - (ge8 >> 3); // (low: 0x07 per byte with a target >= 8)
+                const uint32_t slo = (tgt[q] & ~low) | (ge8 >> 1);       // target < 8: the target; else 0x0c
+                const uint32_t shi = (tgt[q] & low) | lt8 | (lt8 >> 1);  // target >= 8: target - 8 (12 .. 15 -- never a tagger's target -- pick from the zero register); else 0x0c
+                // the target's alive flag at the tagger's turn: alive now (after this step's kills) ...
+                uint32_t tal80 = (__builtin_amdgcn_perm(w.al[1], w.al[0], slo) | __builtin_amdgcn_perm(0u, w.al[NW > 2 ? 2 : 0], shi)) << 7;
+                // ... or killed this step by a killer whose turn comes AFTER the tagger's (the tagger had already acted)
+#pragma unroll
+                for (int it = 0; it < NI; it++)
+                    tal80 |= (__builtin_amdgcn_perm(vk80[it][1], vk80[it][0], slo) | __builtin_amdgcn_perm(0u, vk80[it][NW > 2 ? 2 : 0], shi)) & ~gek80[it][q];
+                vt80[q] = tag80[q] & ~(w.used[q] << 7) & tal80 & k80; // first tag of the interval, living target
+            } else {
             // the target's alive flag at the tagger's turn: alive now (after this step's kills) ...
             uint32_t tal80 = __builtin_amdgcn_perm(NW > 1 ? w.al[hi] : 0u, w.al[0], tgt[q]) << 7;
             // ... or killed this step by a killer whose turn comes AFTER the tagger's (the tagger had already acted)
@@ -965,9 +979,34 @@ __device__ __forceinline__ void step_swar(const Consts &c, const Tables &T, Swar
             for (int it = 0; it < NI; it++)
                 tal80 |= __builtin_amdgcn_perm(NW > 1 ? vk80[it][hi] : 0u, vk80[it][0], tgt[q]) & ~gek80[it][q];
             vt80[q] = tag80[q] & ~(w.used[q] << 7) & tal80 & k80; // first tag of the interval, living target
+            }
             w.used[q] |= vt80[q] >> 7;
             any_new |= vt80[q];
         }
+        if constexpr (NW > 2) {
+            if (__builtin_amdgcn_ballot_w64(any_new != 0u) != 0ull) { // tag_counts[target] += 1 per counted tag
+                // the step's increments, FOUR bits per target (a target collects at most A - 1 <= 11 tags a step): twelve targets take 48 bits
+                uint64_t inc4 = 0ull;
+                uint32_t sh4[NW];
+#pragma unroll
+                for (int q = 0; q < NW; q++) sh4[q] = tgt[q] << 2; // 4 * target per agent byte (< 64)
+#pragma unroll
+                for (int i = 0; i < A; i++) {
+                    const uint32_t bit = __builtin_amdgcn_ubfe(vt80[i / 4], 8u * (uint32_t)(i & 3) + 7u, 1u);
+                    const uint32_t sh = __builtin_amdgcn_ubfe(sh4[i / 4], 8u * (uint32_t)(i & 3), 6u);
+                    inc4 += (uint64_t)bit << sh;
+                }
+                // ... spread to one byte per target and added to the counts (no byte overflows: a count stays below 12 -- every agent tags
+                // once per interval, tagging.py:103-110 -- and the state's 4-bit count field holds it)
+#pragma unroll
+                for (int q = 0; q < NW; q++) {
+                    uint32_t v = (uint32_t)(inc4 >> (16 * q)) & 0xffffu;
+                    v = (v | (v << 8)) & 0x00ff00ffu;
+                    v = (v | (v << 4)) & 0x0f0f0f0fu;
+                    w.cnt[q] += v;
+                }
+            }
+        } else
         if (__builtin_amdgcn_ballot_w64(any_new != 0u) != 0ull) { // tag_counts[target] += 1 per counted tag
             // the step's increments first, FOUR bits per target in one register (a target collects at most A - 1 <= 7 tags): a shift-and-add
             // per tagger (round 4: a 64-bit shift and a 64-bit add per tagger on the byte counts themselves: ~35 instructions a tick) ...
@@ -1007,6 +1046,50 @@ __device__ __forceinline__ void step_swar(const Consts &c, const Tables &T, Swar
         }
         w.timer += 1u;                                                               // tagging.py:182
         const bool due = w.timer >= (uint32_t)c.tag_interval;
+        if constexpr (NW > 2) {
+            if (__builtin_amdgcn_ballot_w64(due) != 0ull) { // tagging.py:184-207
+                // np.argmax (first maximum) as ONE maximum over keys count << 4 | (15 - index): a larger count wins, among equal counts the
+                // lower index (counts < 12, indices < 12: a key -- 0xbf at most -- fits its byte)
+                uint32_t kmax = 0;
+#pragma unroll
+                for (int q = 0; q < NW; q++) {
+                    const uint32_t keys = (w.cnt[q] << 4) + (q == 0 ? 0x0c0d0e0fu : (q == 1 ? 0x08090a0bu : 0x04050607u));
+#pragma unroll
+                    for (int i = 4 * q; i < A && i < 4 * q + 4; i++) {
+                        const uint32_t kv = __builtin_amdgcn_ubfe(keys, 8u * (uint32_t)(i & 3), 8u);
+                        kmax = kv > kmax ? kv : kmax;
+                    }
+                }
+                const uint32_t best = 15u - (kmax & 15u), highest = kmax >> 4;
+                uint32_t alive_sum = 0;
+#pragma unroll
+                for (int q = 0; q < NW; q++) alive_sum += (uint32_t)__popc(w.al[q] & kLive[q] & k01);
+                const bool out = due && highest >= ((alive_sum + 1u) >> 1);
+                voted_out = out;
+                const uint32_t hotb = (out ? 1u : 0u) << (8u * (best & 3u)); // 0x01 at the ejected agent's byte of its word
+                uint32_t vim = 0;
+#pragma unroll
+                for (int q = 0; q < NW; q++) { // (the word is picked with masks: see ranks_from_order)
+                    const uint32_t h1 = (best >> 2) == (uint32_t)q ? hotb : 0u;
+                    vim |= w.im80[q] & (h1 << 7);
+                    w.al[q] &= ~h1;
+                    w.al80[q] &= ~(h1 << 7); // (the derived forms of the alive flags: see Swar)
+                    w.crew80[q] &= ~(h1 << 7);
+                    w.ridx[q] += h1 << 4;
+                    idx4[q] += h1 << 4;
+                }
+                const bool vimp = vim != 0u;
+                const float vote = c.fr[RW_VOTE];
+                team += out ? vote * (vimp ? -1.0f : 1.0f) : 0.0f; // tagging.py:196, sign as coded
+                e.m_kv += out ? (vimp ? (1u << 16) : (1u << 24)) : 0u;
+#pragma unroll
+                for (int q = 0; q < NW; q++) { // tagging.py:237-241
+                    w.cnt[q] = due ? 0u : w.cnt[q];
+                    w.used[q] = due ? 0u : w.used[q];
+                }
+                w.timer = due ? 0u : w.timer;
+            }
+        } else
         if (__builtin_amdgcn_ballot_w64(due) != 0ull) { // tagging.py:184-207
             // np.argmax (first maximum) as ONE maximum over keys count << 3 | (7 - index): a larger count wins, among equal counts the
             // lower index (counts < 8: a key fits its byte)

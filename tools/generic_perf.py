@@ -1,5 +1,5 @@
 """Throughput of configurations OTHER than the four fully compiled-in BASELINE games: the byte-parallel family kernels (any job count up
-to 8, 3..12 agents -- tagging 3..8 --, at most 3 imposters: susnet_family.h), the 1v1 wall-map duel kernel and the generic kernels behind
+to 8, 3..12 agents -- tagging 3..12 too --, at most 3 imposters: susnet_family.h), the 1v1 wall-map duel kernel and the generic kernels behind
 them. GPU box only.
 Both trajectory layouts: separate tensors (actions, rewards, done, truncated, raw uint8 observation) and packed records."""
 import importlib
@@ -25,6 +25,9 @@ cases = {
     "tagging 2v6 j4 14x14": lambda: pkg.BatchedFourRoomEnvWithTagging(2, 6, 4, grid_size=14, **kw),
     "tagging 1v4 j5 (tag5: compiled in)": lambda: pkg.BatchedFourRoomEnvWithTagging(1, 4, 5, **kw),
     "tagging 1v4 j4": lambda: pkg.BatchedFourRoomEnvWithTagging(1, 4, 4, **kw),
+    "tagging 1v8 j3 (9 agents)": lambda: pkg.BatchedFourRoomEnvWithTagging(1, 8, 3, **kw),
+    "tagging 2v9 j4 (11 agents)": lambda: pkg.BatchedFourRoomEnvWithTagging(2, 9, 4, **kw),
+    "tagging 3v9 j8 (12 agents, 3 imposters)": lambda: pkg.BatchedFourRoomEnvWithTagging(3, 9, 8, **kw),
 }
 only = sys.argv[1:]
 for name, make in cases.items():
