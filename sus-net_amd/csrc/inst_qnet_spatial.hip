@@ -96,13 +96,6 @@ __global__ __launch_bounds__(kSpThreads) void k_spatial_conv(SpatialConvArgs a) 
 }
 
 // ---- the recurrence and the head --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sp_tanh(float x) {
-    const float ax = fabsf(x);
-    const float e = expm1f(-2.0f * ax); // in (-1, 0]: tanh |x| = (1 - e^{-2|x|}) / (1 + e^{-2|x|}) = -e / (e + 2), no cancellation near 0
-    const float t = ax >= 16.0f ? 1.0f : -e / (e + 2.0f);
-    return copysignf(t, x);
-}
-
 __global__ __launch_bounds__(kDnThreads) void k_spatial_rnn(SpatialRnnArgs a) {
     extern __shared__ float sr_smem[];
     const int t_ = threadIdx.x, lane = t_ & 63, i = lane & 31;

@@ -3,6 +3,7 @@
 
 #include "susnet_dropout.h"
 #include "susnet_host.h" // lds_opt_in
+#include "susnet_spatial.h" // sp_tanh: the forward's tanh
 #include "susnet_train_core.h"
 
 namespace susnet {
@@ -15,14 +16,6 @@ constexpr int kStOH0 = 0, kStOH1 = kStBuf, kStODA = 2 * kStBuf, kStODB = 3 * kSt
 constexpr int kStLdsBytes = kStLdsFloats * 4;
 static_assert(kStLdsBytes <= 160 * 1024, "gfx950 LDS");
 static_assert(kTrThreads >= kMtMaxHidden, "a thread per unit for the bias gradients");
-
-// tanh as susnet_spatial_forward computes it (inst_qnet_spatial.hip, sp_tanh): exactly 0 at 0, exactly +-1 from |x| = 16
-__device__ __forceinline__ float st_tanh(float x) {
-    const float ax = fabsf(x);
-    const float e = expm1f(-2.0f * ax);
-    const float t = ax >= 16.0f ? 1.0f : -e / (e + 2.0f);
-    return copysignf(t, x);
-}
 
 __device__ __forceinline__ int64_t st_clamp(int64_t v, int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
@@ -127,7 +120,7 @@ __device__ __forceinline__ void st_rnn_step(const SpTrainNet &net, const float *
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int n = n0 + tr_row(r, lane);
-            if (n < H) hout[n * kTrTS + s] = st_tanh(acc[r] + (bih[n] + bhh[n]));
+            if (n < H) hout[n * kTrTS + s] = sp_tanh(acc[r] + (bih[n] + bhh[n]));
         }
         if constexpr (DROP) {
             if (l < net.L - 1) {

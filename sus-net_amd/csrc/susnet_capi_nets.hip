@@ -1,7 +1,7 @@
 // susnet_capi_nets.hip -- the network entry points of the C ABI, none of which touches a stepping kernel: the compiled-in Q-network's checks,
 // pack and forward (qnet_feat and qnet_dims_ok serve the one-kernel tick of susnet_capi.hip and the fused learner of susnet_capi_train.hip
 // too), susnet_mlp_forward, susnet_spatial_forward and susnet_window_push.  Their kernels: inst_qnet_*.hip and inst_window.hip.  What a
-// Linear / PReLU stack is checked for and how it becomes kernel arguments is stated once, in susnet_host.h.
+// Linear / PReLU stack and a SpatialDQN are checked for, and how a stack becomes kernel arguments, is stated once, in susnet_host.h.
 #include <algorithm>
 
 #include "susnet_qnet.h"
@@ -157,52 +157,19 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_forward: null env / io");
     const Refuse bad{env, "susnet_spatial_forward"};
     const auto S = [](long long v) { return std::to_string(v); };
-    const auto range = [&](const std::string &field, long long v, long long lo, long long hi) {
-        return field + " = " + S(v) + " (served: " + S(lo) + " .. " + S(hi) + ")";
-    };
-    if (io->T < 1 || io->T > SUSNET_SPATIAL_MAX_T) return bad(range("T", io->T, 1, SUSNET_SPATIAL_MAX_T));
-    if (io->N < 1 || io->N > SUSNET_SPATIAL_MAX_N) return bad(range("N", io->N, 1, SUSNET_SPATIAL_MAX_N));
-    if (io->C < 1 || io->C > SUSNET_SPATIAL_MAX_C) return bad(range("C", io->C, 1, SUSNET_SPATIAL_MAX_C));
-    if (io->n_conv < 1 || io->n_conv > kSpMaxConv) return bad(range("n_conv", io->n_conv, 1, kSpMaxConv));
-    if (io->k != 1 && io->k != 3 && io->k != 5) return bad("k = " + S(io->k) + " (served: one square kernel size of 1, 3 or 5)");
-    SpatialConvArgs ca{};
-    ca.size[0] = io->N;
-    for (int l = 0; l < io->n_conv; l++) {
-        const std::string at = "[" + S(l) + "]";
-        if (io->conv_out[l] < 1 || io->conv_out[l] > 32) return bad(range("conv_out" + at, io->conv_out[l], 1, 32));
-        if (io->conv_stride[l] < 1 || io->conv_stride[l] > 4) return bad(range("conv_stride" + at, io->conv_stride[l], 1, 4));
-        if (io->conv_padding[l] < 0 || io->conv_padding[l] > 8) return bad(range("conv_padding" + at, io->conv_padding[l], 0, 8));
-        if (io->conv_dilation[l] < 1 || io->conv_dilation[l] > 4) return bad(range("conv_dilation" + at, io->conv_dilation[l], 1, 4));
-        const int span = ca.size[l] + 2 * io->conv_padding[l] - io->conv_dilation[l] * (io->k - 1) - 1;
-        if (span < 0) return bad("conv layer " + S(l) + ": output size < 1 (input " + S(ca.size[l]) + ", k " + S(io->k) + ", conv_padding" + at + " " +
-                                 S(io->conv_padding[l]) + ", conv_dilation" + at + " " + S(io->conv_dilation[l]) + ")");
-        ca.size[l + 1] = span / io->conv_stride[l] + 1;
-        if (!io->conv_weight[l] || misaligned(io->conv_weight[l])) return bad("conv_weight" + at + " is NULL or not 4-byte aligned");
-        if (!io->conv_bias[l] || misaligned(io->conv_bias[l])) return bad("conv_bias" + at + " is NULL or not 4-byte aligned");
-        ca.co[l] = io->conv_out[l];
-        ca.stride[l] = io->conv_stride[l];
-        ca.pad[l] = io->conv_padding[l];
-        ca.dil[l] = io->conv_dilation[l];
-        ca.W[l] = io->conv_weight[l];
-        ca.B[l] = io->conv_bias[l];
-    }
-    if (io->Fn < 0) return bad("Fn = " + S(io->Fn) + " (at least 0)");
-    const long long out_px = (long long)ca.size[io->n_conv] * ca.size[io->n_conv];
-    const long long R = (long long)io->conv_out[io->n_conv - 1] * out_px + io->Fn;
-    if (R > SUSNET_SPATIAL_MAX_R)
-        return bad("R = conv_out * H_out^2 + Fn = " + S(R) + " (the RNN's input width: at most SUSNET_SPATIAL_MAX_R = " + S(SUSNET_SPATIAL_MAX_R) + ")");
-    if (io->rnn_layers < 1 || io->rnn_layers > kSpMaxRnn) return bad(range("rnn_layers", io->rnn_layers, 1, kSpMaxRnn));
-    if (io->rnn_hidden < 1 || io->rnn_hidden > kDnMaxHidden) return bad(range("rnn_hidden", io->rnn_hidden, 1, kDnMaxHidden));
-    if (int rc = check_stack_n_dims(bad, "", io->n_dims, "a head of 1 .. 7 Linear layers")) return rc;
-    if (io->dims[0] != io->rnn_hidden)
-        return bad("dims[0] = " + S(io->dims[0]) + " (the head reads the hidden state: rnn_hidden = " + S(io->rnn_hidden) + ")");
-    if (int rc = check_stack_dims(bad, "", io->n_dims, io->dims, kDnMaxHidden, kDnMaxOut)) return rc;
+    SpatialGeom g;
+    if (int rc = check_spatial_net(bad, "", "", *io, io->n_dims, io->dims, kDnMaxHidden, kDnMaxOut, g)) return rc;
     if (io->n < 1) return bad("n = " + S(io->n) + " (at least one row)");
     if (io->n > (INT64_MAX >> 20)) return bad("n = " + S(io->n) + " (the workspace's byte count overflows)");
     if (io->agents < 1) return bad("agents = " + S(io->agents) + " (at least one agent per env)");
     for (int d = 0; d < 3; d++) {
         if (io->spatial_stride[d] < 0) return bad("spatial_stride[" + S(d) + "] = " + S(io->spatial_stride[d]) + " (at least 0)");
         if (io->Fn > 0 && io->non_spatial_stride[d] < 0) return bad("non_spatial_stride[" + S(d) + "] = " + S(io->non_spatial_stride[d]) + " (at least 0)");
+    }
+    for (int l = 0; l < io->n_conv; l++) {
+        const std::string at = "[" + S(l) + "]";
+        if (!io->conv_weight[l] || misaligned(io->conv_weight[l])) return bad("conv_weight" + at + " is NULL or not 4-byte aligned");
+        if (!io->conv_bias[l] || misaligned(io->conv_bias[l])) return bad("conv_bias" + at + " is NULL or not 4-byte aligned");
     }
     for (int l = 0; l < io->rnn_layers; l++) {
         const std::string at = "[" + S(l) + "]";
@@ -217,13 +184,23 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     if ((!io->non_spatial && io->Fn > 0) || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
     if (!io->rnn_in || misaligned(io->rnn_in)) return bad("rnn_in is NULL or not 4-byte aligned");
     if (!io->q_out || misaligned(io->q_out)) return bad("q_out is NULL or not 4-byte aligned");
+    SpatialConvArgs ca{};
     ca.T = io->T;
     ca.C = io->C;
     ca.n_conv = io->n_conv;
     ca.k = io->k;
     ca.Fn = io->Fn;
     ca.agents = io->agents;
-    ca.R = (int32_t)R;
+    ca.R = g.R;
+    for (int l = 0; l <= io->n_conv; l++) ca.size[l] = g.size[l];
+    for (int l = 0; l < io->n_conv; l++) {
+        ca.co[l] = io->conv_out[l];
+        ca.stride[l] = io->conv_stride[l];
+        ca.pad[l] = io->conv_padding[l];
+        ca.dil[l] = io->conv_dilation[l];
+        ca.W[l] = io->conv_weight[l];
+        ca.B[l] = io->conv_bias[l];
+    }
     ca.spatial = io->spatial;
     ca.non_spatial = io->non_spatial;
     for (int d = 0; d < 3; d++) {
@@ -234,7 +211,7 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     ca.rnn_in = io->rnn_in;
     SpatialRnnArgs ra{};
     ra.T = io->T;
-    ra.R = (int32_t)R;
+    ra.R = g.R;
     ra.L = io->rnn_layers;
     ra.H = io->rnn_hidden;
     for (int l = 0; l < io->rnn_layers; l++) {

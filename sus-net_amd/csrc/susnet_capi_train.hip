@@ -1,7 +1,8 @@
 // susnet_capi_train.hip -- the DQN learners of the C ABI: susnet_dqn_train_step and susnet_dqn_train_sweep (the fused learner on the
 // compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step (the dense learner on any served stack;
 // its gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step (the SpatialDQN learner; its kernels: inst_spatial_train.hip).  All
-// end every update with this unit's k_train_adam.
+// carve their workspace with tr_buffers and the single learners end every update with launch_adam (this unit's k_train_adam); the dense and
+// the SpatialDQN learner share their handle, Adam-constant, pointer and workspace checks (check_*, below).
 #include <algorithm>
 #include <cstring>
 
@@ -14,6 +15,69 @@
 #include "susnet_host.h"
 
 using namespace susnet;
+
+// ---- what the learners share on the host ----
+// the part of a workspace every learner lays out with tr_workspace_layout, as pointers
+struct TrBuffers {
+    int32_t *lists, *counts;
+    float *gacc[2], *partial;
+};
+static TrBuffers tr_buffers(void *workspace, const TrWorkspace &w) {
+    char *ws = static_cast<char *>(workspace);
+    return {reinterpret_cast<int32_t *>(ws + w.off_lists), reinterpret_cast<int32_t *>(ws + w.off_counts),
+            {reinterpret_cast<float *>(ws + w.off_gacc[0]), reinterpret_cast<float *>(ws + w.off_gacc[1])}, reinterpret_cast<float *>(ws + w.off_partial)};
+}
+// the reduce + Adam launch that ends an (agent, team) update of a single learner (NET: TrainNet, MlpTrainNet, SpTrainNet -- P and Pp)
+template <class NET>
+static hipError_t launch_adam(const NET &net, const TrBuffers &b, int agent, int tm, int G, const susnet_dqn_team &T, float *losses, hipStream_t st) {
+    hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((net.P + 1 + 255) / 256)), dim3(256), 0, st, net.P, net.Pp, b.counts, agent, tm, b.partial, G, b.gacc[tm],
+                       T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, losses);
+    return hipGetLastError();
+}
+// The checks the dense and the SpatialDQN learner make alike, in the same words (`bad` carries the entry point's name).  The fused learner's
+// older checks (dqn_plan, dqn_check_io) have words of their own.
+static int check_learner(const Refuse &bad, const susnet_env *env, int64_t n, double gamma) { // the handle and the batch
+    if (env->c.n_imp != 1)
+        return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
+                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
+    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + std::to_string(env->c.A) + " (served: 2 .. 16)");
+    if (n < 0 || n > (1ll << 30)) return bad("n = " + std::to_string((long long)n) + " (served: 0 .. 2^30)");
+    if (!(gamma == gamma)) return bad("gamma is NaN");
+    return SUSNET_OK;
+}
+static int check_adam(const Refuse &bad, const std::string &who, const susnet_dqn_team &T) {
+    if (!(T.lr >= 0.0) || !(T.beta1 >= 0.0 && T.beta1 < 1.0) || !(T.beta2 >= 0.0 && T.beta2 < 1.0) || !(T.eps >= 0.0))
+        return bad(who + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
+    return SUSNET_OK;
+}
+static int check_workspace(const Refuse &bad, const void *workspace, uint64_t have, uint64_t need, const char *query) { // (`query` tells `need`)
+    if (!workspace || have < need || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return bad(std::string("workspace missing, smaller than ") + query + " (" + std::to_string((unsigned long long)need) + " bytes) or not 256-byte aligned");
+    return SUSNET_OK;
+}
+template <class IO> // (susnet_mlp_train_io, susnet_spatial_train_io: the same field names)
+static int check_ring_ptrs(const Refuse &bad, const IO &io) {
+    if (!io.losses_out || misaligned(io.losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
+    const std::pair<const char *, const void *> ring[] = {{"actions", io.actions}, {"rewards", io.rewards}, {"dones", io.dones}, {"imposters", io.imposters}};
+    for (const auto &r : ring)
+        if (!r.second) return bad(std::string(r.first) + " is NULL");
+    if (io.max_size < 1) return bad("max_size = " + std::to_string((long long)io.max_size) + " (at least one ring row)");
+    if (io.n > 0 && !io.indices) return bad("indices is NULL");
+    return SUSNET_OK;
+}
+static int check_team_ptrs(const Refuse &bad, const susnet_dqn_team (&team)[2]) {
+    for (int tm = 0; tm < 2; tm++) {
+        const susnet_dqn_team &T = team[tm];
+        if (!T.enabled) continue;
+        const std::string who = "team[" + std::to_string(tm) + "].";
+        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
+        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
+        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
+        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
+        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
+    }
+    return SUSNET_OK;
+}
 
 // ---- the learner's train step (susnet_train.h) ----
 struct DqnPlan : TrWorkspace {
@@ -70,27 +134,22 @@ template <class ROW>
 static int dqn_launch(const susnet_env *env, const susnet_dqn_io *io, const DqnPlan &pl, hipStream_t st) {
     static LdsOptIn opted; // the dynamic-LDS ceiling of this instantiation's kernel, once per device (susnet_host.h)
     HIP_TRY(lds_opt_in(reinterpret_cast<const void *>(&k_train_grad<ROW>), kTrLdsBytes, opted));
-    char *ws = static_cast<char *>(io->workspace);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
-    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    const TrBuffers b = tr_buffers(io->workspace, pl);
     TrainRing ring{io->states, io->next_states, io->actions, io->rewards, io->dones, io->imposters, io->max_size,
                    (int32_t)env->layout.obs_raw_size, (int32_t)env->c.A, (int32_t)env->c.n_imp};
     const int64_t N = io->n;
-    hipLaunchKernelGGL(k_train_select, dim3(1), dim3(kTrThreads), kTrThreads * 4, st, ring, io->indices, N, lists, counts, gacc[0], pl.net[0].P, gacc[1],
-                       pl.net[1].P, io->losses_out);
+    hipLaunchKernelGGL(k_train_select, dim3(1), dim3(kTrThreads), kTrThreads * 4, st, ring, io->indices, N, b.lists, b.counts, b.gacc[0], pl.net[0].P,
+                       b.gacc[1], pl.net[1].P, io->losses_out);
     HIP_TRY(hipGetLastError());
     if (N == 0) return SUSNET_OK;
     for (int agent = 0; agent < env->c.A; agent++)
         for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
             const susnet_dqn_team &T = io->team[tm];
             if (!T.enabled) continue;
-            hipLaunchKernelGGL(k_train_grad<ROW>, dim3((unsigned)pl.G), dim3(kTrThreads), kTrLdsBytes, st, ring, pl.net[tm], T.params, T.target_params, lists,
-                               counts, N, agent, tm, (float)io->gamma, partial, T.step);
+            hipLaunchKernelGGL(k_train_grad<ROW>, dim3((unsigned)pl.G), dim3(kTrThreads), kTrLdsBytes, st, ring, pl.net[tm], T.params, T.target_params, b.lists,
+                               b.counts, N, agent, tm, (float)io->gamma, b.partial, T.step);
             HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
-                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_adam(pl.net[tm], b, agent, tm, (int)pl.G, T, io->losses_out, st));
         }
     for (int tm = 0; tm < 2; tm++) {
         const susnet_dqn_team &T = io->team[tm];
@@ -142,17 +201,14 @@ static int dqn_sweep_launch(susnet_env *const *envs, const susnet_dqn_io *ios, i
     bool packs[2] = {false, false};
     for (int k = 0; k < K; k++) {
         const susnet_dqn_io &io = ios[k];
-        char *ws = static_cast<char *>(io.workspace);
-        int32_t *lists = reinterpret_cast<int32_t *>(ws + pls[k].off_lists), *counts = reinterpret_cast<int32_t *>(ws + pls[k].off_counts);
-        float *gacc[2] = {reinterpret_cast<float *>(ws + pls[k].off_gacc[0]), reinterpret_cast<float *>(ws + pls[k].off_gacc[1])};
+        const TrBuffers b = tr_buffers(io.workspace, pls[k]);
         const TrainRing ring{io.states, io.next_states, io.actions, io.rewards, io.dones, io.imposters, io.max_size,
                              (int32_t)envs[k]->layout.obs_raw_size, (int32_t)envs[k]->c.A, (int32_t)envs[k]->c.n_imp};
-        sel.l[k] = TrainSelLearner{ring, io.indices, lists, counts, gacc[0], gacc[1], io.losses_out};
+        sel.l[k] = TrainSelLearner{ring, io.indices, b.lists, b.counts, b.gacc[0], b.gacc[1], io.losses_out};
         for (int tm = 0; tm < 2; tm++) {
             const susnet_dqn_team &T = io.team[tm];
             if (!T.enabled) continue;
-            tab[tm].l[k] = TrainLearner{ring, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, lists, counts, gacc[tm],
-                                        reinterpret_cast<float *>(ws + pls[k].off_partial), io.losses_out, T.packed,
+            tab[tm].l[k] = TrainLearner{ring, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, b.lists, b.counts, b.gacc[tm], b.partial, io.losses_out, T.packed,
                                         T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
             packs[tm] = packs[tm] || T.packed != nullptr;
         }
@@ -241,12 +297,7 @@ static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, 
     if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_mlp_train_step: null env / io");
     static_assert(kMtMaxHidden == kDnMaxHidden && kMtMaxOut == kDnMaxOut, "the dense learner trains what the dense forward serves"); // (one check_stack_dims)
     const Refuse bad{env, "susnet_mlp_train_step"};
-    if (env->c.n_imp != 1)
-        return bad("n_imposters = " + std::to_string(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
-                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
-    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + std::to_string(env->c.A) + " (served: 2 .. 16)");
-    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + std::to_string((long long)io->n) + " (served: 0 .. 2^30)");
-    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
+    if (int rc = check_learner(bad, env, io->n, io->gamma)) return rc;
     int64_t pmax = 4, zmax = 0;
     int F = 0;
     for (int tm = 0; tm < 2; tm++) {
@@ -262,8 +313,7 @@ static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, 
             return bad(who + "dims[0] = " + std::to_string(T.dims[0]) + " but team[0].dims[0] = " + std::to_string(F) + ": both teams read the same feature rows");
         F = T.dims[0];
         if (T.packed) return bad(who + "packed must be NULL (the dense forward reads params in place: there is no image to rewrite)");
-        if (!(T.lr >= 0.0) || !(T.beta1 >= 0.0 && T.beta1 < 1.0) || !(T.beta2 >= 0.0 && T.beta2 < 1.0) || !(T.eps >= 0.0))
-            return bad(who + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
+        if (int rc = check_adam(bad, who, T)) return rc;
         MlpTrainNet &net = pl.net[tm];
         net.nl = nl;
         for (int l = 0; l <= nl; l++) net.d[l] = T.dims[l];
@@ -295,48 +345,27 @@ extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io 
     MlpTrainPlan pl;
     if (int rc = mlp_train_plan(env, io, pl)) return rc;
     const Refuse bad{env, "susnet_mlp_train_step"};
-    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
-        return bad("workspace missing, smaller than susnet_mlp_train_workspace_bytes (" + std::to_string((unsigned long long)pl.bytes) +
-                   " bytes) or not 256-byte aligned");
-    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
-    if (!io->actions) return bad("actions is NULL");
-    if (!io->rewards) return bad("rewards is NULL");
-    if (!io->dones) return bad("dones is NULL");
-    if (!io->imposters) return bad("imposters is NULL");
-    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
+    if (int rc = check_workspace(bad, io->workspace, io->workspace_bytes, pl.bytes, "susnet_mlp_train_workspace_bytes")) return rc;
+    if (int rc = check_ring_ptrs(bad, *io)) return rc;
     if (io->n > 0) {
-        if (!io->indices) return bad("indices is NULL");
         if (!io->feat || misaligned(io->feat)) return bad("feat is NULL or not 4-byte aligned");
         if (!io->next_feat || misaligned(io->next_feat)) return bad("next_feat is NULL or not 4-byte aligned");
     }
-    for (int tm = 0; tm < 2; tm++) {
-        const susnet_dqn_team &T = io->team[tm];
-        if (!T.enabled) continue;
-        const std::string who = "team[" + std::to_string(tm) + "].";
-        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
-        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
-        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
-        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
-        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
-    }
+    if (int rc = check_team_ptrs(bad, io->team)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(io->workspace);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
-    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial), *zsave = reinterpret_cast<float *>(ws + pl.off_z);
+    const TrBuffers w = tr_buffers(io->workspace, pl);
+    float *zsave = reinterpret_cast<float *>(static_cast<char *>(io->workspace) + pl.off_z);
     const MlpTrainBatch b{io->feat, io->next_feat, io->actions, io->rewards, io->dones, io->imposters, io->indices, io->max_size, io->n,
                           (int32_t)env->c.A, (int32_t)env->c.n_imp};
-    HIP_TRY(mlp_train_select_launch(b, lists, counts, gacc[0], pl.net[0].P, gacc[1], pl.net[1].P, io->losses_out, st));
+    HIP_TRY(mlp_train_select_launch(b, w.lists, w.counts, w.gacc[0], pl.net[0].P, w.gacc[1], pl.net[1].P, io->losses_out, st));
     if (io->n == 0) return SUSNET_OK;
     for (int agent = 0; agent < env->c.A; agent++)
         for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
             const susnet_dqn_team &T = io->team[tm];
             if (!T.enabled) continue;
-            HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, zsave, T.step,
-                                          (int)pl.G, st));
-            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
-                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, w.lists, w.counts, agent, tm, (float)io->gamma, w.partial, zsave,
+                                          T.step, (int)pl.G, st));
+            HIP_TRY(launch_adam(pl.net[tm], w, agent, tm, (int)pl.G, T, io->losses_out, st));
         }
     return SUSNET_OK;
 }
@@ -347,70 +376,36 @@ struct SpTrainPlan : TrWorkspace {
     int64_t G = 1, Gconv = 1;
     uint64_t off_X = 0, off_Xt = 0, off_act = 0, off_dact = 0, off_dX = 0, off_tact = 0, off_hs = 0, off_ds = 0, off_zs = 0, off_nets = 0, off_ms = 0, bytes = 0;
 };
-// one enabled team's network: the spatial rules (those of susnet_spatial_forward) stated here, the head's by the shared stack checks
+// one enabled team's network: the rules are check_spatial_net's (susnet_host.h, shared with susnet_spatial_forward); its own are the flat
+// parameter offsets (SpatialDQN.parameters() order) and the layout of the saved activations
 static int sp_train_net(const Refuse &bad, int t, const susnet_spatial_net &sn, const susnet_dqn_team &tm, SpTrainNet &net) {
-    const auto S = [](long long v) { return std::to_string(v); };
-    const std::string who = "net[" + S(t) + "].", team = "team[" + S(t) + "]."; // where the spatial fields and the head's sit
-    const auto range = [&](const std::string &field, long long v, long long lo, long long hi) {
-        return who + field + " = " + S(v) + " (served: " + S(lo) + " .. " + S(hi) + ")";
-    };
-    if (sn.T < 1 || sn.T > SUSNET_SPATIAL_MAX_T) return bad(range("T", sn.T, 1, SUSNET_SPATIAL_MAX_T));
-    if (sn.N < 1 || sn.N > SUSNET_SPATIAL_MAX_N) return bad(range("N", sn.N, 1, SUSNET_SPATIAL_MAX_N));
-    if (sn.C < 1 || sn.C > SUSNET_SPATIAL_MAX_C) return bad(range("C", sn.C, 1, SUSNET_SPATIAL_MAX_C));
-    if (sn.n_conv < 1 || sn.n_conv > SUSNET_SPATIAL_MAX_CONV) return bad(range("n_conv", sn.n_conv, 1, SUSNET_SPATIAL_MAX_CONV));
-    if (sn.k != 1 && sn.k != 3 && sn.k != 5) return bad(who + "k = " + S(sn.k) + " (served: one square kernel size of 1, 3 or 5)");
-    if (sn.Fn < 0) return bad(who + "Fn = " + S(sn.Fn) + " (at least 0)");
+    const std::string who = "net[" + std::to_string(t) + "].", team = "team[" + std::to_string(t) + "]."; // where the spatial fields and the head's sit
+    SpatialGeom g;
+    if (int rc = check_spatial_net(bad, who, team, sn, tm.n_dims, tm.dims, kMtMaxHidden, kMtMaxOut, g)) return rc;
+    if (tm.packed) return bad(team + "packed must be NULL (susnet_spatial_forward reads params in place: there is no image to rewrite)");
+    if (int rc = check_adam(bad, team, tm)) return rc;
     net = SpTrainNet{};
     net.T = sn.T, net.N = sn.N, net.C = sn.C, net.Fn = sn.Fn, net.n_conv = sn.n_conv, net.k = sn.k;
-    net.size[0] = sn.N, net.ch[0] = sn.C, net.sz[0] = sn.C * sn.N * sn.N;
+    net.R = g.R, net.Rc = g.Rc, net.L = sn.rnn_layers, net.H = sn.rnn_hidden;
+    for (int l = 0; l <= sn.n_conv; l++) net.size[l] = g.size[l], net.ch[l] = g.ch[l], net.sz[l] = g.sz[l];
     int off = 0;
+    const auto take = [&](int32_t &at, int floats) { at = off, off += floats; };
     for (int l = 0; l < sn.n_conv; l++) {
-        const std::string at = "[" + S(l) + "]";
-        if (sn.conv_out[l] < 1 || sn.conv_out[l] > 32) return bad(range("conv_out" + at, sn.conv_out[l], 1, 32));
-        if (sn.conv_stride[l] < 1 || sn.conv_stride[l] > 4) return bad(range("conv_stride" + at, sn.conv_stride[l], 1, 4));
-        if (sn.conv_padding[l] < 0 || sn.conv_padding[l] > 8) return bad(range("conv_padding" + at, sn.conv_padding[l], 0, 8));
-        if (sn.conv_dilation[l] < 1 || sn.conv_dilation[l] > 4) return bad(range("conv_dilation" + at, sn.conv_dilation[l], 1, 4));
-        const int span = net.size[l] + 2 * sn.conv_padding[l] - sn.conv_dilation[l] * (sn.k - 1) - 1;
-        if (span < 0) return bad(who + "conv layer " + S(l) + ": output size < 1 (input " + S(net.size[l]) + ", k " + S(sn.k) + ", conv_padding" + at + " " +
-                                 S(sn.conv_padding[l]) + ", conv_dilation" + at + " " + S(sn.conv_dilation[l]) + ")");
-        net.size[l + 1] = span / sn.conv_stride[l] + 1;
-        net.ch[l + 1] = sn.conv_out[l];
-        net.sz[l + 1] = net.ch[l + 1] * net.size[l + 1] * net.size[l + 1];
         net.stride[l] = sn.conv_stride[l], net.pad[l] = sn.conv_padding[l], net.dil[l] = sn.conv_dilation[l];
-        net.oCW[l] = off;
-        off += net.ch[l + 1] * net.ch[l] * sn.k * sn.k;
-        net.oCB[l] = off;
-        off += net.ch[l + 1];
+        take(net.oCW[l], net.ch[l + 1] * net.ch[l] * sn.k * sn.k);
+        take(net.oCB[l], net.ch[l + 1]);
         net.maxsz = std::max(net.maxsz, net.sz[l + 1]);
         if (l < sn.n_conv - 1) {
             net.aoff[l] = net.asz;
             net.asz += net.sz[l + 1];
         }
     }
-    const long long R = (long long)net.sz[sn.n_conv] + sn.Fn;
-    if (R > SUSNET_SPATIAL_MAX_R)
-        return bad(who + "R = conv_out * H_out^2 + Fn = " + S(R) + " (the RNN's input width: at most SUSNET_SPATIAL_MAX_R = " + S(SUSNET_SPATIAL_MAX_R) + ")");
-    net.R = (int32_t)R, net.Rc = net.sz[sn.n_conv];
-    if (sn.rnn_layers < 1 || sn.rnn_layers > SUSNET_SPATIAL_MAX_RNN_LAYERS) return bad(range("rnn_layers", sn.rnn_layers, 1, SUSNET_SPATIAL_MAX_RNN_LAYERS));
-    if (sn.rnn_hidden < 1 || sn.rnn_hidden > kMtMaxHidden) return bad(range("rnn_hidden", sn.rnn_hidden, 1, kMtMaxHidden));
-    net.L = sn.rnn_layers, net.H = sn.rnn_hidden;
     for (int l = 0; l < net.L; l++) {
-        net.oWih[l] = off;
-        off += net.H * (l == 0 ? net.R : net.H);
-        net.oWhh[l] = off;
-        off += net.H * net.H;
-        net.oBih[l] = off;
-        off += net.H;
-        net.oBhh[l] = off;
-        off += net.H;
+        take(net.oWih[l], net.H * (l == 0 ? net.R : net.H));
+        take(net.oWhh[l], net.H * net.H);
+        take(net.oBih[l], net.H);
+        take(net.oBhh[l], net.H);
     }
-    if (int rc = check_stack_n_dims(bad, team, tm.n_dims, "a head of 1 .. 7 Linear layers")) return rc;
-    if (tm.dims[0] != sn.rnn_hidden)
-        return bad(team + "dims[0] = " + S(tm.dims[0]) + " (the head reads the hidden state: " + who + "rnn_hidden = " + S(sn.rnn_hidden) + ")");
-    if (int rc = check_stack_dims(bad, team, tm.n_dims, tm.dims, kMtMaxHidden, kMtMaxOut)) return rc;
-    if (tm.packed) return bad(team + "packed must be NULL (susnet_spatial_forward reads params in place: there is no image to rewrite)");
-    if (!(tm.lr >= 0.0) || !(tm.beta1 >= 0.0 && tm.beta1 < 1.0) || !(tm.beta2 >= 0.0 && tm.beta2 < 1.0) || !(tm.eps >= 0.0))
-        return bad(team + "lr / beta1 / beta2 / eps (served: lr >= 0, 0 <= beta < 1, eps >= 0)");
     MlpTrainNet &hd = net.head;
     hd.nl = tm.n_dims - 1;
     for (int l = 0; l <= hd.nl; l++) hd.d[l] = tm.dims[l];
@@ -431,12 +426,7 @@ static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *i
     if (!env || !io) return fail(SUSNET_E_INVALID, std::string(entry) + ": null env / io");
     const Refuse bad{env, entry};
     const auto S = [](long long v) { return std::to_string(v); };
-    if (env->c.n_imp != 1)
-        return bad("n_imposters = " + S(env->c.n_imp) + ": one imposter is served -- the reference's train_step fails on two or more, "
-                   "`(batch.imposters == agent_idx).view(-1)` (src/train.py:83) has n_imposters * N entries");
-    if (env->c.A < 2 || env->c.A > 16) return bad("n_agents = " + S(env->c.A) + " (served: 2 .. 16)");
-    if (io->n < 0 || io->n > (1ll << 30)) return bad("n = " + S(io->n) + " (served: 0 .. 2^30)");
-    if (!(io->gamma == io->gamma)) return bad("gamma is NaN");
+    if (int rc = check_learner(bad, env, io->n, io->gamma)) return rc;
     int64_t pmax = 4, T = 1, R = 1, Rc = 1, asz = 0, maxsz = 1, slice = 1, mslice = 1, Z = 4;
     int first = -1;
     for (int tm = 0; tm < 2; tm++) {
@@ -517,40 +507,23 @@ static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io
         if (int rc = drop_check(bad, "drop[" + std::to_string(tm) + "].", drop[tm], io->n, dr[tm])) return rc;
         masked[tm] = (dr[tm].thr[0] != 0u || dr[tm].thr[1] != 0u) && pl.net[tm].L > 1;
     }
-    if (!io->workspace || io->workspace_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(io->workspace) & 255u))
-        return bad(std::string("workspace missing, smaller than ") + (drop ? "susnet_spatial_train_dropout_workspace_bytes (" : "susnet_spatial_train_workspace_bytes (") +
-                   std::to_string((unsigned long long)pl.bytes) + " bytes) or not 256-byte aligned");
-    if (!io->losses_out || misaligned(io->losses_out)) return bad("losses_out is NULL or not 4-byte aligned");
-    if (!io->actions) return bad("actions is NULL");
-    if (!io->rewards) return bad("rewards is NULL");
-    if (!io->dones) return bad("dones is NULL");
-    if (!io->imposters) return bad("imposters is NULL");
-    if (io->max_size < 1) return bad("max_size = " + std::to_string((long long)io->max_size) + " (at least one ring row)");
+    if (int rc = check_workspace(bad, io->workspace, io->workspace_bytes, pl.bytes,
+                                 drop ? "susnet_spatial_train_dropout_workspace_bytes" : "susnet_spatial_train_workspace_bytes"))
+        return rc;
+    if (int rc = check_ring_ptrs(bad, *io)) return rc;
     const bool any = io->team[0].enabled || io->team[1].enabled;
     const int Fn = io->team[0].enabled ? io->net[0].Fn : io->team[1].enabled ? io->net[1].Fn : 0;
     if (io->n > 0 && any) {
-        if (!io->indices) return bad("indices is NULL");
         if (!io->spatial || misaligned(io->spatial)) return bad("spatial is NULL or not 4-byte aligned");
         if (!io->next_spatial || misaligned(io->next_spatial)) return bad("next_spatial is NULL or not 4-byte aligned");
         // (Fn = 0: nothing is read through them, so NULL is accepted, as susnet_spatial_forward does; a pointer that is given is still checked)
         if ((!io->non_spatial && Fn > 0) || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
         if ((!io->next_non_spatial && Fn > 0) || misaligned(io->next_non_spatial)) return bad("next_non_spatial is NULL or not 4-byte aligned");
-    } else if (io->n > 0 && !io->indices) return bad("indices is NULL");
-    for (int tm = 0; tm < 2; tm++) {
-        const susnet_dqn_team &T = io->team[tm];
-        if (!T.enabled) continue;
-        const std::string who = "team[" + std::to_string(tm) + "].";
-        if (!T.params || misaligned(T.params)) return bad(who + "params is NULL or not 4-byte aligned");
-        if (!T.target_params || misaligned(T.target_params)) return bad(who + "target_params is NULL or not 4-byte aligned");
-        if (!T.exp_avg || misaligned(T.exp_avg)) return bad(who + "exp_avg is NULL or not 4-byte aligned");
-        if (!T.exp_avg_sq || misaligned(T.exp_avg_sq)) return bad(who + "exp_avg_sq is NULL or not 4-byte aligned");
-        if (!T.step || misaligned(T.step)) return bad(who + "step is NULL or not 4-byte aligned");
     }
+    if (int rc = check_team_ptrs(bad, io->team)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(io->workspace);
-    int32_t *lists = reinterpret_cast<int32_t *>(ws + pl.off_lists), *counts = reinterpret_cast<int32_t *>(ws + pl.off_counts);
-    float *gacc[2] = {reinterpret_cast<float *>(ws + pl.off_gacc[0]), reinterpret_cast<float *>(ws + pl.off_gacc[1])};
-    float *partial = reinterpret_cast<float *>(ws + pl.off_partial);
+    const TrBuffers t = tr_buffers(io->workspace, pl);
     const auto at = [&](uint64_t off) { return reinterpret_cast<float *>(ws + off); };
     const SpTrainWs w{at(pl.off_X), at(pl.off_Xt), at(pl.off_act), at(pl.off_dact), at(pl.off_dX), at(pl.off_tact), at(pl.off_hs), at(pl.off_ds), at(pl.off_zs)};
     SpTrainBatch b{};
@@ -559,17 +532,15 @@ static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io
     b.actions = io->actions, b.rewards = io->rewards, b.dones = io->dones, b.imposters = io->imposters, b.idx = io->indices;
     b.max_size = io->max_size, b.n = io->n, b.A = (int32_t)env->c.A, b.n_imp = (int32_t)env->c.n_imp;
     SpTrainNet *nets = reinterpret_cast<SpTrainNet *>(ws + pl.off_nets);
-    HIP_TRY(sp_train_select_launch(b, pl.net[0], pl.net[1], nets, lists, counts, gacc[0], gacc[1], io->losses_out, st));
+    HIP_TRY(sp_train_select_launch(b, pl.net[0], pl.net[1], nets, t.lists, t.counts, t.gacc[0], t.gacc[1], io->losses_out, st));
     if (io->n == 0) return SUSNET_OK;
     for (int agent = 0; agent < env->c.A; agent++)
         for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
             const susnet_dqn_team &T = io->team[tm];
             if (!T.enabled) continue;
-            HIP_TRY(sp_train_update_launch(b, nets + tm, w, T.params, T.target_params, lists, counts, agent, tm, (float)io->gamma, partial, T.step,
+            HIP_TRY(sp_train_update_launch(b, nets + tm, w, T.params, T.target_params, t.lists, t.counts, agent, tm, (float)io->gamma, t.partial, T.step,
                                            (int)pl.G, (int)pl.Gconv, st, masked[tm] ? &dr[tm] : nullptr, masked[tm] ? at(pl.off_ms) : nullptr));
-            hipLaunchKernelGGL(k_train_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256)), dim3(256), 0, st, pl.net[tm].P, pl.net[tm].Pp, counts, agent, tm,
-                               partial, (int)pl.G, gacc[tm], T.params, T.exp_avg, T.exp_avg_sq, T.step, T.lr, T.beta1, T.beta2, T.eps, io->losses_out);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_adam(pl.net[tm], t, agent, tm, (int)pl.G, T, io->losses_out, st));
         }
     return SUSNET_OK;
 }

@@ -1,5 +1,6 @@
 // susnet_host.h -- what every host-side translation unit of the C ABI shares (susnet_capi*.hip; the launchers of inst_qnet_dense.hip and
-// inst_mlp_train.hip take the LDS opt-in from here): the handle, the error conventions, and the small helpers of the entry points.
+// inst_mlp_train.hip take the LDS opt-in from here): the handle, the error conventions, the small helpers of the entry points, and the ONE
+// statement of what a layer stack and a SpatialDQN are checked for (check_stack_*, check_spatial_net).
 // Private to csrc/: the public interface is include/susnet.h.
 #pragma once
 
@@ -129,4 +130,52 @@ inline void fill_stack(ARGS &a, const IO &io) {
     for (int l = 0; l < io.n_dims; l++) a.d[l] = io.dims[l];
     for (int l = 0; l < io.n_dims - 1; l++) a.W[l] = io.weight[l], a.B[l] = io.bias[l];
     for (int l = 0; l < io.n_dims - 2; l++) a.A[l] = io.slope[l];
+}
+
+// ---- a SpatialDQN at an entry point (susnet_spatial_forward; each enabled team of susnet_spatial_train_step): the ONE statement of its
+// rules, their order -- T, N, C, n_conv, k, the conv layers, Fn, R, rnn_layers, rnn_hidden, then the head -- and their words.  `net_prefix`
+// names the struct the spatial fields sit in ("net[0]."), `team_prefix` the one with the head's n_dims / dims ("team[0]."); NET is a
+// susnet_spatial_net or the forward's susnet_spatial_io, which holds the same fields and the head inline (both prefixes empty) ----
+struct SpatialGeom { // what every caller derives from a checked net, per activation level 0 .. n_conv
+    int32_t size[SUSNET_SPATIAL_MAX_CONV + 1], ch[SUSNET_SPATIAL_MAX_CONV + 1], sz[SUSNET_SPATIAL_MAX_CONV + 1]; // image size, channels, floats (ch * size^2)
+    int32_t Rc, R; // the RNN's input width R = Rc + Fn; its convolution columns
+};
+template <class NET>
+inline int check_spatial_net(const Refuse &bad, const std::string &net_prefix, const std::string &team_prefix, const NET &sn, int32_t n_dims,
+                             const int32_t *dims, int max_hidden, int max_out, SpatialGeom &g) {
+    const auto S = [](long long v) { return std::to_string(v); };
+    const auto range = [&](const std::string &field, long long v, long long lo, long long hi) {
+        return net_prefix + field + " = " + S(v) + " (served: " + S(lo) + " .. " + S(hi) + ")";
+    };
+    if (sn.T < 1 || sn.T > SUSNET_SPATIAL_MAX_T) return bad(range("T", sn.T, 1, SUSNET_SPATIAL_MAX_T));
+    if (sn.N < 1 || sn.N > SUSNET_SPATIAL_MAX_N) return bad(range("N", sn.N, 1, SUSNET_SPATIAL_MAX_N));
+    if (sn.C < 1 || sn.C > SUSNET_SPATIAL_MAX_C) return bad(range("C", sn.C, 1, SUSNET_SPATIAL_MAX_C));
+    if (sn.n_conv < 1 || sn.n_conv > SUSNET_SPATIAL_MAX_CONV) return bad(range("n_conv", sn.n_conv, 1, SUSNET_SPATIAL_MAX_CONV));
+    if (sn.k != 1 && sn.k != 3 && sn.k != 5) return bad(net_prefix + "k = " + S(sn.k) + " (served: one square kernel size of 1, 3 or 5)");
+    g = SpatialGeom{};
+    g.size[0] = sn.N, g.ch[0] = sn.C, g.sz[0] = sn.C * sn.N * sn.N;
+    for (int l = 0; l < sn.n_conv; l++) {
+        const std::string at = "[" + S(l) + "]";
+        if (sn.conv_out[l] < 1 || sn.conv_out[l] > 32) return bad(range("conv_out" + at, sn.conv_out[l], 1, 32));
+        if (sn.conv_stride[l] < 1 || sn.conv_stride[l] > 4) return bad(range("conv_stride" + at, sn.conv_stride[l], 1, 4));
+        if (sn.conv_padding[l] < 0 || sn.conv_padding[l] > 8) return bad(range("conv_padding" + at, sn.conv_padding[l], 0, 8));
+        if (sn.conv_dilation[l] < 1 || sn.conv_dilation[l] > 4) return bad(range("conv_dilation" + at, sn.conv_dilation[l], 1, 4));
+        const int span = g.size[l] + 2 * sn.conv_padding[l] - sn.conv_dilation[l] * (sn.k - 1) - 1;
+        if (span < 0) return bad(net_prefix + "conv layer " + S(l) + ": output size < 1 (input " + S(g.size[l]) + ", k " + S(sn.k) + ", conv_padding" + at +
+                                 " " + S(sn.conv_padding[l]) + ", conv_dilation" + at + " " + S(sn.conv_dilation[l]) + ")");
+        g.size[l + 1] = span / sn.conv_stride[l] + 1;
+        g.ch[l + 1] = sn.conv_out[l];
+        g.sz[l + 1] = g.ch[l + 1] * g.size[l + 1] * g.size[l + 1];
+    }
+    if (sn.Fn < 0) return bad(net_prefix + "Fn = " + S(sn.Fn) + " (at least 0)");
+    const long long R = (long long)g.sz[sn.n_conv] + sn.Fn;
+    if (R > SUSNET_SPATIAL_MAX_R)
+        return bad(net_prefix + "R = conv_out * H_out^2 + Fn = " + S(R) + " (the RNN's input width: at most SUSNET_SPATIAL_MAX_R = " + S(SUSNET_SPATIAL_MAX_R) + ")");
+    g.Rc = g.sz[sn.n_conv], g.R = (int32_t)R;
+    if (sn.rnn_layers < 1 || sn.rnn_layers > SUSNET_SPATIAL_MAX_RNN_LAYERS) return bad(range("rnn_layers", sn.rnn_layers, 1, SUSNET_SPATIAL_MAX_RNN_LAYERS));
+    if (sn.rnn_hidden < 1 || sn.rnn_hidden > max_hidden) return bad(range("rnn_hidden", sn.rnn_hidden, 1, max_hidden));
+    if (int rc = check_stack_n_dims(bad, team_prefix, n_dims, "a head of 1 .. 7 Linear layers")) return rc;
+    if (dims[0] != sn.rnn_hidden)
+        return bad(team_prefix + "dims[0] = " + S(dims[0]) + " (the head reads the hidden state: " + net_prefix + "rnn_hidden = " + S(sn.rnn_hidden) + ")");
+    return check_stack_dims(bad, team_prefix, n_dims, dims, max_hidden, max_out);
 }

@@ -63,6 +63,16 @@ struct SpatialRnnArgs {
     int32_t buf; // floats per hidden-state buffer: 64 rows x the widest of H and the head's hidden layers
 };
 
+#ifdef __HIPCC__
+// tanh as the forward (inst_qnet_spatial.hip) and the learner (inst_spatial_train.hip) compute it: exactly 0 at 0, exactly +-1 from |x| = 16
+__device__ __forceinline__ float sp_tanh(float x) {
+    const float ax = fabsf(x);
+    const float e = expm1f(-2.0f * ax); // in (-1, 0]: tanh |x| = (1 - e^{-2|x|}) / (1 + e^{-2|x|}) = -e / (e + 2), no cancellation near 0
+    const float t = ax >= 16.0f ? 1.0f : -e / (e + 2.0f);
+    return copysignf(t, x);
+}
+#endif
+
 // LDS bytes of a call's two kernels; they also fill in G / slot0 / slot1 and buf
 size_t spatial_conv_lds(SpatialConvArgs &a);
 size_t spatial_rnn_lds(SpatialRnnArgs &a);

@@ -31,7 +31,9 @@ through stock PyTorch-ROCm -- which is the faster of the two at large batches --
   imposter or the crew network by the env's role mask, argmax (optionally epsilon-greedy, train.py:355-381), step,
   window roll (np.roll, train.py:388-389) or refill with the fresh first state where an episode ended.  With ``kernels=True`` a
   served ``SpatialDQN`` runs through ``SpatialQNet`` -> ``susnet_spatial_forward`` (convolutions on the vector ALU, recurrence and head on
-  the f32-input MFMA), one call per team per tick for all ``B * A`` rows.
+  the f32-input MFMA), one call per team per tick for all ``B * A`` rows.  What a served ``SpatialDQN`` is, whether a featurizer feeds it
+  and how raw rows become the kernels' inputs is stated once, for the actor and the trainer: ``spatial_desc``, ``spatial_feed_mismatch``,
+  ``SpatialFeed``.
 """
 from __future__ import annotations
 
@@ -355,69 +357,134 @@ def _spatial_stack(model):
     return dict(convs=convs, k=convs[0].kernel_size[0], rnn=rnn, linears=head[0], acts=head[1], dims=head[2])
 
 
+def spatial_desc(model):
+    """The ONE description of a ``SpatialDQN`` the spatial kernels serve, or None: ``_spatial_stack`` within every bound of ``include/susnet.h``
+    (the C side of the same statement: ``check_spatial_net``, csrc/susnet_host.h) and the two LDS sizes (``spatial_conv_lds`` /
+    ``spatial_rnn_lds``, csrc/inst_qnet_spatial.hip).  ``dict(N, C, Fn, k, convs = [(out, stride, padding, dilation)], sizes = [N, layer
+    outputs ..], R, layers, hidden, linears, acts, dims, p)`` -- ``p`` the dropout between RNN layers (0.0 with one layer) -- and the modules
+    whose parameters are read in place (``conv_modules``, ``rnn``).  ``SpatialQNet`` acts with it, ``DeviceDQNTeamTrainer`` trains it."""
+    stack = _spatial_stack(model)
+    if stack is None:
+        return None
+    modules, k, rnn, dims = stack["convs"], stack["k"], stack["rnn"], stack["dims"]  # (dims[0] is rnn.hidden_size)
+    N, C, Fn = int(model.config["input_image_size"]), modules[0].in_channels, int(model.config["non_spatial_input_size"])
+    if k not in (1, 3, 5) or not 1 <= len(modules) <= L.SPATIAL_MAX_CONV or not 1 <= N <= L.SPATIAL_MAX_N or not 1 <= C <= L.SPATIAL_MAX_C or Fn < 0:
+        return None
+    convs, sizes = [(m.out_channels, m.stride[0], m.padding[0], m.dilation[0]) for m in modules], [N]
+    for out, stride, padding, dilation in convs:
+        span = sizes[-1] + 2 * padding - dilation * (k - 1) - 1
+        if not (1 <= out <= 32 and 1 <= stride <= 4 and 0 <= padding <= 8 and 1 <= dilation <= 4) or span < 0:
+            return None
+        sizes.append(span // stride + 1)
+    R, layers = convs[-1][0] * sizes[-1] ** 2 + Fn, rnn.num_layers
+    if R != rnn.input_size or R > L.SPATIAL_MAX_R or not 1 <= layers <= L.SPATIAL_MAX_RNN_LAYERS or \
+            not stack_within_bounds(dims, L.MLP_MAX_HIDDEN):  # (the head's input is the hidden state: rnn_hidden in 1 .. 256)
+        return None
+    slots = [C * N * N, 0]  # the convolution kernel's two LDS buffers per image (layer l writes buffer 1 - l % 2) ...
+    for l, (out, *_) in enumerate(convs[:-1]):
+        slots[1 - (l & 1)] = max(slots[1 - (l & 1)], out * sizes[l + 1] ** 2)
+    # ... and the recurrence's rotating hidden buffers
+    if 4 * sum(slots) > L.SPATIAL_LDS_BYTES or 4 * (layers + 1) * L.MLP_ROW_TILE * max(dims[:-1]) > L.SPATIAL_LDS_BYTES:
+        return None
+    return dict(N=N, C=C, Fn=Fn, k=k, convs=convs, sizes=sizes, R=R, layers=layers, hidden=rnn.hidden_size, linears=stack["linears"],
+                acts=stack["acts"], dims=dims, p=float(rnn.dropout) if layers > 1 else 0.0, conv_modules=modules, rnn=rnn)
+
+
+def fill_spatial_net(dst, desc, T: int) -> None:
+    """The network's shape in a ``SpatialIO`` or a ``SpatialNet`` (the same field names) from a ``spatial_desc``, as ``fill_stack`` does for the head."""
+    dst.T, dst.N, dst.C, dst.Fn, dst.n_conv, dst.k = T, desc["N"], desc["C"], desc["Fn"], len(desc["convs"]), desc["k"]
+    for l, conv in enumerate(desc["convs"]):
+        dst.conv_out[l], dst.conv_stride[l], dst.conv_padding[l], dst.conv_dilation[l] = conv
+    dst.rnn_layers, dst.rnn_hidden = desc["layers"], desc["hidden"]
+
+
+def spatial_feed_mismatch(env, featurizer, desc, n_actions: int) -> Optional[str]:
+    """Why the tensors of ``featurizer`` (Global / Perspective, over ``env``) do not feed the network of ``desc`` with ``n_actions`` outputs, or
+    None if they do: the actor, the trainer and ``train_loop.spatial_unserved_reason`` ask here."""
+    from .features import GlobalFeaturizer
+
+    # the featurizer's own shapes: planes [.., C, N, N]; non-spatial columns per agent view (the Global featurizer appends onehot(agent))
+    _, planes, non_spatial = env._make_obs(featurizer.config, 1, rows=1)
+    if non_spatial is None:  # (forward() takes a real non_spatial tensor)
+        return "the featurizer has no non-spatial block"
+    Fn = non_spatial.shape[-1] + (env.n_agents if isinstance(featurizer, GlobalFeaturizer) else 0)
+    reads, want = (desc["C"], desc["N"], desc["Fn"], desc["dims"][-1]), (planes.shape[-3], planes.shape[-1], Fn, n_actions)
+    if reads != want:
+        return f"the network reads (channels, image size, non-spatial width, actions) = {reads}, the featurizer and the game give {want}"
+    return None
+
+
+def spatial_strides(x, inner: int, agents: int, what: str):
+    """(env, agent, timestep) strides in floats of ``x``: ``[B, T, A, *inner]`` (a view per agent) or ``[B, T, *inner]`` (one for all)."""
+    per_agent = x.dim() == inner + 3
+    assert x.dim() in (inner + 2, inner + 3) and x.dtype == torch.float32, f"SpatialQNet: {what} is float32 [B, T, (A,) ...], got {tuple(x.shape)} {x.dtype}"
+    tail = x.shape[-inner:]
+    want, expect = 1, []
+    for d in reversed(tail):
+        expect.insert(0, want)
+        want *= d
+    assert all(d == 1 or s == e for d, s, e in zip(tail, x.stride()[-inner:], expect)), f"SpatialQNet: the last {inner} dimensions of {what} must be contiguous"
+    if per_agent:
+        assert x.shape[2] == agents, f"SpatialQNet: {what} has {x.shape[2]} agent views, agents = {agents}"
+        return x.stride(0), x.stride(2), x.stride(1)
+    return x.stride(0), 0, x.stride(1)
+
+
+class SpatialFeed:
+    """Raw rows to kernel inputs for ``n`` windows of ``T`` states: the reused ``_make_obs`` buffers of ``n * T`` rows, ONE ``susnet_featurize``
+    launch per ``featurize``, and the tensors ``susnet_spatial_forward`` / ``susnet_spatial_train_step`` read where they lie -- ``spatial``
+    (the Perspective featurizer's per-agent views ``[n, T, A, C, N, N]``, the Global featurizer's shared planes ``[n, T, C, N, N]``) and
+    ``non_spatial`` ``[n, T, A, Fn]`` (the Global rows with every agent's one-hot appended, model_ready.py:291-306: the one-hot columns are
+    written once, here; ``finish`` copies the rest behind a launch).  The actor keeps one, the trainer two (states and next states)."""
+
+    def __init__(self, env, featurizer, n: int, T: int):
+        from .features import GlobalFeaturizer
+
+        self.env, self.n, self.T = env, n, T
+        self.spec, planes, self._non = env._make_obs(featurizer.config, 1, rows=n * T)
+        self.spatial, self._glob = planes.view(n, T, *planes.shape[1:]), None
+        if isinstance(featurizer, GlobalFeaturizer):
+            A = env.n_agents
+            Fn = self._non.shape[-1] + A
+            self._glob = torch.empty(n, T, A, Fn, dtype=torch.float32, device=env.device)
+            self._glob[..., Fn - A:] = torch.eye(A, dtype=torch.float32, device=env.device)
+        self.non_spatial = self._glob if self._glob is not None else self._non.view(n, T, *self._non.shape[1:])
+
+    def featurize(self, rows: torch.Tensor) -> None:
+        """The launch (on the caller's device context; the featurizer's row check is the caller's to poll)."""
+        env = self.env
+        L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], self.n * self.T, C.byref(self.spec), env._stream()))
+
+    def finish(self) -> None:
+        """Behind ``featurize``: the Global featurizer's non-spatial columns into the per-agent rows (nothing to do for Perspective)."""
+        if self._glob is not None:
+            base = self._non.shape[-1]
+            self._glob[..., :base] = self._non.view(self.n, self.T, 1, base)
+
+    def strides(self, agents: int):
+        """``(spatial, non_spatial)`` strides, three each, as the io structs take them."""
+        return spatial_strides(self.spatial, 3, agents, "spatial"), spatial_strides(self.non_spatial, 1, agents, "non_spatial")
+
+
 class SpatialQNet:
     """A reference ``SpatialDQN`` served by ``susnet_spatial_forward``: the module's EVAL-mode forward (dqn.py:205-301) as two HIP kernels on
     the featurizers' ``(spatial, non_spatial)`` tensors where they lie.  ``SpatialQNet(env, model)`` is None for anything the kernels do not
-    serve -- another module, a non-square kernel / stride / padding / dilation, kernel sizes other than 1, 3, 5, an RNN that is not a
-    unidirectional tanh ``nn.RNN`` with biases, a per-channel PReLU, a bound of ``include/susnet.h`` exceeded (callers then run the module).
+    serve (``spatial_desc``) -- another module, a non-square kernel / stride / padding / dilation, kernel sizes other than 1, 3, 5, an RNN that
+    is not a unidirectional tanh ``nn.RNN`` with biases, a per-channel PReLU, a bound of ``include/susnet.h`` exceeded (callers then run the module).
 
     Like ``DenseQNet`` nothing is packed or cached: every ``forward`` takes the parameters' ``data_ptr()``s afresh, so ``optimizer.step`` and
     ``load_state_dict`` are followed without a refresh.  The RNN-input workspace ``[n, T, R]`` and the default output buffer are owned and
     re-made when the shape changes."""
 
     def __new__(cls, env, model):
-        stack = _spatial_stack(model)
-        if stack is None:
-            return None
-        convs, k, rnn, dims = stack["convs"], stack["k"], stack["rnn"], stack["dims"]  # (dims[0] is rnn.hidden_size)
-        cfg = model.config
-        N, C, Fn = int(cfg["input_image_size"]), convs[0].in_channels, int(cfg["non_spatial_input_size"])
-        if k not in (1, 3, 5) or not 1 <= len(convs) <= L.SPATIAL_MAX_CONV or not 1 <= N <= L.SPATIAL_MAX_N or not 1 <= C <= L.SPATIAL_MAX_C or Fn < 0:
-            return None
-        size = N
-        for m in convs:
-            if not (1 <= m.out_channels <= 32 and 1 <= m.stride[0] <= 4 and 0 <= m.padding[0] <= 8 and 1 <= m.dilation[0] <= 4):
-                return None
-            span = size + 2 * m.padding[0] - m.dilation[0] * (k - 1) - 1
-            if span < 0:
-                return None
-            size = span // m.stride[0] + 1
-        R = convs[-1].out_channels * size * size + Fn
-        layers = rnn.num_layers
-        if R != rnn.input_size or R > L.SPATIAL_MAX_R or not 1 <= layers <= L.SPATIAL_MAX_RNN_LAYERS or \
-                not stack_within_bounds(dims, L.MLP_MAX_HIDDEN):  # (the head's input is the hidden state: rnn_hidden in 1 .. 256)
-            return None
-        slot0, slot1, s = C * N * N, 0, N  # the convolution kernel's two LDS buffers per image, and the recurrence's rotating hidden buffers
-        for l, m in enumerate(convs[:-1]):
-            s = (s + 2 * m.padding[0] - m.dilation[0] * (k - 1) - 1) // m.stride[0] + 1
-            if l & 1:
-                slot0 = max(slot0, m.out_channels * s * s)
-            else:
-                slot1 = max(slot1, m.out_channels * s * s)
-        if 4 * (slot0 + slot1) > L.SPATIAL_LDS_BYTES or 4 * (layers + 1) * L.MLP_ROW_TILE * max(dims[:-1]) > L.SPATIAL_LDS_BYTES:
+        desc = spatial_desc(model)
+        if desc is None:
             return None
         self = super().__new__(cls)
-        self.env, self.model = env, model
-        self.N, self.C, self.Fn, self.R, self.k, self.dims = N, C, Fn, R, k, dims
-        self._convs, self._rnn, self._linears, self._acts = convs, rnn, stack["linears"], stack["acts"]
+        self.env, self.model, self.desc = env, model, desc
+        self.N, self.C, self.Fn, self.R, self.k, self.dims = (desc[f] for f in ("N", "C", "Fn", "R", "k", "dims"))
         self._q = self._rnn_in = None
         return self
-
-    @staticmethod
-    def _strides(x, inner: int, agents: int, what: str):
-        """(env, agent, timestep) strides in floats of ``x``: ``[B, T, A, *inner]`` (a view per agent) or ``[B, T, *inner]`` (one for all)."""
-        per_agent = x.dim() == inner + 3
-        assert x.dim() in (inner + 2, inner + 3) and x.dtype == torch.float32, f"SpatialQNet: {what} is float32 [B, T, (A,) ...], got {tuple(x.shape)} {x.dtype}"
-        tail = x.shape[-inner:]
-        want, expect = 1, []
-        for d in reversed(tail):
-            expect.insert(0, want)
-            want *= d
-        assert all(d == 1 or s == e for d, s, e in zip(tail, x.stride()[-inner:], expect)), f"SpatialQNet: the last {inner} dimensions of {what} must be contiguous"
-        if per_agent:
-            assert x.shape[2] == agents, f"SpatialQNet: {what} has {x.shape[2]} agent views, agents = {agents}"
-            return x.stride(0), x.stride(2), x.stride(1)
-        return x.stride(0), 0, x.stride(1)
 
     @torch.no_grad()
     def forward(self, spatial: torch.Tensor, non_spatial: torch.Tensor, agents: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -425,15 +492,15 @@ class SpatialQNet:
         ``spatial`` ``[B, T, A, C, N, N]`` (PerspectiveFeaturizer) or ``[B, T, C, N, N]`` (GlobalFeaturizer's shared planes: every agent
         reads the same image), ``non_spatial`` ``[B, T, A, Fn]`` or ``[B, T, Fn]``.  ``out``: where they go (default: a buffer this object
         keeps: a result is valid until the next call).  Two launches, asynchronous."""
-        env, model, rnn = self.env, self.model, self._rnn
+        env, model, desc, rnn = self.env, self.model, self.desc, self.desc["rnn"]
         if model.training and rnn.dropout > 0 and rnn.num_layers > 1:
             raise RuntimeError("SpatialQNet: the model is in training mode with rnn_dropout > 0 between its RNN layers; the kernels compute the "
                                "eval-mode forward (no dropout): call model.eval(), or run the torch module")
         dev = env.device
         assert spatial.device == dev and non_spatial.device == dev, f"SpatialQNet: inputs on {dev}"
         agents = int(agents)
-        sp = self._strides(spatial, 3, agents, "spatial")
-        ns = self._strides(non_spatial, 1, agents, "non_spatial")
+        sp = spatial_strides(spatial, 3, agents, "spatial")
+        ns = spatial_strides(non_spatial, 1, agents, "non_spatial")
         B, T = spatial.shape[:2]
         assert tuple(spatial.shape[-3:]) == (self.C, self.N, self.N) and non_spatial.shape[-1] == self.Fn and tuple(non_spatial.shape[:2]) == (B, T), (
             f"SpatialQNet: spatial [.., {self.C}, {self.N}, {self.N}] and non_spatial [.., {self.Fn}] with the same [B, T], got "
@@ -444,15 +511,13 @@ class SpatialQNet:
             self._rnn_in = torch.empty(n, T, self.R, dtype=torch.float32, device=dev)
         ptr = partial(_param_ptr, dev, "SpatialQNet")
         io = L.SpatialIO()
-        io.T, io.N, io.C, io.n_conv, io.k, io.Fn = T, self.N, self.C, len(self._convs), self.k, self.Fn
-        for l, m in enumerate(self._convs):
-            io.conv_out[l], io.conv_stride[l], io.conv_padding[l], io.conv_dilation[l] = m.out_channels, m.stride[0], m.padding[0], m.dilation[0]
+        fill_spatial_net(io, desc, T)
+        for l, m in enumerate(desc["conv_modules"]):
             io.conv_weight[l], io.conv_bias[l] = ptr(m.weight), ptr(m.bias)
-        io.rnn_layers, io.rnn_hidden = rnn.num_layers, rnn.hidden_size
         for l in range(rnn.num_layers):
             for name, field in (("weight_ih", io.w_ih), ("weight_hh", io.w_hh), ("bias_ih", io.b_ih), ("bias_hh", io.b_hh)):
                 field[l] = ptr(getattr(rnn, f"{name}_l{l}"))
-        fill_stack(io, self._linears, self._acts, ptr)
+        fill_stack(io, desc["linears"], desc["acts"], ptr)
         io.spatial, io.non_spatial = spatial.data_ptr(), non_spatial.data_ptr()
         for d in range(3):
             io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
@@ -795,7 +860,7 @@ class WindowedPolicyRollout:
         self._gen.manual_seed(seed)
         self.window = None
         self._actions = torch.zeros(env.batch, env.n_agents, dtype=torch.int64, device=env.device)
-        self._q_bufs = None  # q_rows(): (featurize spec, planes, non-spatial rows, the Global rows with the one-hot columns)
+        self._feed = None  # q_rows(): the SpatialFeed of the B windows
 
     @property
     def sequence_length(self) -> int:
@@ -807,15 +872,7 @@ class WindowedPolicyRollout:
         net = SpatialQNet(self.env, model)
         if net is None or not isinstance(self.featurizer, (GlobalFeaturizer, PerspectiveFeaturizer)) or self.T > L.SPATIAL_MAX_T:
             return None
-        env, A = self.env, self.env.n_agents
-        # the featurizer's own shapes: planes [.., C, N, N]; non-spatial columns per agent view (the Global featurizer appends onehot(agent))
-        _, planes, non_spatial = env._make_obs(self.featurizer.config, 1, rows=1)
-        Fn = (non_spatial.shape[-1] if non_spatial is not None else 0) + (A if isinstance(self.featurizer, GlobalFeaturizer) else 0)
-        if non_spatial is None:  # (a featurizer without a non-spatial block: forward() takes a real non_spatial tensor)
-            return None
-        if (net.C, net.N, net.Fn, net.dims[-1]) != (planes.shape[-3], planes.shape[-1], Fn, n_actions):
-            return None
-        return net
+        return net if spatial_feed_mismatch(self.env, self.featurizer, net.desc, n_actions) is None else None
 
     def kernel_inputs(self):
         """``(spatial, non_spatial)`` of the fitted featurizer as ``SpatialQNet.forward`` takes them: the Perspective featurizer's buffers in
@@ -877,38 +934,21 @@ class WindowedPolicyRollout:
     @torch.no_grad()
     def q_rows(self):
         """``(q_imposter [B * A, n], q_crew [B * A, n] or None)`` of the acting window: ONE ``susnet_featurize`` launch over its ``B * T`` rows
-        into reused buffers, the Global featurizer's non-spatial rows with every agent's one-hot appended (the one-hot columns written
-        once, as ``DeviceDQNTeamTrainer._spatial_step`` does), and one ``SpatialQNet.forward`` per team that has a model.  Row
-        ``b * A + i`` = env b, agent i; a result is valid until the next call."""
-        from .features import GlobalFeaturizer
-
-        env, T = self.env, self.T
-        B, A = env.batch, env.n_agents
+        into reused buffers (a ``SpatialFeed``), and one ``SpatialQNet.forward`` per team that has a model.  Row ``b * A + i`` = env b, agent i; a
+        result is valid until the next call."""
+        env, A = self.env, self.env.n_agents
         assert self.spatial_imposter is not None and (self.crew_model is None or self.spatial_crew is not None), (
             "q_rows: susnet_spatial_forward does not serve this policy (WindowedPolicyRollout(kernels=True) with SpatialDQN models)")
         assert self.window is not None, "q_rows: no window yet (reset_window / load_window)"
-        glob = isinstance(self.featurizer, GlobalFeaturizer)
-        if self._q_bufs is None:
-            spec, planes, non = env._make_obs(self.featurizer.config, 1, rows=B * T)
-            g = None
-            if glob:
-                Fn = non.shape[-1] + A
-                g = torch.empty(B, T, A, Fn, dtype=torch.float32, device=env.device)
-                g[..., Fn - A:] = torch.eye(A, dtype=torch.float32, device=env.device)
-            self._q_bufs = (spec, planes, non, g)
-        spec, planes, non, g = self._q_bufs
-        rows = self.window
+        if self._feed is None:
+            self._feed = SpatialFeed(env, self.featurizer, env.batch, self.T)
+        feed = self._feed
         with env._on_device():
             # (the window's rows were written by the stepping kernel: valid by construction, the featurizer's row check is not polled)
-            L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], B * T, C.byref(spec), env._stream()))
-        if glob:
-            base = non.shape[-1]
-            g[..., :base] = non.view(B, T, 1, base)
-            spatial, non_spatial = planes.view(B, T, *planes.shape[1:]), g
-        else:
-            spatial, non_spatial = planes.view(B, T, *planes.shape[1:]), non.view(B, T, *non.shape[1:])
-        q_imp = self.spatial_imposter.forward(spatial, non_spatial, A)
-        q_crew = self.spatial_crew.forward(spatial, non_spatial, A) if self.spatial_crew is not None else None
+            feed.featurize(self.window)
+        feed.finish()
+        q_imp = self.spatial_imposter.forward(feed.spatial, feed.non_spatial, A)
+        q_crew = self.spatial_crew.forward(feed.spatial, feed.non_spatial, A) if self.spatial_crew is not None else None
         return q_imp, q_crew
 
     @torch.no_grad()

@@ -27,7 +27,8 @@ import torch
 from . import _lib as L
 from .episodes import EpisodeLog
 from .metrics import EpisodicMetricHandler, SusMetrics
-from .policy import MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, SpatialQNet, WindowedPolicyRollout, acts_per_agent, served_by_kernels
+from .policy import (MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout, acts_per_agent, served_by_kernels, spatial_desc,
+                     spatial_feed_mismatch)
 from .replay import DeviceReplayBuffer
 from .scheduler import ExponentialSchedule
 from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer
@@ -334,21 +335,13 @@ def spatial_unserved_reason(env, featurizer, model, n_actions: int, T: int) -> O
         return "the featurizer must be a GlobalFeaturizer / PerspectiveFeaturizer over the env that is trained on"
     if not 1 <= T <= L.SPATIAL_MAX_T:
         return f"sequence_length = {T}: windows of 1 .. {L.SPATIAL_MAX_T} states are served (SUSNET_SPATIAL_MAX_T)"
-    net = SpatialQNet(env, model)
-    if net is None:
+    desc = spatial_desc(model)
+    if desc is None:
         return ("susnet_spatial_forward does not serve this module: square 1 / 3 / 5 kernels, at most "
                 f"{L.SPATIAL_MAX_CONV} convolutions of at most 32 channels on images of at most {L.SPATIAL_MAX_N} x {L.SPATIAL_MAX_N} x "
                 f"{L.SPATIAL_MAX_C}, an RNN input of at most {L.SPATIAL_MAX_R}, at most {L.SPATIAL_MAX_RNN_LAYERS} unidirectional tanh RNN layers "
                 f"with biases, a Linear + single-slope PReLU head of widths up to {L.MLP_MAX_HIDDEN}")
-    _, planes, non_spatial = env._make_obs(featurizer.config, 1, rows=1)
-    if non_spatial is None:
-        return "the featurizer has no non-spatial block"
-    Fn = non_spatial.shape[-1] + (env.n_agents if isinstance(featurizer, GlobalFeaturizer) else 0)
-    want = (planes.shape[-3], planes.shape[-1], Fn, n_actions)
-    if (net.C, net.N, net.Fn, net.dims[-1]) != want:
-        return (f"the network reads (channels, image size, non-spatial width, actions) = {(net.C, net.N, net.Fn, net.dims[-1])}, the "
-                f"featurizer and the game give {want}")
-    return None
+    return spatial_feed_mismatch(env, featurizer, desc, n_actions)
 
 
 def _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size, replay_prepopulate_steps,

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib as L
-from .policy import MLP, RandomEquiprobable, SpatialQNet, _spatial_stack, _weights_version, dense_stack, linear_prelu_stack
+from .policy import MLP, RandomEquiprobable, SpatialFeed, _weights_version, dense_stack, fill_spatial_net, linear_prelu_stack, spatial_desc, spatial_feed_mismatch
 
 BETAS, EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults (train.py:35-37 passes only lr)
 
@@ -157,7 +157,7 @@ class DeviceDQNTeamTrainer:
                               for m, tr in zip(self.models, self.trained)]
         self.spatial = (bool(spatial) and self.device.type == "cuda" and any(self.trained) and self._spatial_featurizer() is not None
                         and all(d is not None for d, tr in zip(self._spatial_nets, self.trained) if tr) and self._spatial_served())
-        self._spatial_bufs = None  # (n, T, gathered states, gathered next states, obs of states, obs of next states, Global non-spatial rows x 2)
+        self._spatial_bufs = None  # (n, T, gathered states, gathered next states, SpatialFeed of the states, of the next states)
 
     # ---- configuration ----
     @staticmethod
@@ -263,25 +263,18 @@ class DeviceDQNTeamTrainer:
         return None
 
     def _spatial_net(self, model, dropout: bool = False):
-        """What ``susnet_spatial_train_step`` needs to know of a ``SpatialDQN`` that ``SpatialQNet`` serves and whose training-mode forward
-        the kernels compute (no dropout between RNN layers; with ``dropout``: ``susnet_spatial_train_step_dropout`` computes it), or None."""
-        stack = _spatial_stack(model)
-        if stack is None or SpatialQNet(self.env, model) is None:
+        """``policy.spatial_desc`` of a ``SpatialDQN`` whose training-mode forward the kernels compute too -- the trainer's two own rules: no
+        dropout between RNN layers (with ``dropout``: ``susnet_spatial_train_step_dropout`` computes it) and ``parameters()`` in the order of
+        the flat layout the kernels assume (convolutions, RNN layer by layer, head) -- or None."""
+        d = spatial_desc(model)
+        if d is None or (d["p"] > 0 and not dropout):  # (nn.RNN drops out between layers in training mode: the plain kernels do not)
             return None
-        rnn = stack["rnn"]
-        if rnn.dropout > 0 and rnn.num_layers > 1 and not dropout:
-            return None  # (nn.RNN drops out between layers in training mode: the plain kernels do not)
-        convs = stack["convs"]
-        # parameters() order must be the flat layout the kernels assume: convolutions, RNN layer by layer, head
         names = [n for n, _ in model.named_parameters()]
-        want = [f"cnn.model.{2 * l}.{w}" for l in range(len(convs)) for w in ("weight", "bias")]
-        want += [f"rnn.model.{w}_l{l}" for l in range(rnn.num_layers) for w in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        want = [f"cnn.model.{2 * l}.{w}" for l in range(len(d["convs"])) for w in ("weight", "bias")]
+        want += [f"rnn.model.{w}_l{l}" for l in range(d["layers"]) for w in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
         if names[:len(want)] != want or not all(n.startswith("prediction_head.") for n in names[len(want):]):
             return None
-        cfg = model.config
-        return dict(N=int(cfg["input_image_size"]), C=convs[0].in_channels, Fn=int(cfg["non_spatial_input_size"]), k=stack["k"],
-                    convs=[(m.out_channels, m.stride[0], m.padding[0], m.dilation[0]) for m in convs], layers=rnn.num_layers,
-                    hidden=rnn.hidden_size, dims=stack["dims"], p=float(rnn.dropout) if rnn.num_layers > 1 else 0.0)
+        return d
 
     def _spatial_dropout(self):
         """The two ``susnet_rnn_dropout`` ([imposter, crew]) of the next dropout step, or None where no trained team has dropout to apply."""
@@ -305,23 +298,13 @@ class DeviceDQNTeamTrainer:
             if not self.trained[t] or d is None:
                 continue
             self._fill_team(io.team[t], t, d["dims"])
-            net = io.net[t]
-            net.T, net.N, net.C, net.Fn, net.n_conv, net.k = T, d["N"], d["C"], d["Fn"], len(d["convs"]), d["k"]
-            for l, (co, st, pad, dil) in enumerate(d["convs"]):
-                net.conv_out[l], net.conv_stride[l], net.conv_padding[l], net.conv_dilation[l] = co, st, pad, dil
-            net.rnn_layers, net.rnn_hidden = d["layers"], d["hidden"]
+            fill_spatial_net(io.net[t], d, T)
         return io
 
     def _spatial_served(self) -> bool:
-        env, A = self.env, self.env.n_agents
-        _, planes, non_spatial = env._make_obs(self._featurizer.config, 1, rows=1)
-        if non_spatial is None:
-            return False
-        Fn = non_spatial.shape[-1] + (A if self._spatial_featurizer() == "global" else 0)
-        n_actions = (env.n_imposter_actions, env.n_crew_actions)
-        for t in range(2):
-            d = self._spatial_nets[t]
-            if self.trained[t] and (d["C"], d["N"], d["Fn"], d["dims"][-1]) != (planes.shape[-3], planes.shape[-1], Fn, n_actions[t]):
+        env = self.env
+        for t, n_actions in enumerate((env.n_imposter_actions, env.n_crew_actions)):
+            if self.trained[t] and spatial_feed_mismatch(env, self._featurizer, self._spatial_nets[t], n_actions) is not None:
                 return False  # the networks do not read this featurizer's tensors
         io = self._spatial_io(1)
         io.max_size, io.n = 1, 1
@@ -417,41 +400,24 @@ class DeviceDQNTeamTrainer:
         return self._losses.clone()
 
     def _spatial_step(self, ring, idx):
-        """Gather the batch's ``[n, T, S]`` windows and next windows and featurize them (``n * T`` rows, the featurizer's kernel) into reused
-        buffers, then ``susnet_spatial_train_step`` on the planes where they lie: the Perspective featurizer's per-agent views in place, the
-        Global featurizer's shared planes with an agent stride of 0 and its non-spatial rows with every agent's one-hot appended
-        (``[n, T, A, Fn]``, as ``WindowedPolicyRollout.kernel_inputs`` builds them).  Nothing waits on the host (with ``env.check_errors``
-        the featurizer's row check is polled)."""
+        """Gather the batch's ``[n, T, S]`` windows and next windows and featurize them (two ``policy.SpatialFeed``s: ``n * T`` rows each, the
+        featurizer's kernel, reused buffers), then ``susnet_spatial_train_step`` on the tensors where they lie.  Nothing waits on the host
+        (with ``env.check_errors`` the featurizer's row check is polled)."""
         env, n, T, A = self.env, int(idx.numel()), ring.trajectory_size, self.env.n_agents
-        kind = self._spatial_featurizer()
         for t in range(2):
             self._state_to_flat(t)
         io = self._spatial_io(T)
         if n > 0:
             if self._spatial_bufs is None or self._spatial_bufs[:2] != (n, T):
-                oc = self._featurizer.config
-                obs, next_obs = env._make_obs(oc, 1, rows=n * T), env._make_obs(oc, 1, rows=n * T)
-                glob = [None, None]
-                if kind == "global":
-                    Fn = obs[2].shape[-1] + A
-                    glob = [torch.empty(n, T, A, Fn, dtype=torch.float32, device=self.device) for _ in range(2)]
-                    for g in glob:  # (the one-hot columns never change)
-                        g[..., Fn - A:] = torch.eye(A, dtype=torch.float32, device=self.device)
                 self._spatial_bufs = (n, T, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
                                       torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
-                                      obs, next_obs, glob[0], glob[1])
-            _, _, rows, next_rows, (spec, planes, non), (next_spec, next_planes, next_non), g, next_g = self._spatial_bufs
+                                      SpatialFeed(env, self._featurizer, n, T), SpatialFeed(env, self._featurizer, n, T))
+            _, _, rows, next_rows, feed, next_feed = self._spatial_bufs
             torch.index_select(ring.states, 0, idx, out=rows)
             torch.index_select(ring.next_states, 0, idx, out=next_rows)
-            img = planes[0].numel() if kind == "global" else planes[0, 0].numel()  # floats of one [C, N, N] image
-            if kind == "global":  # planes [n T, C, N, N], shared by the agents; non-spatial rows built below
-                sp, ns = (T * img, 0, img), (g.stride(0), g.stride(2), g.stride(1))
-                non_ptr, next_non_ptr = g.data_ptr(), next_g.data_ptr()
-            else:                 # planes [n T, A, C, N, N], non-spatial [n T, A, F2]
-                f2 = non.shape[-1]
-                sp, ns = (T * A * img, img, A * img), (T * A * f2, f2, A * f2)
-                non_ptr, next_non_ptr = non.data_ptr(), next_non.data_ptr()
-            io.spatial, io.next_spatial, io.non_spatial, io.next_non_spatial = planes.data_ptr(), next_planes.data_ptr(), non_ptr, next_non_ptr
+            io.spatial, io.next_spatial = feed.spatial.data_ptr(), next_feed.spatial.data_ptr()
+            io.non_spatial, io.next_non_spatial = feed.non_spatial.data_ptr(), next_feed.non_spatial.data_ptr()
+            sp, ns = feed.strides(A)
             for d in range(3):
                 io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
         io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
@@ -462,15 +428,12 @@ class DeviceDQNTeamTrainer:
                                    else env.lib.susnet_spatial_train_dropout_workspace_bytes)
         with torch.cuda.device(self.device):
             if n > 0:
-                dt = env._ROW_DTYPES[rows.dtype]
-                L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), dt, n * T, C.byref(spec), env._stream()))
-                L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n * T, C.byref(next_spec), env._stream()))
+                feed.featurize(rows)
+                next_feed.featurize(next_rows)
                 if env.check_errors:
                     env.poll_errors()
-                if kind == "global":
-                    base = non.shape[-1]
-                    g[..., :base] = non.view(n, T, 1, base)
-                    next_g[..., :base] = next_non.view(n, T, 1, base)
+                feed.finish()
+                next_feed.finish()
             if drop is None:
                 L.check(env.lib.susnet_spatial_train_step(env._h, C.byref(io), env._stream()))
             else:
