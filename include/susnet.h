@@ -868,6 +868,44 @@ int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_spatial_trai
 int susnet_rnn_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agent, int32_t layers, int64_t n, int32_t T,
                             int32_t H, float *out, void *stream);
 
+/* A sweep's train step for the SpatialDQN.  The reference's users run sweeps -- notebooks/experiment_1v1.ipynb and
+ * notebooks/experiment_mlp.ipynb loop `for config in configs: run_experiment(**config)` over gamma ([0.99, 0.9, 0.8]) and the learning
+ * rate -- and run_experiment's default model is the SpatialDQN (src/train.py:152-176, src/models/dqn.py:205-301); every run takes
+ * DQNTeamTrainer.train_step (src/train.py:50-149) on its own.  At the reference's batch size (32 rows: one tile of the recurrence kernel)
+ * one learner's step is a chain of 1 + 4 x agents x enabled teams launches in which a single workgroup works; this call runs the steps of
+ * n_learners independent learners of one shape in the SAME launches, the learner being the grid's second dimension -- what
+ * susnet_dqn_train_sweep does for the fused MLP learner.
+ *   ios[k] is a complete susnet_spatial_train_io as susnet_spatial_train_step takes it -- its own batch tensors, ring pointers, indices,
+ * gamma, Adam constants, parameters, losses_out and its own workspace, of susnet_spatial_train_workspace_bytes(envs[k], &ios[k]) bytes
+ * where drops == NULL and of susnet_spatial_train_dropout_workspace_bytes otherwise -- and passes every check of that call (the same plan,
+ * pointer and dropout checks run per learner; a learner's own message is carried through behind "learner k: ").  The handles supply
+ * configuration only.  drops == NULL: every learner takes the plain step.  Otherwise drops[2 k + team] is what
+ * susnet_spatial_train_step_dropout would get as drop[team] for learner k.
+ *   Served: 1 .. SUSNET_SPATIAL_SWEEP_MAX_LEARNERS learners, each one served by the single call, that AGREE on what shapes the step: agent
+ * and imposter count, n, both teams' `enabled`, every field of net[] and team[].n_dims / dims of the enabled teams, the three spatial
+ * strides and (Fn > 0) the three non-spatial strides, and per team whether the team is masked (a p > 0 with more than one RNN layer: it
+ * selects the recurrence kernel).  gamma, the Adam constants, max_size, every pointer and the dropout seed, offset, row_base and p values
+ * may differ.  No two learners share `params` (of either team), `workspace` or `losses_out`.  `table` is device scratch of
+ * susnet_spatial_train_sweep_table_bytes(n_learners) bytes, 256-byte aligned: a learner's record (pointers, gamma, dropout constants,
+ * about 250 bytes) times 16 and the two networks' descriptions exceed the 4 KB of a launch's arguments, so the select launches write the
+ * records there from their arguments -- no copy from the host, the call stays capturable -- and the update's kernels read them through a
+ * pointer; what the learners agree on (networks, strides, n, agent count, workspace offsets) is kept once.  The table carries 16 learners.
+ * Anything else: SUSNET_E_INVALID before anything is launched, the message naming the entry point, the first offending learner and the
+ * field ("susnet_spatial_train_sweep: learner 2: net[0].rnn_hidden differs from learner 0's ..").
+ *   After the call every learner's params, exp_avg, exp_avg_sq, step (of either team) and losses_out hold BIT FOR BIT what its own
+ * susnet_spatial_train_step(envs[k], &ios[k], stream) -- with drops: susnet_spatial_train_step_dropout(envs[k], &ios[k], drops + 2 k,
+ * stream) -- would have left: workgroup (g, k) walks the tiles and images workgroup g of that call walks, in the same summation order, and
+ * writes the same partial slot.  A learner whose (agent, team) list is empty skips that update (train.py:101) whatever the others do.
+ *   Launches: S to split the batches and fill the table -- S = 1 for n_learners <= 8, S = 2 above (8 learners' records per launch) --, then
+ * 4 per (agent, enabled team) update (convolutions, recurrence, convolutions' backward, and the fused learner's sweep form of k_train_adam
+ * over the learners): S + 4 x agents x enabled teams per call whatever n_learners and the data are (n == 0: the S launches alone, which zero
+ * every learner's losses).  All on `stream`, no host synchronisation, no parallel branches, no atomics: a call can be captured as a
+ * hipGraph (after one eager call, which sets the recurrence kernels' LDS ceilings). */
+#define SUSNET_SPATIAL_SWEEP_MAX_LEARNERS 16
+int susnet_spatial_train_sweep_table_bytes(int32_t n_learners, uint64_t *bytes_out);
+int susnet_spatial_train_sweep(susnet_env *const *envs, const susnet_spatial_train_io *ios, const susnet_rnn_dropout *drops /* [n_learners][2] or NULL */,
+                               int32_t n_learners, void *table, uint64_t table_bytes, void *stream);
+
 /* Per-episode returns and lengths from a feed block -- train()'s bookkeeping (src/train.py:385-386, 419-450) for B environments in
  * lockstep.  Inputs: the [T][B] feed arrays as susnet_qnet_policy_rollout / susnet_step write them and susnet_ring_append reads them.
  * Per tick t and environment b, for every agent: G[a] = (double)rewards[t][b][a] + gamma * G[a] in float64, the product rounded before

@@ -36,49 +36,7 @@ __global__ __launch_bounds__(kTrThreads) void k_sp_train_select(SpTrainBatch b, 
 __global__ __launch_bounds__(kStConvThreads) void k_sp_train_conv(SpTrainBatch b, const SpTrainNet *__restrict__ netp, SpTrainWs ws, const float *__restrict__ prm,
                                                                   const float *__restrict__ tgt, const int32_t *__restrict__ lists,
                                                                   const int32_t *__restrict__ counts, int agent, int team) {
-    const int tid = threadIdx.x;
-    const int count = counts[2 * agent + team];
-    if (count == 0) return;
-    const SpTrainNet &net = *netp;
-    const int32_t *list = lists + ((int64_t)agent * 2 + team) * b.n;
-    const int64_t nimg = (int64_t)count * net.T;
-    float *slice = ws.tact + (size_t)blockIdx.x * 2 * net.maxsz;
-    for (int64_t job = blockIdx.x; job < 2 * nimg; job += gridDim.x) {
-        const bool target = job >= nimg;
-        const int64_t img = target ? job - nimg : job;
-        const int64_t j = img / net.T;
-        const int step = (int)(img % net.T);
-        const int64_t s = st_clamp(list[j], b.n);
-        const float *P = target ? tgt : prm;
-        const float *in = (target ? b.next_spatial : b.spatial) + s * b.sp_stride[0] + agent * b.sp_stride[1] + step * b.sp_stride[2];
-        float *xrow = (target ? ws.Xt : ws.X) + (size_t)img * net.R;
-        for (int l = 0; l < net.n_conv; l++) {
-            float *out = l == net.n_conv - 1 ? xrow : (target ? slice + (l & 1) * net.maxsz : ws.act + (size_t)img * net.asz + net.aoff[l]);
-            const int si = net.size[l], so = net.size[l + 1], ci_n = net.ch[l], k = net.k, str = net.stride[l], pad = net.pad[l], dil = net.dil[l];
-            const float *W = P + net.oCW[l], *B = P + net.oCB[l];
-            for (int e = tid; e < net.sz[l + 1]; e += kStConvThreads) {
-                const int co = e / (so * so), oy = (e / so) % so, ox = e % so;
-                float acc = B[co];
-                for (int ci = 0; ci < ci_n; ci++)
-                    for (int ky = 0; ky < k; ky++) {
-                        const int iy = oy * str - pad + ky * dil;
-                        if (iy < 0 || iy >= si) continue;
-                        for (int kx = 0; kx < k; kx++) {
-                            const int ix = ox * str - pad + kx * dil;
-                            if (ix < 0 || ix >= si) continue;
-                            acc = fmaf(W[((co * ci_n + ci) * k + ky) * k + kx], in[(ci * si + iy) * si + ix], acc);
-                        }
-                    }
-                out[e] = acc > 0.0f ? acc : 0.0f;
-            }
-            __syncthreads();
-            in = out;
-        }
-        if (net.Fn > 0) {
-            const float *ns = (target ? b.next_non_spatial : b.non_spatial) + s * b.ns_stride[0] + agent * b.ns_stride[1] + step * b.ns_stride[2];
-            for (int f = tid; f < net.Fn; f += kStConvThreads) xrow[net.Rc + f] = ns[f];
-        }
-    }
+#include "susnet_spatial_train_conv_body.h"
 }
 
 // one step of the recurrence on a tile: h[l][t] = tanh(b_ih + b_hh + W_ih in + W_hh h[l][t-1]), in = the RNN input rows X (l = 0; a column
@@ -192,80 +150,106 @@ __global__ __launch_bounds__(kTrThreads) void k_sp_train_rnn_dropout(SpTrainBatc
 __global__ __launch_bounds__(kStConvThreads) void k_sp_train_conv_bwd(SpTrainBatch b, const SpTrainNet *__restrict__ netp, SpTrainWs ws, const float *__restrict__ prm,
                                                                       const int32_t *__restrict__ lists, const int32_t *__restrict__ counts, int agent,
                                                                       int team, float *__restrict__ partial) {
-    const int tid = threadIdx.x;
-    const int count = counts[2 * agent + team];
-    if (count == 0) return;
-    const SpTrainNet &net = *netp;
-    const int32_t *list = lists + ((int64_t)agent * 2 + team) * b.n;
-    const int64_t nimg = (int64_t)count * net.T;
-    float *out = partial + (size_t)blockIdx.x * net.Pp;
-    const int k = net.k, last = net.n_conv - 1;
-    // through the ReLUs and the transposed convolutions, top down; the gated gradient of every layer's output stays in the workspace
-    for (int64_t img = blockIdx.x; img < nimg; img += gridDim.x) {
-        for (int l = last; l >= 0; l--) {
-            const float *y = l == last ? ws.X + (size_t)img * net.R : ws.act + (size_t)img * net.asz + net.aoff[l];
-            float *d = l == last ? ws.dX + (size_t)img * net.Rc : ws.dact + (size_t)img * net.asz + net.aoff[l];
-            for (int e = tid; e < net.sz[l + 1]; e += kStConvThreads) d[e] = y[e] > 0.0f ? d[e] : 0.0f; // relu'(0) = 0, as torch
-            __syncthreads();
-            if (l > 0) {
-                float *din = ws.dact + (size_t)img * net.asz + net.aoff[l > 0 ? l - 1 : 0];
-                const int si = net.size[l], so = net.size[l + 1], ci_n = net.ch[l], co_n = net.ch[l + 1], str = net.stride[l], pad = net.pad[l],
-                          dil = net.dil[l];
-                const float *W = prm + net.oCW[l];
-                for (int e = tid; e < net.sz[l]; e += kStConvThreads) {
-                    const int ci = e / (si * si), iy = (e / si) % si, ix = e % si;
-                    float acc = 0.0f;
-                    for (int co = 0; co < co_n; co++)
-                        for (int ky = 0; ky < k; ky++) {
-                            const int ny = iy + pad - ky * dil;
-                            if (ny < 0 || ny % str != 0 || ny / str >= so) continue;
-                            for (int kx = 0; kx < k; kx++) {
-                                const int nx = ix + pad - kx * dil;
-                                if (nx < 0 || nx % str != 0 || nx / str >= so) continue;
-                                acc = fmaf(W[((co * ci_n + ci) * k + ky) * k + kx], d[(co * so + ny / str) * so + nx / str], acc);
-                            }
-                        }
-                    din[e] = acc;
-                }
-                __syncthreads();
-            }
-        }
+#include "susnet_spatial_train_conv_bwd_body.h"
+}
+
+// ---- the sweep forms (susnet_spatial_train.h): learner blockIdx.y of the table; every body is the single learner's text ----
+// what the bodies name as kernel arguments, from the shared record and the learner's own
+__device__ __forceinline__ SpTrainBatch st_sweep_batch(const SpSweepShared &sh, const SpSweepLearner &lrn) {
+    SpTrainBatch b;
+    b.spatial = lrn.spatial, b.next_spatial = lrn.next_spatial, b.non_spatial = lrn.non_spatial, b.next_non_spatial = lrn.next_non_spatial;
+#pragma unroll
+    for (int d = 0; d < 3; d++) b.sp_stride[d] = sh.sp_stride[d], b.ns_stride[d] = sh.ns_stride[d];
+    b.actions = lrn.actions, b.rewards = lrn.rewards, b.dones = lrn.dones, b.imposters = lrn.imposters, b.idx = lrn.idx;
+    b.max_size = lrn.max_size, b.n = sh.n, b.A = sh.A, b.n_imp = sh.n_imp;
+    return b;
+}
+__device__ __forceinline__ SpTrainWs st_sweep_ws(const SpSweepShared &sh, const SpSweepLearner &lrn) {
+    const auto at = [&](uint64_t off) { return reinterpret_cast<float *>(lrn.workspace + off); };
+    return SpTrainWs{at(sh.off_X), at(sh.off_Xt), at(sh.off_act), at(sh.off_dact), at(sh.off_dX), at(sh.off_tact), at(sh.off_hs), at(sh.off_ds), at(sh.off_zs)};
+}
+// `first`: the table index of a.l[0]; the launch with first == 0 also writes the shared record.  A workgroup reads its learner from the
+// ARGUMENTS (nothing another workgroup of this launch writes), the later launches read the table
+__global__ __launch_bounds__(kTrThreads) void k_sp_train_sweep_select(SpSweepShared sh, SpSweepSelArgs a, int first, SpSweepTable *table) {
+    extern __shared__ int32_t st_scan[];
+    const SpSweepLearner &lrn = a.l[blockIdx.y];
+    if (threadIdx.x == 0) {
+        if (first == 0 && blockIdx.y == 0) table->sh = sh;
+        table->l[first + blockIdx.y] = lrn;
     }
-    // weight and bias gradients: a thread per parameter, images then pixels in ascending order, stored once
-    for (int l = 0; l <= last; l++) {
-        const int si = net.size[l], so = net.size[l + 1], ci_n = net.ch[l], co_n = net.ch[l + 1], str = net.stride[l], pad = net.pad[l], dil = net.dil[l];
-        const int nW = co_n * ci_n * k * k;
-        for (int w = tid; w < nW + co_n; w += kStConvThreads) {
-            const bool bias = w >= nW;
-            const int co = bias ? w - nW : w / (ci_n * k * k), ci = bias ? 0 : (w / (k * k)) % ci_n, ky = bias ? 0 : (w / k) % k, kx = bias ? 0 : w % k;
-            float acc = 0.0f;
-            for (int64_t img = blockIdx.x; img < nimg; img += gridDim.x) {
-                const float *d = (l == last ? ws.dX + (size_t)img * net.Rc : ws.dact + (size_t)img * net.asz + net.aoff[l]) + (size_t)co * so * so;
-                if (bias) {
-                    for (int e = 0; e < so * so; e++) acc += d[e];
-                    continue;
-                }
-                const float *in;
-                if (l == 0) {
-                    const int64_t s = st_clamp(list[img / net.T], b.n);
-                    in = b.spatial + s * b.sp_stride[0] + agent * b.sp_stride[1] + (img % net.T) * b.sp_stride[2];
-                } else {
-                    in = ws.act + (size_t)img * net.asz + net.aoff[l > 0 ? l - 1 : 0];
-                }
-                in += (size_t)ci * si * si;
-                for (int oy = 0; oy < so; oy++) {
-                    const int iy = oy * str - pad + ky * dil;
-                    if (iy < 0 || iy >= si) continue;
-                    for (int ox = 0; ox < so; ox++) {
-                        const int ix = ox * str - pad + kx * dil;
-                        if (ix < 0 || ix >= si) continue;
-                        acc = fmaf(d[oy * so + ox], in[iy * si + ix], acc);
-                    }
-                }
-            }
-            out[bias ? net.oCB[l] + co : net.oCW[l] + w] = acc;
-        }
+    const SpTrainBatch b = st_sweep_batch(sh, lrn);
+    tr_select<true>(b, b.idx, b.n, reinterpret_cast<int32_t *>(lrn.workspace + sh.off_lists), reinterpret_cast<int32_t *>(lrn.workspace + sh.off_counts),
+                    reinterpret_cast<float *>(lrn.workspace + sh.off_gacc[0]), sh.net[0].P, reinterpret_cast<float *>(lrn.workspace + sh.off_gacc[1]),
+                    sh.net[1].P, lrn.losses, st_scan);
+}
+// the arguments of the single learner's kernels, as locals of the same names
+#define SP_SWEEP_ARGS                                                                                                        \
+    const SpSweepShared &sh = table->sh;                                                                                     \
+    const SpSweepLearner &lrn = table->l[blockIdx.y];                                                                        \
+    const SpTrainBatch b = st_sweep_batch(sh, lrn);                                                                          \
+    const SpTrainNet *__restrict__ netp = &sh.net[team];                                                                     \
+    const SpTrainWs ws = st_sweep_ws(sh, lrn);                                                                               \
+    const float *__restrict__ prm = lrn.prm[team];                                                                           \
+    [[maybe_unused]] const float *__restrict__ tgt = lrn.tgt[team];                                                          \
+    const int32_t *__restrict__ lists = reinterpret_cast<const int32_t *>(lrn.workspace + sh.off_lists);                     \
+    const int32_t *__restrict__ counts = reinterpret_cast<const int32_t *>(lrn.workspace + sh.off_counts);                   \
+    [[maybe_unused]] float *__restrict__ partial = reinterpret_cast<float *>(lrn.workspace + sh.off_partial);
+#define SP_SWEEP_RNN_ARGS                                                                                                    \
+    SP_SWEEP_ARGS                                                                                                            \
+    const float gamma = lrn.gamma;                                                                                           \
+    float *step = lrn.step[team];
+
+__global__ __launch_bounds__(kStConvThreads) void k_sp_train_sweep_conv(const SpSweepTable *__restrict__ table, int agent, int team) {
+    SP_SWEEP_ARGS
+#include "susnet_spatial_train_conv_body.h"
+}
+__global__ __launch_bounds__(kTrThreads) void k_sp_train_sweep_rnn(const SpSweepTable *__restrict__ table, int agent, int team) {
+    SP_SWEEP_RNN_ARGS
+#define SP_TRAIN_DROPOUT 0
+#include "susnet_spatial_train_rnn_body.h"
+#undef SP_TRAIN_DROPOUT
+}
+__global__ __launch_bounds__(kTrThreads) void k_sp_train_sweep_rnn_dropout(const SpSweepTable *__restrict__ table, int agent, int team) {
+    SP_SWEEP_RNN_ARGS
+    const SpDropArgs &da = lrn.dr[team];
+    const SpDrop dr{da.k0, da.k1, da.off_lo, da.off_hi, {da.thr[0], da.thr[1]}, {da.scale[0], da.scale[1]}, da.row_base, agent};
+    float *ms = reinterpret_cast<float *>(lrn.workspace + sh.off_ms);
+#define SP_TRAIN_DROPOUT 1
+#include "susnet_spatial_train_rnn_body.h"
+#undef SP_TRAIN_DROPOUT
+}
+__global__ __launch_bounds__(kStConvThreads) void k_sp_train_sweep_conv_bwd(const SpSweepTable *__restrict__ table, int agent, int team) {
+    SP_SWEEP_ARGS
+#include "susnet_spatial_train_conv_bwd_body.h"
+}
+#undef SP_SWEEP_RNN_ARGS
+#undef SP_SWEEP_ARGS
+
+hipError_t sp_train_sweep_select_launch(const SpSweepShared &sh, const SpSweepLearner *l, int K, SpSweepTable *table, hipStream_t st) {
+    for (int first = 0; first < K; first += kSpSweepSelLearners) {
+        const int count = K - first < kSpSweepSelLearners ? K - first : kSpSweepSelLearners;
+        SpSweepSelArgs a{};
+        for (int k = 0; k < count; k++) a.l[k] = l[first + k];
+        hipLaunchKernelGGL(k_sp_train_sweep_select, dim3(1, (unsigned)count), dim3(kTrThreads), kTrThreads * 4, st, sh, a, first, table);
+        if (hipError_t e = hipGetLastError()) return e;
     }
+    return hipSuccess;
+}
+
+hipError_t sp_train_sweep_update_launch(const SpSweepTable *table, int K, int agent, int team, int G, int Gconv, bool dropout, hipStream_t st) {
+    // the recurrence kernels' dynamic-LDS ceilings, as sp_train_update_launch sets its kernels'
+    static LdsOptIn opted, opted_drop;
+    if (hipError_t e = dropout ? lds_opt_in(reinterpret_cast<const void *>(&k_sp_train_sweep_rnn_dropout), kStLdsBytes, opted_drop)
+                               : lds_opt_in(reinterpret_cast<const void *>(&k_sp_train_sweep_rnn), kStLdsBytes, opted))
+        return e;
+    const unsigned Ku = (unsigned)K;
+    hipLaunchKernelGGL(k_sp_train_sweep_conv, dim3((unsigned)Gconv, Ku), dim3(kStConvThreads), 0, st, table, agent, team);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (dropout) hipLaunchKernelGGL(k_sp_train_sweep_rnn_dropout, dim3((unsigned)G, Ku), dim3(kTrThreads), kStLdsBytes, st, table, agent, team);
+    else hipLaunchKernelGGL(k_sp_train_sweep_rnn, dim3((unsigned)G, Ku), dim3(kTrThreads), kStLdsBytes, st, table, agent, team);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(k_sp_train_sweep_conv_bwd, dim3((unsigned)G, Ku), dim3(kStConvThreads), 0, st, table, agent, team);
+    return hipGetLastError();
 }
 
 hipError_t sp_train_select_launch(const SpTrainBatch &b, const SpTrainNet &net0, const SpTrainNet &net1, SpTrainNet *nets, int32_t *lists,

@@ -1,10 +1,13 @@
 // susnet_capi_train.hip -- the DQN learners of the C ABI: susnet_dqn_train_step and susnet_dqn_train_sweep (the fused learner on the
 // compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step (the dense learner on any served stack;
-// its gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step (the SpatialDQN learner; its kernels: inst_spatial_train.hip).  All
+// its gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step / susnet_spatial_train_sweep (the SpatialDQN learner and its sweep
+// form; their kernels: inst_spatial_train.hip).  All
 // carve their workspace with tr_buffers and the single learners end every update with launch_adam (this unit's k_train_adam); the dense and
 // the SpatialDQN learner share their handle, Adam-constant, pointer and workspace checks (check_*, below).
 #include <algorithm>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "susnet_qnet.h" // QNet, QRow1 / QRow3 / QRowC: the pack kernels write susnet_qnet_pack's image
 #include "susnet_dense.h" // kDnMaxHidden / kDnMaxOut: the forward's widths, which the dense learner's must equal
@@ -492,16 +495,20 @@ extern "C" int susnet_spatial_train_dropout_workspace_bytes(const susnet_env *en
     return SUSNET_OK;
 }
 
-// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only.
-// `drop` (susnet_spatial_train_step_dropout): two structs, [0] imposters, [1] crew; a team with a mask (a p > 0 and more than one RNN layer)
-// takes k_sp_train_rnn_dropout, any other the plain kernel
-static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream) {
-    const char *entry = drop ? "susnet_spatial_train_step_dropout" : "susnet_spatial_train_step";
+// the checks of one call (`entry`: its name), shared with the sweep, which asks them of every learner: the plan, the dropout structs, the
+// workspace and every pointer
+struct SpTrainChecked {
     SpTrainPlan pl;
-    if (int rc = sp_train_plan(env, io, pl, drop != nullptr, entry)) return rc;
-    const Refuse bad{env, entry};
     SpDrop dr[2] = {};
     bool masked[2] = {false, false};
+    int Fn = 0;
+};
+static int sp_train_check(const susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, const char *entry, SpTrainChecked &c) {
+    SpTrainPlan &pl = c.pl;
+    if (int rc = sp_train_plan(env, io, pl, drop != nullptr, entry)) return rc;
+    const Refuse bad{env, entry};
+    SpDrop(&dr)[2] = c.dr;
+    bool(&masked)[2] = c.masked;
     for (int tm = 0; drop && tm < 2; tm++) {
         if (!io->team[tm].enabled) continue;
         if (int rc = drop_check(bad, "drop[" + std::to_string(tm) + "].", drop[tm], io->n, dr[tm])) return rc;
@@ -512,7 +519,7 @@ static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io
         return rc;
     if (int rc = check_ring_ptrs(bad, *io)) return rc;
     const bool any = io->team[0].enabled || io->team[1].enabled;
-    const int Fn = io->team[0].enabled ? io->net[0].Fn : io->team[1].enabled ? io->net[1].Fn : 0;
+    const int Fn = c.Fn = io->team[0].enabled ? io->net[0].Fn : io->team[1].enabled ? io->net[1].Fn : 0;
     if (io->n > 0 && any) {
         if (!io->spatial || misaligned(io->spatial)) return bad("spatial is NULL or not 4-byte aligned");
         if (!io->next_spatial || misaligned(io->next_spatial)) return bad("next_spatial is NULL or not 4-byte aligned");
@@ -520,7 +527,18 @@ static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io
         if ((!io->non_spatial && Fn > 0) || misaligned(io->non_spatial)) return bad("non_spatial is NULL or not 4-byte aligned");
         if ((!io->next_non_spatial && Fn > 0) || misaligned(io->next_non_spatial)) return bad("next_non_spatial is NULL or not 4-byte aligned");
     }
-    if (int rc = check_team_ptrs(bad, io->team)) return rc;
+    return check_team_ptrs(bad, io->team);
+}
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only.
+// `drop` (susnet_spatial_train_step_dropout): two structs, [0] imposters, [1] crew; a team with a mask (a p > 0 and more than one RNN layer)
+// takes k_sp_train_rnn_dropout, any other the plain kernel
+static int spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream) {
+    SpTrainChecked c;
+    if (int rc = sp_train_check(env, io, drop, drop ? "susnet_spatial_train_step_dropout" : "susnet_spatial_train_step", c)) return rc;
+    const SpTrainPlan &pl = c.pl;
+    const SpDrop(&dr)[2] = c.dr;
+    const bool(&masked)[2] = c.masked;
+    const int Fn = c.Fn;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(io->workspace);
     const TrBuffers t = tr_buffers(io->workspace, pl);
@@ -550,4 +568,135 @@ extern "C" int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_t
 extern "C" int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream) {
     if (env && io && !drop) return Refuse{env, "susnet_spatial_train_step_dropout"}("drop is NULL");
     return spatial_train_step(env, io, drop, stream);
+}
+
+// ---- a sweep's SpatialDQN train step: K learners in the launches of one (susnet_spatial_train.h, k_sp_train_sweep_*) ----
+static_assert(kSpSweepMaxLearners <= kTrMaxLearners, "the reduce + Adam launch is k_train_sweep_adam: its table carries the learners");
+
+extern "C" int susnet_spatial_train_sweep_table_bytes(int32_t n_learners, uint64_t *bytes_out) {
+    if (n_learners < 1 || n_learners > SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)
+        return fail(SUSNET_E_INVALID, "susnet_spatial_train_sweep_table_bytes: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
+                                          std::to_string(SUSNET_SPATIAL_SWEEP_MAX_LEARNERS));
+    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_sweep_table_bytes: null bytes_out");
+    *bytes_out = sp_sweep_table_bytes(n_learners);
+    return SUSNET_OK;
+}
+
+// the first field of what shapes the step in which learner k's io differs from learner 0's, or an empty string
+static std::string sp_sweep_mismatch(const susnet_env *e0, const susnet_spatial_train_io &i0, const SpTrainChecked &c0, const susnet_env *e,
+                                     const susnet_spatial_train_io &io, const SpTrainChecked &c, bool drops) {
+    const auto S = [](int v) { return std::to_string(v); };
+    if (e->c.A != e0->c.A || e->c.n_imp != e0->c.n_imp) return "agent count";
+    if (io.n != i0.n) return "n";
+    for (int tm = 0; tm < 2; tm++)
+        if ((io.team[tm].enabled != 0) != (i0.team[tm].enabled != 0)) return "team[" + S(tm) + "].enabled";
+    for (int tm = 0; tm < 2; tm++) {
+        if (!i0.team[tm].enabled) continue;
+        const susnet_spatial_net &a = i0.net[tm], &b = io.net[tm];
+        const std::string net = "net[" + S(tm) + "].", team = "team[" + S(tm) + "].";
+        const std::pair<const char *, bool> scalars[] = {{"T", a.T != b.T}, {"N", a.N != b.N}, {"C", a.C != b.C}, {"Fn", a.Fn != b.Fn},
+                                                         {"n_conv", a.n_conv != b.n_conv}, {"k", a.k != b.k}};
+        for (const auto &f : scalars)
+            if (f.second) return net + f.first;
+        for (int l = 0; l < a.n_conv; l++) {
+            const std::string at = "[" + S(l) + "]";
+            if (a.conv_out[l] != b.conv_out[l]) return net + "conv_out" + at;
+            if (a.conv_stride[l] != b.conv_stride[l]) return net + "conv_stride" + at;
+            if (a.conv_padding[l] != b.conv_padding[l]) return net + "conv_padding" + at;
+            if (a.conv_dilation[l] != b.conv_dilation[l]) return net + "conv_dilation" + at;
+        }
+        if (a.rnn_layers != b.rnn_layers) return net + "rnn_layers";
+        if (a.rnn_hidden != b.rnn_hidden) return net + "rnn_hidden";
+        if (io.team[tm].n_dims != i0.team[tm].n_dims) return team + "n_dims";
+        if (memcmp(io.team[tm].dims, i0.team[tm].dims, sizeof(int32_t) * (size_t)i0.team[tm].n_dims) != 0) return team + "dims";
+    }
+    for (int d = 0; d < 3; d++)
+        if (io.spatial_stride[d] != i0.spatial_stride[d]) return "spatial_stride[" + S(d) + "]";
+    for (int d = 0; d < 3 && c0.Fn > 0; d++)
+        if (io.non_spatial_stride[d] != i0.non_spatial_stride[d]) return "non_spatial_stride[" + S(d) + "]";
+    for (int tm = 0; tm < 2 && drops; tm++)
+        if (c.masked[tm] != c0.masked[tm]) return "drops: whether team[" + S(tm) + "] is masked (a p > 0 with more than one RNN layer)";
+    return "";
+}
+
+extern "C" int susnet_spatial_train_sweep(susnet_env *const *envs, const susnet_spatial_train_io *ios, const susnet_rnn_dropout *drops, int32_t n_learners,
+                                          void *table, uint64_t table_bytes, void *stream) {
+    const std::string entry = "susnet_spatial_train_sweep: ";
+    if (!envs || !ios) return fail(SUSNET_E_INVALID, entry + "null envs / ios");
+    if (n_learners < 1 || n_learners > SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)
+        return fail(SUSNET_E_INVALID, entry + "n_learners " + std::to_string(n_learners) + " outside 1 .. " + std::to_string(SUSNET_SPATIAL_SWEEP_MAX_LEARNERS));
+    const int K = n_learners;
+    const auto who = [&](int k, const std::string &what) { return entry + "learner " + std::to_string(k) + ": " + what; };
+    std::vector<SpTrainChecked> cs((size_t)K);
+    for (int k = 0; k < K; k++) { // each learner passes its own call's checks ...
+        if (!envs[k]) return fail(SUSNET_E_INVALID, who(k, "null handle"));
+        if (int rc = sp_train_check(envs[k], &ios[k], drops ? drops + 2 * k : nullptr, drops ? "susnet_spatial_train_step_dropout" : "susnet_spatial_train_step",
+                                    cs[(size_t)k]))
+            return fail(rc, who(k, g_err));
+    }
+    for (int k = 1; k < K; k++) { // ... and all agree on what shapes the step
+        const std::string field = sp_sweep_mismatch(envs[0], ios[0], cs[0], envs[k], ios[k], cs[(size_t)k], drops != nullptr);
+        if (!field.empty()) return fail(SUSNET_E_INVALID, who(k, field + " differs from learner 0's (a sweep runs learners of one shape)"));
+        if (cs[(size_t)k].pl.bytes != cs[0].pl.bytes || cs[(size_t)k].pl.G != cs[0].pl.G || cs[(size_t)k].pl.Gconv != cs[0].pl.Gconv)
+            return fail(SUSNET_E_INVALID, who(k, "workspace plan differs from learner 0's"));
+    }
+    for (int k = 1; k < K; k++) // no two learners write the same memory
+        for (int j = 0; j < k; j++) {
+            const char *field = nullptr;
+            if (ios[k].workspace == ios[j].workspace) field = "workspace";
+            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
+            for (int a = 0; a < 2 && !field; a++)
+                for (int b = 0; b < 2 && !field; b++)
+                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
+                        field = a ? "team[1].params" : "team[0].params";
+            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
+        }
+    const uint64_t need = sp_sweep_table_bytes(K);
+    if (!table || table_bytes < need || (reinterpret_cast<uintptr_t>(table) & 255u))
+        return fail(SUSNET_E_INVALID, entry + "table missing, smaller than susnet_spatial_train_sweep_table_bytes (" + std::to_string((unsigned long long)need) +
+                                          " bytes) or not 256-byte aligned");
+    // what the learners share, and each one's own
+    const SpTrainPlan &pl = cs[0].pl;
+    const susnet_spatial_train_io &i0 = ios[0];
+    SpSweepShared sh{};
+    sh.net[0] = pl.net[0], sh.net[1] = pl.net[1];
+    for (int d = 0; d < 3; d++) sh.sp_stride[d] = i0.spatial_stride[d], sh.ns_stride[d] = cs[0].Fn > 0 ? i0.non_spatial_stride[d] : 0;
+    sh.n = i0.n, sh.A = (int32_t)envs[0]->c.A, sh.n_imp = (int32_t)envs[0]->c.n_imp;
+    sh.off_lists = pl.off_lists, sh.off_counts = pl.off_counts, sh.off_gacc[0] = pl.off_gacc[0], sh.off_gacc[1] = pl.off_gacc[1], sh.off_partial = pl.off_partial;
+    sh.off_X = pl.off_X, sh.off_Xt = pl.off_Xt, sh.off_act = pl.off_act, sh.off_dact = pl.off_dact, sh.off_dX = pl.off_dX, sh.off_tact = pl.off_tact;
+    sh.off_hs = pl.off_hs, sh.off_ds = pl.off_ds, sh.off_zs = pl.off_zs, sh.off_ms = pl.off_ms;
+    SpSweepLearner learners[kSpSweepMaxLearners] = {};
+    TrainTable tab[2] = {};
+    TrainNet anet[2] = {};
+    for (int tm = 0; tm < 2; tm++) anet[tm].P = pl.net[tm].P, anet[tm].Pp = pl.net[tm].Pp;
+    for (int k = 0; k < K; k++) {
+        const susnet_spatial_train_io &io = ios[k];
+        const TrBuffers b = tr_buffers(io.workspace, pl);
+        SpSweepLearner &l = learners[k];
+        l.spatial = io.spatial, l.next_spatial = io.next_spatial, l.non_spatial = io.non_spatial, l.next_non_spatial = io.next_non_spatial;
+        l.actions = io.actions, l.rewards = io.rewards, l.dones = io.dones, l.imposters = io.imposters, l.idx = io.indices;
+        l.max_size = io.max_size, l.workspace = static_cast<char *>(io.workspace), l.losses = io.losses_out, l.gamma = (float)io.gamma;
+        for (int tm = 0; tm < 2; tm++) {
+            const susnet_dqn_team &T = io.team[tm];
+            if (!T.enabled) continue;
+            l.prm[tm] = T.params, l.tgt[tm] = T.target_params, l.step[tm] = T.step;
+            const SpDrop &d = cs[(size_t)k].dr[tm];
+            l.dr[tm] = SpDropArgs{d.k0, d.k1, d.off_lo, d.off_hi, {d.thr[0], d.thr[1]}, {d.scale[0], d.scale[1]}, d.row_base};
+            tab[tm].l[k] = TrainLearner{TrainRing{}, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, b.lists, b.counts, b.gacc[tm], b.partial,
+                                        io.losses_out, nullptr, T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
+        }
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SpSweepTable *dtab = static_cast<SpSweepTable *>(table);
+    HIP_TRY(sp_train_sweep_select_launch(sh, learners, K, dtab, st));
+    if (i0.n == 0) return SUSNET_OK;
+    const unsigned Ku = (unsigned)K;
+    for (int agent = 0; agent < envs[0]->c.A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            if (!i0.team[tm].enabled) continue;
+            HIP_TRY(sp_train_sweep_update_launch(dtab, K, agent, tm, (int)pl.G, (int)pl.Gconv, cs[0].masked[tm], st));
+            hipLaunchKernelGGL(k_train_sweep_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256), Ku), dim3(256), 0, st, tab[tm], anet[tm], agent, tm, (int)pl.G);
+            HIP_TRY(hipGetLastError());
+        }
+    return SUSNET_OK;
 }

@@ -83,6 +83,64 @@ struct SpTrainWs {
     float *zs;           // [G][head.Z]
 };
 
+// ---- a sweep (susnet_spatial_train_sweep): K learners of one shape in the launches of one, the learner is blockIdx.y ----
+// k_sp_train_sweep_select / _conv / _rnn / _rnn_dropout / _conv_bwd are the kernels above with the SAME body text (the select kernel calls
+// the same tr_select; the others include the same susnet_spatial_train_*_body.h), so workgroup (g, k) does what workgroup g of learner k's
+// own call does -- same tiles and images, same order of every sum, same partial slot -- and a learner's results are bitwise those of
+// susnet_spatial_train_step / _dropout.  What a body names as a kernel argument, the sweep form builds from the learner's table entry.
+// The table lives in DEVICE memory (a learner's record is about 250 bytes: 16 of them and the two networks do not fit a 4 KB argument
+// block): [SpSweepShared][SpSweepLearner x K], caller-supplied, written by the select launches from their kernel arguments (no copy from
+// the host: the call stays capturable) -- kSpSweepSelLearners learners per launch, so 1 launch up to 8 learners and 2 beyond -- and read
+// through a pointer by the update's kernels, which run behind them on the same stream.  What the learners agree on is kept once
+// (SpSweepShared): the two networks, the strides, n, the agent count and the plan's workspace offsets.  The reduce + Adam launch is
+// susnet_train.h's k_train_sweep_adam as it is: its table (pointers, Adam constants) and its net (P, Pp) describe a spatial learner.
+constexpr int kSpSweepMaxLearners = SUSNET_SPATIAL_SWEEP_MAX_LEARNERS;
+constexpr int kSpSweepSelLearners = 8; // learners one select launch carries in its arguments
+
+struct SpDropArgs { // SpDrop (susnet_dropout.h) without its agent, which the update supplies
+    uint32_t k0, k1, off_lo, off_hi, thr[2];
+    float scale[2];
+    int64_t row_base;
+};
+struct SpSweepShared { // what all learners of a sweep agree on
+    SpTrainNet net[2];
+    int64_t sp_stride[3], ns_stride[3], n;
+    int32_t A, n_imp;
+    uint64_t off_lists, off_counts, off_gacc[2], off_partial; // TrWorkspace
+    uint64_t off_X, off_Xt, off_act, off_dact, off_dX, off_tact, off_hs, off_ds, off_zs, off_ms; // SpTrainWs, and the multipliers' slices
+};
+struct SpSweepLearner { // one learner's own
+    const float *spatial, *next_spatial, *non_spatial, *next_non_spatial;
+    const int64_t *actions;
+    const float *rewards;
+    const uint8_t *dones;
+    const int16_t *imposters;
+    const int64_t *idx;
+    int64_t max_size;
+    char *workspace;
+    const float *prm[2], *tgt[2];
+    float *step[2];
+    float *losses;
+    float gamma;
+    int32_t pad_;
+    SpDropArgs dr[2];
+};
+struct SpSweepSelArgs {
+    SpSweepLearner l[kSpSweepSelLearners];
+};
+struct SpSweepTable {
+    SpSweepShared sh;
+    SpSweepLearner l[kSpSweepMaxLearners]; // (the first K are written and read)
+};
+static_assert(sizeof(SpSweepShared) + sizeof(SpSweepSelArgs) + 64 <= 4096, "the select launch's arguments: 4 KB");
+static_assert(kSpSweepMaxLearners <= 2 * kSpSweepSelLearners, "at most two select launches");
+inline uint64_t sp_sweep_table_bytes(int K) { return (sizeof(SpSweepShared) + (uint64_t)K * sizeof(SpSweepLearner) + 255) / 256 * 256; }
+
+// the select launches: learners l[0 .. K) into `table` and their batches split (1 launch for K <= kSpSweepSelLearners, else 2)
+hipError_t sp_train_sweep_select_launch(const SpSweepShared &sh, const SpSweepLearner *l, int K, SpSweepTable *table, hipStream_t st);
+// conv, recurrence (the dropout form iff `dropout`) and conv_bwd of one (agent, team) update for the K learners of `table`
+hipError_t sp_train_sweep_update_launch(const SpSweepTable *table, int K, int agent, int team, int G, int Gconv, bool dropout, hipStream_t st);
+
 // (nets: device, two SpTrainNet -- the select kernel writes them, the update's kernels read their team's: `net` below is a DEVICE pointer)
 hipError_t sp_train_select_launch(const SpTrainBatch &b, const SpTrainNet &net0, const SpTrainNet &net1, SpTrainNet *nets, int32_t *lists,
                                   int32_t *counts, float *gacc0, float *gacc1, float *losses, hipStream_t st);

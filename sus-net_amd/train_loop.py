@@ -214,7 +214,8 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
     ``(env, metrics, replay_buffer, policy, trainer, scheduler, save_directory_path, generator)`` per run, each with its own env, ring,
     models and generator.  Per block every member first does what ``train()`` does before the train step -- its saves, its target sync,
     its ``collect`` at its own epsilon, its ``EpisodeLog.update`` -- then ONE ``DeviceDQNSweepTrainer.train_step`` steps all members
-    (``susnet_dqn_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
+    (``susnet_dqn_train_sweep``, or for ``WindowedPolicyRollout(kernels=True)`` members with ``spatial=True`` trainers
+    ``susnet_spatial_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
     ``batch_size``, ``num_saves``, ``target_update_interval``) is shared.  Each member's metrics, losses, checkpoints and ``EpisodeLog``
     (returned, in member order) are what ``train()`` alone produces for it: its step is bitwise its own, and its random streams are
     its own (give every member a generator: without one the draws come from the device's global generator, in member order)."""
@@ -419,7 +420,7 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
               gamma: float = 0.99, scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
               train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
               train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
-              seed: int = 0, dense_train: bool = False) -> List[EpisodicMetricHandler]:
+              seed: int = 0, dense_train: bool = False, featurizer_factory=None) -> List[EpisodicMetricHandler]:
     """The reference's sweeps -- ``for config in configs: run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
     notebooks/experiment_mlp.ipynb: gamma 0.99 / 0.9 / 0.8 on one game and one MLP) -- as ONE run: the members collect one after another
     and take their train steps together (``train_sweep``).  The shared arguments are ``run_experiment``'s.  ``variants``: one dict per
@@ -430,10 +431,29 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     too.  Each member gets ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values),
     the checkpoints and ``metrics.json`` exactly as ``run_experiment`` writes them, so plotting over one directory per gamma keeps
     working.  ``dense_train`` is ``run_experiment``'s: members whose step the sweep call does not serve then take their dense steps one
-    after another.  Returns the members' metric handlers.  MLP-only: ``SpatialDQN`` members (``run_experiment(..., featurizer=...)``) are
-    not swept -- ``susnet_dqn_train_sweep`` steps reference MLPs."""
+    after another.  Returns the members' metric handlers.
+
+    ``featurizer_factory(env)`` (opt-in; None: everything above -- that form is MLP-only as it was, a ``SpatialDQN`` is a ``ValueError``
+    there) returning a ``GlobalFeaturizer`` /
+    ``PerspectiveFeaturizer`` over the member's env sweeps ``SpatialDQN`` members -- the reference's default model -- built as
+    ``run_experiment(..., featurizer=...)`` builds a run: ``env_factory(seed)`` builds the env ``obs=ObsConfig('raw', torch.uint8),
+    auto_reset=True``, the factories return ``SpatialDQN``s (a crew of None acts randomly), ``components`` is not read, the teams act
+    through ``WindowedPolicyRollout(kernels=True, sequence_length=T)`` in eval mode, the ring has ``trajectory_size = sequence_length``
+    (1 .. ``SPATIAL_MAX_T``) and the trainer is ``DeviceDQNTeamTrainer(featurizer=..., spatial=True)``; the
+    members' train steps are ONE ``susnet_spatial_train_sweep`` call per chunk of ``SPATIAL_SWEEP_MAX_LEARNERS``.  A model the spatial
+    kernels do not serve is a ``ValueError`` with the bound that failed (``spatial_unserved_reason``).  There is no dropout seed here:
+    members with dropout between their RNN layers take ``torch_train_step`` one after another, as such a ``run_experiment`` without
+    ``rnn_dropout_seed`` does (a ``DeviceDQNSweepTrainer`` over trainers built with ``rnn_dropout_seed`` does sweep them).
+    ``config.json`` records as ``train_step`` what the members take:
+    ``susnet_spatial_train_sweep``, or -- where the sweep call does not serve them -- a member's own ``susnet_spatial_train_step`` /
+    ``torch_train_step``."""
     components = list(components)
     variants = check_variants(variants)
+    if featurizer_factory is not None:
+        return _run_spatial_sweep(env_factory, variants, num_steps, imposter_model_factory, crew_model_factory, featurizer_factory, int(sequence_length),
+                                  replay_buffer_size, replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps,
+                                  scheduler_time_steps, train_imposter, train_crew, experiment_base_dir, learning_rate, train_step_interval,
+                                  num_checkpoint_saves, target_update_interval, seed)
     if sequence_length != 1:
         raise ValueError("run_sweep: a window of one state is served (sequence_length=1): the Q-network kernel and "
                          "susnet_dqn_train_sweep read one state")
@@ -472,6 +492,72 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
         generator.manual_seed(int(v["seed"]))
         handlers.append(EpisodicMetricHandler())
         members.append((env, handlers[-1], ring, policy, trainer, scheduler, experiment_dir, generator))
+    train_sweep(members, num_steps, train_step_interval=train_step_interval, batch_size=batch_size, num_saves=num_checkpoint_saves,
+                target_update_interval=target_update_interval, per_episode_info=True)
+    for handler, experiment_dir in zip(handlers, dirs):
+        handler.save_metrics(save_file_path=experiment_dir / "metrics.json")
+    return handlers
+
+
+def _run_spatial_sweep(env_factory, variants, num_steps, imposter_model_factory, crew_model_factory, featurizer_factory, T, replay_buffer_size,
+                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter,
+                       train_crew, experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves, target_update_interval,
+                       seed) -> List[EpisodicMetricHandler]:
+    """``run_sweep`` for ``SpatialDQN`` members on a Global / Perspective featurizer (see there): each member is built as
+    ``_run_spatial_experiment`` builds a run."""
+    from .features import GlobalFeaturizer
+
+    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
+    dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+    shared = {"gamma": gamma, "learning_rate": learning_rate, "seed": seed, "scheduler_start_eps": scheduler_start_eps,
+              "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps}
+    members, handlers, configs = [], [], []
+    for k, (variant, experiment_dir) in enumerate(zip(variants, dirs)):
+        v = {**shared, **{key: val for key, val in variant.items() if key != "name"}}
+        env = env_factory(int(v["seed"]))
+        if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
+            raise ValueError("run_sweep: with featurizer_factory, env_factory must build the env with obs=ObsConfig('raw', dtype=torch.uint8), "
+                             "auto_reset=True")
+        featurizer = featurizer_factory(env)
+        torch.manual_seed(int(v["seed"]))
+        imposter_model = imposter_model_factory(env)
+        crew_model = crew_model_factory(env) if crew_model_factory is not None else None
+        for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
+            if team == "crew" and model is None:
+                continue
+            why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
+            if why is not None:
+                raise ValueError(f"run_sweep: variant {k}: the {team} model is not served by the spatial kernels: {why}")
+        if crew_model is None and env.rng_kind != "philox":
+            raise ValueError("run_sweep: a random crew draws from the production stream: build the env with rng='philox'")
+        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
+        trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, [], lr=v["learning_rate"], gamma=v["gamma"], train_imposter=train_imposter,
+                                       train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True)
+        config = _experiment_config(env, imposter_model, crew_model, [], base, num_steps=num_steps, sequence_length=T,
+                                    replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
+                                    gamma=v["gamma"], scheduler_start_eps=v["scheduler_start_eps"], scheduler_end_eps=v["scheduler_end_eps"],
+                                    scheduler_time_steps=v["scheduler_time_steps"], train_imposter=train_imposter, train_crew=train_crew,
+                                    learning_rate=v["learning_rate"], train_step_interval=train_step_interval,
+                                    target_update_interval=target_update_interval,
+                                    featurizer_type="global" if isinstance(featurizer, GlobalFeaturizer) else "perspective")
+        config["seed"], config["rnn_dropout_seed"] = v["seed"], None
+        scheduler = ExponentialSchedule(v["scheduler_start_eps"], v["scheduler_end_eps"], v["scheduler_time_steps"])
+        ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
+        generator = torch.Generator(device=env.device)
+        generator.manual_seed(int(v["seed"]))
+        handlers.append(EpisodicMetricHandler())
+        configs.append(config)
+        members.append((env, handlers[-1], ring, policy, trainer, scheduler, experiment_dir, generator))
+    # which learner the members' train steps take: the sweep call where it serves all training members, else each member's own
+    training = [m for m in members if any(m[4].trained)]
+    swept = bool(training) and DeviceDQNSweepTrainer([m[4] for m in training]).uses_spatial([m[2] for m in training])
+    for (env, _, ring, _, trainer, _, experiment_dir, _), config in zip(members, configs):
+        own = "susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step"
+        config["train_step"] = ("susnet_spatial_train_sweep" if swept else own) if any(trainer.trained) else None
+        experiment_dir.mkdir(parents=True, exist_ok=True)
+        (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
+        if replay_prepopulate_steps > 0:
+            ring.populate_fused(env, replay_prepopulate_steps)
     train_sweep(members, num_steps, train_step_interval=train_step_interval, batch_size=batch_size, num_saves=num_checkpoint_saves,
                 target_update_interval=target_update_interval, per_episode_info=True)
     for handler, experiment_dir in zip(handlers, dirs):

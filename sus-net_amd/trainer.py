@@ -399,10 +399,12 @@ class DeviceDQNTeamTrainer:
             self.policy.refresh_weights(force=True)  # (a fused image of these weights: only where the fused step was switched off by hand)
         return self._losses.clone()
 
-    def _spatial_step(self, ring, idx):
-        """Gather the batch's ``[n, T, S]`` windows and next windows and featurize them (two ``policy.SpatialFeed``s: ``n * T`` rows each, the
-        featurizer's kernel, reused buffers), then ``susnet_spatial_train_step`` on the tensors where they lie.  Nothing waits on the host
-        (with ``env.check_errors`` the featurizer's row check is polled)."""
+    def _spatial_prepare(self, ring, idx):
+        """The spatial step up to its launch: gather the batch's ``[n, T, S]`` windows and next windows and featurize them (two
+        ``policy.SpatialFeed``s: ``n * T`` rows each, the featurizer's kernel, reused buffers), fill the ``susnet_spatial_train_io`` (workspace
+        and losses allocated) and the two ``susnet_rnn_dropout`` of the step (None: the plain step).  Returns ``(io, drop)``: what
+        ``_spatial_step`` launches, and what a ``DeviceDQNSweepTrainer`` collects from every member before its one launch.  Nothing waits
+        on the host (with ``env.check_errors`` the featurizer's row check is polled)."""
         env, n, T, A = self.env, int(idx.numel()), ring.trajectory_size, self.env.n_agents
         for t in range(2):
             self._state_to_flat(t)
@@ -434,6 +436,14 @@ class DeviceDQNTeamTrainer:
                     env.poll_errors()
                 feed.finish()
                 next_feed.finish()
+        return io, drop
+
+    def _spatial_step(self, ring, idx):
+        """``_spatial_prepare``, then ``susnet_spatial_train_step`` (with dropout structs: ``susnet_spatial_train_step_dropout``) on the
+        tensors where they lie."""
+        env = self.env
+        io, drop = self._spatial_prepare(ring, idx)
+        with torch.cuda.device(self.device):
             if drop is None:
                 L.check(env.lib.susnet_spatial_train_step(env._h, C.byref(io), env._stream()))
             else:
@@ -550,13 +560,18 @@ def sweep_chunks(n_members: int, limit: int = L.DQN_MAX_LEARNERS):
 
 class DeviceDQNSweepTrainer:
     """The train steps of a sweep -- the reference's loops over ``run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
-    notebooks/experiment_mlp.ipynb: one game, one MLP shape, gamma 0.99 / 0.9 / 0.8) -- taken in lockstep: ``trainers`` are independent
+    notebooks/experiment_mlp.ipynb: one game, one model shape, gamma 0.99 / 0.9 / 0.8) -- taken in lockstep: ``trainers`` are independent
     ``DeviceDQNTeamTrainer`` objects, each over its own env, models and policy, and one ``train_step`` steps every one of them.
 
     When every member is served by the HIP path and the members have one shape (``compatible()``), the step is ONE
     ``susnet_dqn_train_sweep`` call per chunk of at most 16 members: the launches of one learner's step with the learner as the grid's
-    second dimension, each member's result bitwise what its own ``train_step_on_indices`` leaves.  Otherwise the members' own
-    ``train_step_on_indices`` run one after another (the torch path for CPU tensors, ``SpatialDQN`` and anything else unserved)."""
+    second dimension, each member's result bitwise what its own ``train_step_on_indices`` leaves.  When every member takes the spatial
+    step (``DeviceDQNTeamTrainer(spatial=True)`` over served ``SpatialDQN``s: ``uses_spatial``) on windows of one length, the members
+    have one shape and the index counts agree, every member prepares its own batch (gather, featurize: ``_spatial_prepare``) and the step
+    is ONE ``susnet_spatial_train_sweep`` call per chunk of at most ``SPATIAL_SWEEP_MAX_LEARNERS`` members, again bitwise each member's
+    own step, dropout masks included (a member's ``dropout_steps`` advances as its own steps would advance it).  The trainer owns the
+    call's table buffer and the ``[K, 2]`` losses.  Otherwise the members' own ``train_step_on_indices`` run one after another (the
+    torch path for CPU tensors and anything else unserved)."""
 
     def __init__(self, trainers: Sequence[DeviceDQNTeamTrainer]):
         self.trainers = list(trainers)
@@ -565,25 +580,48 @@ class DeviceDQNSweepTrainer:
         if len(set(id(t) for t in self.trainers)) != len(self.trainers):
             raise ValueError("a trainer appears twice in the sweep: two learners would update the same parameters")
         self._losses = None
+        self._table = None  # susnet_spatial_train_sweep's device table
 
     def __len__(self):
         return len(self.trainers)
 
+    @staticmethod
+    def _spatial_shape(t: DeviceDQNTeamTrainer):
+        """What ``susnet_spatial_train_sweep`` requires its learners to agree on beyond the env, of a ``spatial=True`` trainer: the
+        featurizer's layout, each trained team's network (the dropout probability itself may differ) and whether the team is masked (a
+        p > 0 between several RNN layers, with a dropout seed), and whether the step passes dropout structs at all.  None otherwise."""
+        if not t.spatial:
+            return None
+        nets = [None if not tr or d is None else
+                ([d[key] for key in ("N", "C", "Fn", "k", "convs", "layers", "hidden", "dims")],
+                 t.rnn_dropout_seed is not None and d["p"] > 0 and d["layers"] > 1)
+                for d, tr in zip(t._spatial_nets, t.trained)]
+        return t._spatial_featurizer(), nets, t._spatial_dropout() is None
+
     def compatible(self) -> bool:
-        """Whether the members agree on what shapes the step (what ``susnet_dqn_train_sweep`` requires): device, agent and imposter
-        count, raw row size, grid, components, which teams train and their layer dims.  gamma, learning rate and weights may differ."""
+        """Whether the members agree on what shapes the step (what ``susnet_dqn_train_sweep`` and ``susnet_spatial_train_sweep`` require):
+        device, agent and imposter count, raw row size, grid, components, which teams train and their layer dims; of ``spatial=True``
+        members also the featurizer's layout, the networks and which teams are under a dropout mask (``_spatial_shape``).  gamma,
+        learning rate, weights, and the dropout probability and seed may differ."""
         a = self.trainers[0]
         for b in self.trainers[1:]:
             ea, eb = a.env, b.env
             if (b.device != a.device or eb.n_agents != ea.n_agents or eb.n_imposters != ea.n_imposters
                     or eb.flattened_state_size != ea.flattened_state_size or eb.grid.shape != ea.grid.shape or not (eb.grid == ea.grid).all()
-                    or b.components != a.components or b.trained != a.trained or b._dims != a._dims):
+                    or b.components != a.components or b.trained != a.trained or b._dims != a._dims
+                    or self._spatial_shape(b) != self._spatial_shape(a)):
                 return False
         return True
 
     def uses_hip(self, rings) -> bool:
         """Whether a step on ``rings`` (one per member) is served by ``susnet_dqn_train_sweep`` for ALL members (else: the per-member loop)."""
         return len(rings) == len(self.trainers) and all(t.uses_hip(r) for t, r in zip(self.trainers, rings)) and self.compatible()
+
+    def uses_spatial(self, rings) -> bool:
+        """Whether a step on ``rings`` (one per member) is served by ``susnet_spatial_train_sweep`` for ALL members: every member takes
+        the spatial step on its ring, the rings' windows have one length, and the members have one shape (else: the per-member loop)."""
+        return (len(rings) == len(self.trainers) and all(t.uses_spatial(r) for t, r in zip(self.trainers, rings))
+                and len(set(r.trajectory_size for r in rings)) == 1 and self.compatible())
 
     def train_step(self, rings, batch_size: int, generators=None) -> torch.Tensor:
         """Draw each member's ``batch_size`` ring rows with its own generator -- the draw the member's ``train_step`` makes -- and take
@@ -602,7 +640,10 @@ class DeviceDQNSweepTrainer:
         if len(rings) != K or len(idxs) != K:
             raise ValueError(f"a sweep of {K} members needs {K} rings and {K} index tensors")
         idxs = [i.to(r.states.device, torch.int64).contiguous() for r, i in zip(rings, idxs)]
-        if not (self.uses_hip(rings) and len(set(int(i.numel()) for i in idxs)) == 1):
+        same_n = len(set(int(i.numel()) for i in idxs)) == 1
+        if same_n and not self.uses_hip(rings) and self.uses_spatial(rings):
+            return self._spatial_sweep_step(rings, idxs)
+        if not (self.uses_hip(rings) and same_n):
             return torch.stack([t.train_step_on_indices(r, i) for t, r, i in zip(self.trainers, rings, idxs)])
         first = self.trainers[0]
         if self._losses is None or self._losses.shape[0] != K:
@@ -619,6 +660,34 @@ class DeviceDQNSweepTrainer:
                 L.check(first.env.lib.susnet_dqn_train_sweep(envs, ios, n, first.env._stream()))
         for t in self.trainers:
             t._sync_policy_version()
+        return self._losses.clone()
+
+    def _spatial_sweep_step(self, rings, idxs) -> torch.Tensor:
+        """Every member's ``_spatial_prepare``, then one ``susnet_spatial_train_sweep`` per chunk of ``SPATIAL_SWEEP_MAX_LEARNERS``."""
+        K, first = len(self.trainers), self.trainers[0]
+        lib = first.env.lib
+        if self._losses is None or self._losses.shape[0] != K:
+            self._losses = torch.zeros(K, 2, dtype=torch.float32, device=first.device)
+        if self._table is None:
+            nbytes = C.c_uint64()
+            L.check(lib.susnet_spatial_train_sweep_table_bytes(L.SPATIAL_SWEEP_MAX_LEARNERS, C.byref(nbytes)))
+            self._table = torch.empty(int(nbytes.value), dtype=torch.uint8, device=first.device)
+        row_bytes = self._losses.stride(0) * self._losses.element_size()
+        for lo, hi in sweep_chunks(K, L.SPATIAL_SWEEP_MAX_LEARNERS):
+            n = hi - lo
+            ios, envs, drops = (L.SpatialTrainIO * n)(), (C.c_void_p * n)(), None
+            for j, k in enumerate(range(lo, hi)):
+                io, drop = self.trainers[k]._spatial_prepare(rings[k], idxs[k])
+                io.losses_out = self._losses.data_ptr() + k * row_bytes
+                ios[j], envs[j] = io, self.trainers[k].env._h
+                if drop is not None:  # (compatible(): all members pass dropout structs, or none does)
+                    drops = drops if drops is not None else (L.RnnDropout * (2 * n))()
+                    drops[2 * j], drops[2 * j + 1] = drop[0], drop[1]
+            with torch.cuda.device(first.device):
+                L.check(lib.susnet_spatial_train_sweep(envs, ios, drops, n, self._table.data_ptr(), self._table.numel(), first.env._stream()))
+            if drops is not None:
+                for k in range(lo, hi):
+                    self.trainers[k].dropout_steps += 1  # (after the check, as the member's own step: a refused call uses up no offset)
         return self._losses.clone()
 
     @torch.no_grad()
