@@ -81,6 +81,40 @@ static int check_team_ptrs(const Refuse &bad, const susnet_dqn_team (&team)[2]) 
     }
     return SUSNET_OK;
 }
+// what the four *_workspace_bytes entry points (`entry`: the one's name) do around their learner's plan (PLAN: its type; `plan(pl)` fills it)
+template <class PLAN, class FILL>
+static int plan_bytes(const char *entry, uint64_t *bytes_out, const FILL &plan) {
+    PLAN pl;
+    if (int rc = plan(pl)) return rc;
+    if (!bytes_out) return fail(SUSNET_E_INVALID, std::string(entry) + ": null bytes_out");
+    *bytes_out = pl.bytes;
+    return SUSNET_OK;
+}
+// The checks the two sweeps make alike, in the same words: the learner count ...
+static int check_n_learners(const char *entry, int32_t n_learners, int32_t most) {
+    if (n_learners < 1 || n_learners > most)
+        return fail(SUSNET_E_INVALID, std::string(entry) + ": n_learners " + std::to_string(n_learners) + " outside 1 .. " + std::to_string(most));
+    return SUSNET_OK;
+}
+static std::string sweep_learner(const char *entry, int k, const std::string &what) { // (how a sweep names the learner it refuses)
+    return std::string(entry) + ": learner " + std::to_string(k) + ": " + what;
+}
+// ... and that no two learners write the same memory (susnet_dqn_io, susnet_spatial_train_io: the same field names)
+template <class IO>
+static int check_learners_apart(const char *entry, const IO *ios, int K) {
+    for (int k = 1; k < K; k++)
+        for (int j = 0; j < k; j++) {
+            const char *field = nullptr;
+            if (ios[k].workspace == ios[j].workspace) field = "workspace";
+            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
+            for (int a = 0; a < 2 && !field; a++)
+                for (int b = 0; b < 2 && !field; b++)
+                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
+                        field = a ? "team[1].params" : "team[0].params";
+            if (field) return fail(SUSNET_E_INVALID, sweep_learner(entry, k, std::string(field) + " is shared with learner " + std::to_string(j)));
+        }
+    return SUSNET_OK;
+}
 
 // ---- the learner's train step (susnet_train.h) ----
 struct DqnPlan : TrWorkspace {
@@ -126,11 +160,7 @@ static int dqn_plan(const susnet_env *env, const susnet_dqn_io *io, DqnPlan &pl)
 }
 
 extern "C" int susnet_dqn_workspace_bytes(const susnet_env *env, const susnet_dqn_io *io, uint64_t *bytes_out) {
-    DqnPlan pl;
-    if (int rc = dqn_plan(env, io, pl)) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_dqn_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
+    return plan_bytes<DqnPlan>("susnet_dqn_workspace_bytes", bytes_out, [&](DqnPlan &pl) { return dqn_plan(env, io, pl); });
 }
 
 template <class ROW>
@@ -239,11 +269,9 @@ static int dqn_sweep_launch(susnet_env *const *envs, const susnet_dqn_io *ios, i
 
 extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_io *ios, int32_t n_learners, void *stream) {
     if (!envs || !ios) return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: null envs / ios");
-    if (n_learners < 1 || n_learners > SUSNET_DQN_MAX_LEARNERS)
-        return fail(SUSNET_E_INVALID, "susnet_dqn_train_sweep: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
-                                          std::to_string(SUSNET_DQN_MAX_LEARNERS));
+    if (int rc = check_n_learners("susnet_dqn_train_sweep", n_learners, SUSNET_DQN_MAX_LEARNERS)) return rc;
     const int K = n_learners;
-    auto who = [](int k, const std::string &what) { return "susnet_dqn_train_sweep: learner " + std::to_string(k) + ": " + what; };
+    const auto who = [](int k, const std::string &what) { return sweep_learner("susnet_dqn_train_sweep", k, what); };
     DqnPlan pls[SUSNET_DQN_MAX_LEARNERS];
     for (int k = 0; k < K; k++) { // each learner passes susnet_dqn_train_step's checks ...
         int rc = check_bound(envs[k]);
@@ -271,17 +299,7 @@ extern "C" int susnet_dqn_train_sweep(susnet_env *const *envs, const susnet_dqn_
         }
         if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " differs from learner 0's (a sweep runs learners of one shape)"));
     }
-    for (int k = 1; k < K; k++) // no two learners write the same memory
-        for (int j = 0; j < k; j++) {
-            const char *field = nullptr;
-            if (ios[k].workspace == ios[j].workspace) field = "workspace";
-            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
-            for (int a = 0; a < 2 && !field; a++)
-                for (int b = 0; b < 2 && !field; b++)
-                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
-                        field = a ? "team[1].params" : "team[0].params";
-            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
-        }
+    if (int rc = check_learners_apart("susnet_dqn_train_sweep", ios, K)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (pls[0].feat) {
     case FEAT_ONEHOT: return dqn_sweep_launch<QRow1>(envs, ios, K, pls, st);
@@ -336,11 +354,7 @@ static int mlp_train_plan(const susnet_env *env, const susnet_mlp_train_io *io, 
 }
 
 extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out) {
-    MlpTrainPlan pl;
-    if (int rc = mlp_train_plan(env, io, pl)) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_mlp_train_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
+    return plan_bytes<MlpTrainPlan>("susnet_mlp_train_workspace_bytes", bytes_out, [&](MlpTrainPlan &pl) { return mlp_train_plan(env, io, pl); });
 }
 
 // everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
@@ -480,19 +494,11 @@ static int sp_train_plan(const susnet_env *env, const susnet_spatial_train_io *i
 }
 
 extern "C" int susnet_spatial_train_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out) {
-    SpTrainPlan pl;
-    if (int rc = sp_train_plan(env, io, pl)) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
+    return plan_bytes<SpTrainPlan>("susnet_spatial_train_workspace_bytes", bytes_out, [&](SpTrainPlan &pl) { return sp_train_plan(env, io, pl); });
 }
-
 extern "C" int susnet_spatial_train_dropout_workspace_bytes(const susnet_env *env, const susnet_spatial_train_io *io, uint64_t *bytes_out) {
-    SpTrainPlan pl;
-    if (int rc = sp_train_plan(env, io, pl, true, "susnet_spatial_train_step_dropout")) return rc;
-    if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_dropout_workspace_bytes: null bytes_out");
-    *bytes_out = pl.bytes;
-    return SUSNET_OK;
+    return plan_bytes<SpTrainPlan>("susnet_spatial_train_dropout_workspace_bytes", bytes_out,
+                                   [&](SpTrainPlan &pl) { return sp_train_plan(env, io, pl, true, "susnet_spatial_train_step_dropout"); });
 }
 
 // the checks of one call (`entry`: its name), shared with the sweep, which asks them of every learner: the plan, the dropout structs, the
@@ -574,9 +580,7 @@ extern "C" int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_s
 static_assert(kSpSweepMaxLearners <= kTrMaxLearners, "the reduce + Adam launch is k_train_sweep_adam: its table carries the learners");
 
 extern "C" int susnet_spatial_train_sweep_table_bytes(int32_t n_learners, uint64_t *bytes_out) {
-    if (n_learners < 1 || n_learners > SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)
-        return fail(SUSNET_E_INVALID, "susnet_spatial_train_sweep_table_bytes: n_learners " + std::to_string(n_learners) + " outside 1 .. " +
-                                          std::to_string(SUSNET_SPATIAL_SWEEP_MAX_LEARNERS));
+    if (int rc = check_n_learners("susnet_spatial_train_sweep_table_bytes", n_learners, SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)) return rc;
     if (!bytes_out) return fail(SUSNET_E_INVALID, "susnet_spatial_train_sweep_table_bytes: null bytes_out");
     *bytes_out = sp_sweep_table_bytes(n_learners);
     return SUSNET_OK;
@@ -623,10 +627,9 @@ extern "C" int susnet_spatial_train_sweep(susnet_env *const *envs, const susnet_
                                           void *table, uint64_t table_bytes, void *stream) {
     const std::string entry = "susnet_spatial_train_sweep: ";
     if (!envs || !ios) return fail(SUSNET_E_INVALID, entry + "null envs / ios");
-    if (n_learners < 1 || n_learners > SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)
-        return fail(SUSNET_E_INVALID, entry + "n_learners " + std::to_string(n_learners) + " outside 1 .. " + std::to_string(SUSNET_SPATIAL_SWEEP_MAX_LEARNERS));
+    if (int rc = check_n_learners("susnet_spatial_train_sweep", n_learners, SUSNET_SPATIAL_SWEEP_MAX_LEARNERS)) return rc;
     const int K = n_learners;
-    const auto who = [&](int k, const std::string &what) { return entry + "learner " + std::to_string(k) + ": " + what; };
+    const auto who = [](int k, const std::string &what) { return sweep_learner("susnet_spatial_train_sweep", k, what); };
     std::vector<SpTrainChecked> cs((size_t)K);
     for (int k = 0; k < K; k++) { // each learner passes its own call's checks ...
         if (!envs[k]) return fail(SUSNET_E_INVALID, who(k, "null handle"));
@@ -640,17 +643,7 @@ extern "C" int susnet_spatial_train_sweep(susnet_env *const *envs, const susnet_
         if (cs[(size_t)k].pl.bytes != cs[0].pl.bytes || cs[(size_t)k].pl.G != cs[0].pl.G || cs[(size_t)k].pl.Gconv != cs[0].pl.Gconv)
             return fail(SUSNET_E_INVALID, who(k, "workspace plan differs from learner 0's"));
     }
-    for (int k = 1; k < K; k++) // no two learners write the same memory
-        for (int j = 0; j < k; j++) {
-            const char *field = nullptr;
-            if (ios[k].workspace == ios[j].workspace) field = "workspace";
-            else if (ios[k].losses_out == ios[j].losses_out) field = "losses_out";
-            for (int a = 0; a < 2 && !field; a++)
-                for (int b = 0; b < 2 && !field; b++)
-                    if (ios[k].team[a].enabled && ios[j].team[b].enabled && ios[k].team[a].params == ios[j].team[b].params)
-                        field = a ? "team[1].params" : "team[0].params";
-            if (field) return fail(SUSNET_E_INVALID, who(k, std::string(field) + " is shared with learner " + std::to_string(j)));
-        }
+    if (int rc = check_learners_apart("susnet_spatial_train_sweep", ios, K)) return rc;
     const uint64_t need = sp_sweep_table_bytes(K);
     if (!table || table_bytes < need || (reinterpret_cast<uintptr_t>(table) & 255u))
         return fail(SUSNET_E_INVALID, entry + "table missing, smaller than susnet_spatial_train_sweep_table_bytes (" + std::to_string((unsigned long long)need) +

@@ -15,6 +15,7 @@ host once, after the last block.  (Writing a checkpoint copies weights to the ho
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import pathlib
 from collections import namedtuple
@@ -240,89 +241,56 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
     return _run_blocks(runs, blocks, train_step)
 
 
-def _experiment_config(env, imposter_model, crew_model, components, base, *, num_steps, sequence_length, replay_buffer_size,
-                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter,
-                       train_crew, learning_rate, train_step_interval, target_update_interval, featurizer_type=None) -> dict:
+@dataclasses.dataclass(frozen=True)
+class _Settings:
+    """What ``run_experiment`` and ``run_sweep`` share of a run's settings; a sweep member's are the shared record with its variant's keys
+    replaced.  ``seed`` is a sweep member's (None: ``run_experiment``); ``run_sweep`` has no ``rnn_dropout_seed``."""
+    num_steps: int
+    sequence_length: int
+    replay_buffer_size: int
+    replay_prepopulate_steps: int
+    batch_size: int
+    gamma: float
+    scheduler_start_eps: float
+    scheduler_end_eps: float
+    scheduler_time_steps: int
+    train_imposter: bool
+    train_crew: bool
+    learning_rate: float
+    train_step_interval: int
+    num_checkpoint_saves: int
+    target_update_interval: int
+    dense_train: bool = False
+    rnn_dropout_seed: Optional[int] = None
+    seed: Optional[int] = None
+
+    @classmethod
+    def of(cls, arguments: dict) -> "_Settings":
+        """From an entry point's ``locals()``: the fields it has as parameters, by name."""
+        return cls(**{f.name: arguments[f.name] for f in dataclasses.fields(cls) if f.name in arguments})
+
+    def train_keywords(self) -> dict:
+        """The schedule as ``train`` / ``train_sweep`` take it."""
+        return dict(train_step_interval=self.train_step_interval, batch_size=self.batch_size, num_saves=self.num_checkpoint_saves,
+                    target_update_interval=self.target_update_interval, per_episode_info=True)
+
+
+_Member = namedtuple("_Member", ("env", "metrics", "ring", "policy", "trainer", "scheduler", "directory", "generator", "config"))
+_Member.__doc__ = """A run as ``_build_member`` builds it: a member tuple of ``train_sweep``, then the dict ``config.json`` will hold."""
+
+
+def _experiment_config(env, imposter_model, crew_model, components, base, s: _Settings, featurizer_type=None) -> dict:
     """What ``run_experiment`` writes into ``config.json`` (train.py:185-211), in its key order."""
     return {
-        "num_steps": num_steps, "batch": env.batch, "imposter_model_args": getattr(imposter_model, "config", None),
+        "num_steps": s.num_steps, "batch": env.batch, "imposter_model_args": getattr(imposter_model, "config", None),
         "crew_model_args": getattr(crew_model, "config", None), "imposter_model_type": model_type(imposter_model),
-        "crew_model_type": model_type(crew_model), "featurizer_type": featurizer_type or "flat:" + "+".join(components), "sequence_length": sequence_length,
-        "replay_buffer_size": replay_buffer_size, "replay_prepopulate_steps": replay_prepopulate_steps, "batch_size": batch_size, "gamma": gamma,
-        "scheduler_start_eps": scheduler_start_eps, "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps,
-        "train_imposter": train_imposter, "train_crew": train_crew, "experiment_base_dir": str(base), "optimizer_type": "adam",
-        "learning_rate": learning_rate, "train_step_interval": train_step_interval, "target_update_interval": target_update_interval,
+        "crew_model_type": model_type(crew_model), "featurizer_type": featurizer_type or "flat:" + "+".join(components),
+        "sequence_length": s.sequence_length, "replay_buffer_size": s.replay_buffer_size, "replay_prepopulate_steps": s.replay_prepopulate_steps,
+        "batch_size": s.batch_size, "gamma": s.gamma, "scheduler_start_eps": s.scheduler_start_eps, "scheduler_end_eps": s.scheduler_end_eps,
+        "scheduler_time_steps": s.scheduler_time_steps, "train_imposter": s.train_imposter, "train_crew": s.train_crew,
+        "experiment_base_dir": str(base), "optimizer_type": "adam", "learning_rate": s.learning_rate,
+        "train_step_interval": s.train_step_interval, "target_update_interval": s.target_update_interval,
     }
-
-
-def run_experiment(env, num_steps: int, imposter_model, crew_model, components: Sequence[str], sequence_length: int = 1,
-                   replay_buffer_size: int = 100_000, replay_prepopulate_steps: int = 1000, batch_size: int = 32, gamma: float = 0.99,
-                   scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
-                   train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
-                   train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
-                   generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
-                   dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
-    """``run_experiment`` of src/train.py:152-281 with the models given as modules: writes ``config.json``, builds ring, policy, trainer
-    and schedule, pre-populates the ring with ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
-    entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
-    ``dense_train=True`` (opt-in): the trainer is built with ``dense=True`` -- off the compiled-in layouts the train step is
-    ``susnet_mlp_train_step`` instead of the torch loop.  ``sequence_length`` = T > 1 (the reference's default is 2, train.py:160): the
-    networks read the flattened window of the last T states, ``T * F`` inputs (dqn.py:86-90); acting, collecting and the train step
-    then all go through the dense kernels (the trainer is built ``dense=True`` whatever ``dense_train`` says), and a network that is not
-    dense-served at that T is a ``ValueError``.
-
-    ``featurizer``: a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env`` with ``SpatialDQN`` models (the reference's default,
-    train.py:152-176; the crew may be None) -- ``env`` is then built ``obs=ObsConfig('raw', torch.uint8), auto_reset=True`` and ``components``
-    is not read.  The teams act through ``WindowedPolicyRollout(kernels=True, sequence_length=T)`` (``susnet_spatial_forward`` +
-    ``susnet_agent_policy_actions``), the trainer is built ``featurizer=featurizer, spatial=True`` (a trained team
-    ``susnet_spatial_train_step`` does not serve takes ``torch_train_step``), the ring has ``trajectory_size=T``; ``config.json`` names
-    ``spatial_dqn`` and ``global`` / ``perspective`` and, as ``train_step``, the learner the run takes; the checkpoints are ``<team>_spatial_dqn_<p>.pt``.  A ``SpatialDQN`` the kernels do not
-    act for is a ``ValueError`` that says which bound failed.  ``rnn_dropout_seed`` (with ``featurizer``; None: models with dropout between
-    their RNN layers train through ``torch_train_step``): the trainer is built with it, so such models -- the reference's own
-    ``rnn_layers: 3, rnn_dropout: 0.2`` -- LEARN under the library's dropout masks (``susnet_spatial_train_step_dropout``), online and target
-    network; they ACT in eval mode (put them there with ``model.eval()``: ``susnet_spatial_forward`` is the eval-mode forward and refuses a
-    training-mode model with dropout, as before; the device train step does not put them back into training mode).  The seed is written
-    into ``config.json``."""
-    components = list(components)
-    sequence_length = int(sequence_length)
-    if featurizer is not None:
-        return _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size,
-                                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps,
-                                       train_imposter, train_crew, experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves,
-                                       target_update_interval, generator, episode_log, rnn_dropout_seed)
-    if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
-        raise ValueError("run_experiment: build the env with obs=ObsConfig('flat', components), auto_reset=True")
-    if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
-        raise ValueError("run_experiment: served are reference MLPs (a crew model of None acts randomly)")
-    # (built before anything is written: at sequence_length > 1 a network that is not dense-served is refused here, naming sequence_length
-    # and the input width T * F it would need)
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True, sequence_length=sequence_length)
-    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
-    experiment_dir = base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
-    experiment_dir.mkdir(parents=True, exist_ok=True)
-    config = _experiment_config(env, imposter_model, crew_model, components, base, num_steps=num_steps, sequence_length=sequence_length,
-                                replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
-                                gamma=gamma, scheduler_start_eps=scheduler_start_eps, scheduler_end_eps=scheduler_end_eps,
-                                scheduler_time_steps=scheduler_time_steps, train_imposter=train_imposter, train_crew=train_crew,
-                                learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval)
-    (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
-
-    trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
-                                   train_crew=train_crew, policy=policy, dense=dense_train or sequence_length > 1,
-                                   sequence_length=sequence_length if sequence_length > 1 else None)
-    if sequence_length > 1 and any(trainer.trained) and not trainer.dense:
-        raise ValueError(f"run_experiment: sequence_length = {sequence_length}: the trained networks are not served by susnet_mlp_train_step on "
-                         f"windows of {sequence_length} states (needed: reference MLP stacks with a network input of T * F)")
-    scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
-    metrics = EpisodicMetricHandler()
-    ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
-    if replay_prepopulate_steps > 0:
-        ring.populate_fused(env, replay_prepopulate_steps)
-    train(env, metrics, num_steps, ring, policy, trainer, scheduler, experiment_dir, train_step_interval=train_step_interval,
-          batch_size=batch_size, num_saves=num_checkpoint_saves, target_update_interval=target_update_interval, generator=generator,
-          episode_log=episode_log, per_episode_info=True)
-    metrics.save_metrics(save_file_path=experiment_dir / "metrics.json")
-    return metrics
 
 
 def spatial_unserved_reason(env, featurizer, model, n_actions: int, T: int) -> Optional[str]:
@@ -345,50 +313,126 @@ def spatial_unserved_reason(env, featurizer, model, n_actions: int, T: int) -> O
     return spatial_feed_mismatch(env, featurizer, desc, n_actions)
 
 
-def _run_spatial_experiment(env, num_steps, imposter_model, crew_model, featurizer, sequence_length, replay_buffer_size, replay_prepopulate_steps,
-                            batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter, train_crew,
-                            experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves, target_update_interval, generator,
-                            episode_log, rnn_dropout_seed=None) -> EpisodicMetricHandler:
-    """``run_experiment`` for ``SpatialDQN`` models on a Global / Perspective featurizer (see there)."""
-    from .features import GlobalFeaturizer
-
-    T = sequence_length
-    if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
-        raise ValueError("run_experiment: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
+def _check_spatial_models(who: str, env, featurizer, imposter_model, crew_model, T: int) -> None:
+    """``ValueError`` unless ``WindowedPolicyRollout(kernels=True)`` acts for both teams: each present team's ``SpatialDQN`` is served
+    (``spatial_unserved_reason``; ``who`` may name a sweep's variant), and a random crew has the production stream (that message names the
+    entry point alone, as it always has)."""
     for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
         if team == "crew" and model is None:
             continue
         why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
         if why is not None:
-            raise ValueError(f"run_experiment: the {team} model is not served by the spatial kernels: {why}")
+            raise ValueError(f"{who}: the {team} model is not served by the spatial kernels: {why}")
     if crew_model is None and env.rng_kind != "philox":
-        raise ValueError("run_experiment: a random crew draws from the production stream: build the env with rng='philox'")
-    policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
-    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
-    experiment_dir = base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
-    experiment_dir.mkdir(parents=True, exist_ok=True)
-    config = _experiment_config(env, imposter_model, crew_model, [], base, num_steps=num_steps, sequence_length=T,
-                                replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
-                                gamma=gamma, scheduler_start_eps=scheduler_start_eps, scheduler_end_eps=scheduler_end_eps,
-                                scheduler_time_steps=scheduler_time_steps, train_imposter=train_imposter, train_crew=train_crew,
-                                learning_rate=learning_rate, train_step_interval=train_step_interval, target_update_interval=target_update_interval,
-                                featurizer_type="global" if isinstance(featurizer, GlobalFeaturizer) else "perspective")
-    trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, [], lr=learning_rate, gamma=gamma, train_imposter=train_imposter,
-                                   train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True, rnn_dropout_seed=rnn_dropout_seed)
-    scheduler = ExponentialSchedule(scheduler_start_eps, scheduler_end_eps, scheduler_time_steps)
-    metrics = EpisodicMetricHandler()
-    ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
-    # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
-    config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
-    config["rnn_dropout_seed"] = rnn_dropout_seed
-    (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
-    if replay_prepopulate_steps > 0:
-        ring.populate_fused(env, replay_prepopulate_steps)
-    train(env, metrics, num_steps, ring, policy, trainer, scheduler, experiment_dir, train_step_interval=train_step_interval,
-          batch_size=batch_size, num_saves=num_checkpoint_saves, target_update_interval=target_update_interval, generator=generator,
-          episode_log=episode_log, per_episode_info=True)
-    metrics.save_metrics(save_file_path=experiment_dir / "metrics.json")
-    return metrics
+        raise ValueError(f"{who.partition(':')[0]}: a random crew draws from the production stream: build the env with rng='philox'")
+
+
+def _build_member(variant: Optional[int], env, models, components, featurizer, s: _Settings, dirs, generator) -> _Member:
+    """THE place a run is built -- ``run_experiment``'s one (``variant`` None) and every member of ``run_sweep`` (``variant``: its index):
+    the checks of env and models, then policy, trainer, ring, schedule, metric handler and the ``config.json`` dict.  Nothing is written
+    and nothing is collected.  ``models``: (imposter, crew); ``dirs``: (experiment_base_dir, the run's own directory).
+    ``featurizer`` None is the flat kind: ``env`` fuses ``ObsConfig('flat', components)``, reference MLPs, ``PolicyRollout``.  A Global /
+    Perspective featurizer is the spatial kind: raw uint8 observations, ``SpatialDQN``s, ``WindowedPolicyRollout(kernels=True)``, a trainer
+    built ``featurizer=..., spatial=True``; ``components`` is not read, and ``config.json`` also names the learner the run takes
+    (``train_step``) and the dropout seed.  What the two callers do differently, on purpose:
+    * flat ``run_experiment`` acts and trains through the dense kernels wherever the fused ones do not serve, on windows of T states too;
+      a flat sweep member is built for the fused kernels, one state (``dense_train`` alone sends its trainer to the dense step);
+    * a sweep member's ``config.json`` carries its ``seed``, and its ``generator`` is made here from that seed (``run_experiment`` passes
+      its caller's, or None: the device's global generator)."""
+    from .features import GlobalFeaturizer
+
+    sweep, who = variant is not None, "run_experiment" if variant is None else "run_sweep"
+    (imposter_model, crew_model), (base, experiment_dir), T = models, dirs, s.sequence_length
+    if featurizer is None:
+        if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
+            raise ValueError(f"{who}: {'env_factory must build' if sweep else 'build'} the env with obs=ObsConfig('flat', components), auto_reset=True")
+        if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
+            raise ValueError(f"{who}: served are reference MLPs (a crew model of None acts randomly)")
+        # (at sequence_length > 1 a network that is not dense-served is refused here, naming sequence_length and the input width T * F it needs)
+        policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True,
+                               **({} if sweep else {"dense": True, "sequence_length": T}))
+        learner = {"dense": s.dense_train} if sweep else {"dense": s.dense_train or T > 1, "sequence_length": T if T > 1 else None}
+        featurizer_type = None
+    else:
+        if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
+            raise ValueError(f"{who}: with {'featurizer_factory, env_factory must build' if sweep else 'a featurizer, build'} the env with "
+                             "obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
+        _check_spatial_models(f"{who}: variant {variant}" if sweep else who, env, featurizer, imposter_model, crew_model, T)
+        components = []
+        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
+        learner = {"featurizer": featurizer, "spatial": True, "rnn_dropout_seed": s.rnn_dropout_seed}
+        featurizer_type = "global" if isinstance(featurizer, GlobalFeaturizer) else "perspective"
+    trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=s.learning_rate, gamma=s.gamma, train_imposter=s.train_imposter,
+                                   train_crew=s.train_crew, policy=policy, **learner)
+    if featurizer is None and T > 1 and any(trainer.trained) and not trainer.dense:
+        raise ValueError(f"{who}: sequence_length = {T}: the trained networks are not served by susnet_mlp_train_step on "
+                         f"windows of {T} states (needed: reference MLP stacks with a network input of T * F)")
+    ring = DeviceReplayBuffer(s.replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
+    config = _experiment_config(env, imposter_model, crew_model, components, base, s, featurizer_type)
+    if sweep:  # its seed is on record, and its replay samples are drawn by a generator of its own, seeded with it
+        config["seed"] = s.seed
+        generator = torch.Generator(device=env.device)
+        generator.manual_seed(int(s.seed))
+    if featurizer is not None:
+        # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
+        config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
+        config["rnn_dropout_seed"] = s.rnn_dropout_seed
+    scheduler = ExponentialSchedule(s.scheduler_start_eps, s.scheduler_end_eps, s.scheduler_time_steps)
+    return _Member(env, EpisodicMetricHandler(), ring, policy, trainer, scheduler, experiment_dir, generator, config)
+
+
+def _start(members: List[_Member], s: _Settings) -> None:
+    """Per member: its directory, ``config.json`` (train.py:212-213), then the ring's prepopulation with random ticks."""
+    for m in members:
+        m.directory.mkdir(parents=True, exist_ok=True)
+        (m.directory / "config.json").write_text(json.dumps(m.config, indent=4, default=str))
+        if s.replay_prepopulate_steps > 0:
+            m.ring.populate_fused(m.env, s.replay_prepopulate_steps)
+
+
+def _base_dir(experiment_base_dir) -> pathlib.Path:
+    return pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
+
+
+def run_experiment(env, num_steps: int, imposter_model, crew_model, components: Sequence[str], sequence_length: int = 1,
+                   replay_buffer_size: int = 100_000, replay_prepopulate_steps: int = 1000, batch_size: int = 32, gamma: float = 0.99,
+                   scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
+                   train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
+                   train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
+                   generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
+                   dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
+    """``run_experiment`` of src/train.py:152-281 with the models given as modules: builds ring, policy, trainer and schedule
+    (``_build_member``; a run that is refused there has written nothing), writes ``config.json``, pre-populates the ring with
+    ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
+    entries of ``metrics.json`` hold one value per episode, the reference's shape), writes ``metrics.json`` and the checkpoints into ``experiment_base_dir/<timestamp>/`` and returns the metric handler.  ``replay_buffer_size`` counts transitions.
+    ``dense_train=True`` (opt-in): the trainer is built with ``dense=True`` -- off the compiled-in layouts the train step is
+    ``susnet_mlp_train_step`` instead of the torch loop.  ``sequence_length`` = T > 1 (the reference's default is 2, train.py:160): the
+    networks read the flattened window of the last T states, ``T * F`` inputs (dqn.py:86-90); acting, collecting and the train step
+    then all go through the dense kernels (the trainer is built ``dense=True`` whatever ``dense_train`` says), and a network that is not
+    dense-served at that T is a ``ValueError``.
+
+    ``featurizer``: a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env`` with ``SpatialDQN`` models (the reference's default,
+    train.py:152-176; the crew may be None) -- ``env`` is then built ``obs=ObsConfig('raw', torch.uint8), auto_reset=True`` and ``components``
+    is not read.  The teams act through ``WindowedPolicyRollout(kernels=True, sequence_length=T)`` (``susnet_spatial_forward`` +
+    ``susnet_agent_policy_actions``), the trainer is built ``featurizer=featurizer, spatial=True`` (a trained team
+    ``susnet_spatial_train_step`` does not serve takes ``torch_train_step``), the ring has ``trajectory_size=T``; ``config.json`` names
+    ``spatial_dqn`` and ``global`` / ``perspective`` and, as ``train_step``, the learner the run takes; the checkpoints are ``<team>_spatial_dqn_<p>.pt``.  A ``SpatialDQN`` the kernels do not
+    act for is a ``ValueError`` that says which bound failed.  ``rnn_dropout_seed`` (with ``featurizer``; None: models with dropout between
+    their RNN layers train through ``torch_train_step``): the trainer is built with it, so such models -- the reference's own
+    ``rnn_layers: 3, rnn_dropout: 0.2`` -- LEARN under the library's dropout masks (``susnet_spatial_train_step_dropout``), online and target
+    network; they ACT in eval mode (put them there with ``model.eval()``: ``susnet_spatial_forward`` is the eval-mode forward and refuses a
+    training-mode model with dropout, as before; the device train step does not put them back into training mode).  The seed is written
+    into ``config.json``."""
+    sequence_length = int(sequence_length)
+    s = _Settings.of(locals())
+    base = _base_dir(experiment_base_dir)
+    m = _build_member(None, env, (imposter_model, crew_model), list(components), featurizer, s, (base, base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")),
+                      generator)
+    _start([m], s)
+    train(env, m.metrics, num_steps, m.ring, m.policy, m.trainer, m.scheduler, m.directory, generator=generator, episode_log=episode_log,
+          **s.train_keywords())
+    m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
+    return m.metrics
 
 
 SWEEP_VARIANT_KEYS = ("gamma", "learning_rate", "seed", "scheduler_start_eps", "scheduler_end_eps", "scheduler_time_steps", "name")
@@ -425,144 +469,70 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     notebooks/experiment_mlp.ipynb: gamma 0.99 / 0.9 / 0.8 on one game and one MLP) -- as ONE run: the members collect one after another
     and take their train steps together (``train_sweep``).  The shared arguments are ``run_experiment``'s.  ``variants``: one dict per
     member with any of ``gamma``, ``learning_rate``, ``seed``, ``scheduler_start_eps``, ``scheduler_end_eps``, ``scheduler_time_steps``,
-    ``name`` (anything else: ``ValueError``); a key left out takes the shared value.  ``env_factory(seed)`` builds a member's env
-    (``obs=ObsConfig('flat', components), auto_reset=True``); ``imposter_model_factory(env)`` / ``crew_model_factory(env)`` its MLPs
-    (``crew_model_factory=None``: random crews) under ``torch.manual_seed(seed)``; the member's sample generator is seeded with ``seed``
-    too.  Each member gets ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values),
-    the checkpoints and ``metrics.json`` exactly as ``run_experiment`` writes them, so plotting over one directory per gamma keeps
-    working.  ``dense_train`` is ``run_experiment``'s: members whose step the sweep call does not serve then take their dense steps one
-    after another.  Returns the members' metric handlers.
-
-    ``featurizer_factory(env)`` (opt-in; None: everything above -- that form is MLP-only as it was, a ``SpatialDQN`` is a ``ValueError``
-    there) returning a ``GlobalFeaturizer`` /
-    ``PerspectiveFeaturizer`` over the member's env sweeps ``SpatialDQN`` members -- the reference's default model -- built as
-    ``run_experiment(..., featurizer=...)`` builds a run: ``env_factory(seed)`` builds the env ``obs=ObsConfig('raw', torch.uint8),
-    auto_reset=True``, the factories return ``SpatialDQN``s (a crew of None acts randomly), ``components`` is not read, the teams act
-    through ``WindowedPolicyRollout(kernels=True, sequence_length=T)`` in eval mode, the ring has ``trajectory_size = sequence_length``
-    (1 .. ``SPATIAL_MAX_T``) and the trainer is ``DeviceDQNTeamTrainer(featurizer=..., spatial=True)``; the
-    members' train steps are ONE ``susnet_spatial_train_sweep`` call per chunk of ``SPATIAL_SWEEP_MAX_LEARNERS``.  A model the spatial
-    kernels do not serve is a ``ValueError`` with the bound that failed (``spatial_unserved_reason``).  There is no dropout seed here:
-    members with dropout between their RNN layers take ``torch_train_step`` one after another, as such a ``run_experiment`` without
-    ``rnn_dropout_seed`` does (a ``DeviceDQNSweepTrainer`` over trainers built with ``rnn_dropout_seed`` does sweep them).
-    ``config.json`` records as ``train_step`` what the members take:
-    ``susnet_spatial_train_sweep``, or -- where the sweep call does not serve them -- a member's own ``susnet_spatial_train_step`` /
-    ``torch_train_step``."""
-    components = list(components)
-    variants = check_variants(variants)
-    if featurizer_factory is not None:
-        return _run_spatial_sweep(env_factory, variants, num_steps, imposter_model_factory, crew_model_factory, featurizer_factory, int(sequence_length),
-                                  replay_buffer_size, replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps,
-                                  scheduler_time_steps, train_imposter, train_crew, experiment_base_dir, learning_rate, train_step_interval,
-                                  num_checkpoint_saves, target_update_interval, seed)
-    if sequence_length != 1:
+    ``name`` (anything else: ``ValueError``); a key left out takes the shared value.  Per member: ``env_factory(seed)`` builds its env,
+    ``featurizer_factory(env)`` -- where there is one -- its featurizer, then under ``torch.manual_seed(seed)``
+    ``imposter_model_factory(env)`` / ``crew_model_factory(env)`` its models (``crew_model_factory=None``: random crews);
+    ``_build_member`` builds the rest as it builds ``run_experiment``'s run, with a sample generator seeded with ``seed`` too.  Each member gets
+    ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values and ``seed``), the
+    checkpoints and ``metrics.json`` as ``run_experiment`` writes them, so plotting over one directory per gamma keeps working.  Returns
+    the members' metric handlers.  How a member differs from ``run_experiment``'s run:
+    * without ``featurizer_factory`` the sweep is MLP-only as it was (a ``SpatialDQN`` is a ``ValueError`` there) and a window of one state
+      is served, through the fused kernels: ``sequence_length=1``, and
+      ``dense_train`` only sends members whose step the sweep call does not serve to their dense steps, one after another;
+    * with ``featurizer_factory`` (``SpatialDQN`` members, ``sequence_length`` 1 .. ``SPATIAL_MAX_T``) there is no dropout seed
+      (``config.json`` says None): members with dropout between their RNN layers take ``torch_train_step`` one after another (a
+      ``DeviceDQNSweepTrainer`` over trainers built with ``rnn_dropout_seed`` does sweep them);
+    * ``train_step`` in a ``SpatialDQN`` member's ``config.json`` is ``susnet_spatial_train_sweep`` -- one call per chunk of
+      ``SPATIAL_SWEEP_MAX_LEARNERS`` -- where that serves the training members, else the member's own learner."""
+    components, variants, spatial = list(components), check_variants(variants), featurizer_factory is not None
+    if not spatial and sequence_length != 1:
         raise ValueError("run_sweep: a window of one state is served (sequence_length=1): the Q-network kernel and "
                          "susnet_dqn_train_sweep read one state")
-    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
+    sequence_length = int(sequence_length)
+    shared = _Settings.of(locals())
+    base = _base_dir(experiment_base_dir)
     dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
-    shared = {"gamma": gamma, "learning_rate": learning_rate, "seed": seed, "scheduler_start_eps": scheduler_start_eps,
-              "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps}
-    members, handlers = [], []
+    members = []
     for k, (variant, experiment_dir) in enumerate(zip(variants, dirs)):
-        v = {**shared, **{key: val for key, val in variant.items() if key != "name"}}
-        env = env_factory(int(v["seed"]))
-        if env.obs_config.mode != "flat" or list(env.obs_config.components) != components:
-            raise ValueError("run_sweep: env_factory must build the env with obs=ObsConfig('flat', components), auto_reset=True")
-        torch.manual_seed(int(v["seed"]))
-        imposter_model = imposter_model_factory(env)
-        crew_model = crew_model_factory(env) if crew_model_factory is not None else None
-        if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
-            raise ValueError("run_sweep: served are reference MLPs (a crew model of None acts randomly)")
-        experiment_dir.mkdir(parents=True, exist_ok=True)
-        config = _experiment_config(env, imposter_model, crew_model, components, base, num_steps=num_steps, sequence_length=sequence_length,
-                                    replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
-                                    gamma=v["gamma"], scheduler_start_eps=v["scheduler_start_eps"], scheduler_end_eps=v["scheduler_end_eps"],
-                                    scheduler_time_steps=v["scheduler_time_steps"], train_imposter=train_imposter, train_crew=train_crew,
-                                    learning_rate=v["learning_rate"], train_step_interval=train_step_interval,
-                                    target_update_interval=target_update_interval)
-        config["seed"] = v["seed"]
-        (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
-        policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True)
-        trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=v["learning_rate"], gamma=v["gamma"],
-                                       train_imposter=train_imposter, train_crew=train_crew, policy=policy, dense=dense_train)
-        scheduler = ExponentialSchedule(v["scheduler_start_eps"], v["scheduler_end_eps"], v["scheduler_time_steps"])
-        ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, sequence_length, env.n_agents, env.n_imposters, device=env.device)
-        if replay_prepopulate_steps > 0:
-            ring.populate_fused(env, replay_prepopulate_steps)
-        generator = torch.Generator(device=env.device)
-        generator.manual_seed(int(v["seed"]))
-        handlers.append(EpisodicMetricHandler())
-        members.append((env, handlers[-1], ring, policy, trainer, scheduler, experiment_dir, generator))
-    train_sweep(members, num_steps, train_step_interval=train_step_interval, batch_size=batch_size, num_saves=num_checkpoint_saves,
-                target_update_interval=target_update_interval, per_episode_info=True)
-    for handler, experiment_dir in zip(handlers, dirs):
-        handler.save_metrics(save_file_path=experiment_dir / "metrics.json")
-    return handlers
+        s = dataclasses.replace(shared, **{key: val for key, val in variant.items() if key != "name"})
+        # the order of the member's random draws: env by seed, torch.manual_seed(seed), the imposter factory, the crew factory
+        env = env_factory(int(s.seed))
+        featurizer = featurizer_factory(env) if spatial else None
+        torch.manual_seed(int(s.seed))
+        models = (imposter_model_factory(env), crew_model_factory(env) if crew_model_factory is not None else None)
+        members.append(_build_member(k, env, models, components, featurizer, s, (base, experiment_dir), None))
+    if spatial:  # which learner the train steps take: the sweep call where it serves all training members, else each member's own
+        training = [m for m in members if any(m.trainer.trained)]
+        swept = bool(training) and DeviceDQNSweepTrainer([m.trainer for m in training]).uses_spatial([m.ring for m in training])
+        for m in members:
+            own = m.config.pop("train_step")  # (put back as the last key, behind seed and rnn_dropout_seed, where it has always stood)
+            m.config["train_step"] = "susnet_spatial_train_sweep" if swept and own is not None else own
+    _start(members, shared)
+    train_sweep([m[:8] for m in members], num_steps, **shared.train_keywords())
+    for m in members:
+        m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
+    return [m.metrics for m in members]
 
 
-def _run_spatial_sweep(env_factory, variants, num_steps, imposter_model_factory, crew_model_factory, featurizer_factory, T, replay_buffer_size,
-                       replay_prepopulate_steps, batch_size, gamma, scheduler_start_eps, scheduler_end_eps, scheduler_time_steps, train_imposter,
-                       train_crew, experiment_base_dir, learning_rate, train_step_interval, num_checkpoint_saves, target_update_interval,
-                       seed) -> List[EpisodicMetricHandler]:
-    """``run_sweep`` for ``SpatialDQN`` members on a Global / Perspective featurizer (see there): each member is built as
-    ``_run_spatial_experiment`` builds a run."""
-    from .features import GlobalFeaturizer
-
-    base = pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
-    dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
-    shared = {"gamma": gamma, "learning_rate": learning_rate, "seed": seed, "scheduler_start_eps": scheduler_start_eps,
-              "scheduler_end_eps": scheduler_end_eps, "scheduler_time_steps": scheduler_time_steps}
-    members, handlers, configs = [], [], []
-    for k, (variant, experiment_dir) in enumerate(zip(variants, dirs)):
-        v = {**shared, **{key: val for key, val in variant.items() if key != "name"}}
-        env = env_factory(int(v["seed"]))
-        if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
-            raise ValueError("run_sweep: with featurizer_factory, env_factory must build the env with obs=ObsConfig('raw', dtype=torch.uint8), "
-                             "auto_reset=True")
-        featurizer = featurizer_factory(env)
-        torch.manual_seed(int(v["seed"]))
-        imposter_model = imposter_model_factory(env)
-        crew_model = crew_model_factory(env) if crew_model_factory is not None else None
-        for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
-            if team == "crew" and model is None:
-                continue
-            why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
-            if why is not None:
-                raise ValueError(f"run_sweep: variant {k}: the {team} model is not served by the spatial kernels: {why}")
-        if crew_model is None and env.rng_kind != "philox":
-            raise ValueError("run_sweep: a random crew draws from the production stream: build the env with rng='philox'")
-        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
-        trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, [], lr=v["learning_rate"], gamma=v["gamma"], train_imposter=train_imposter,
-                                       train_crew=train_crew, policy=policy, featurizer=featurizer, spatial=True)
-        config = _experiment_config(env, imposter_model, crew_model, [], base, num_steps=num_steps, sequence_length=T,
-                                    replay_buffer_size=replay_buffer_size, replay_prepopulate_steps=replay_prepopulate_steps, batch_size=batch_size,
-                                    gamma=v["gamma"], scheduler_start_eps=v["scheduler_start_eps"], scheduler_end_eps=v["scheduler_end_eps"],
-                                    scheduler_time_steps=v["scheduler_time_steps"], train_imposter=train_imposter, train_crew=train_crew,
-                                    learning_rate=v["learning_rate"], train_step_interval=train_step_interval,
-                                    target_update_interval=target_update_interval,
-                                    featurizer_type="global" if isinstance(featurizer, GlobalFeaturizer) else "perspective")
-        config["seed"], config["rnn_dropout_seed"] = v["seed"], None
-        scheduler = ExponentialSchedule(v["scheduler_start_eps"], v["scheduler_end_eps"], v["scheduler_time_steps"])
-        ring = DeviceReplayBuffer(replay_buffer_size, env.flattened_state_size, T, env.n_agents, env.n_imposters, device=env.device)
-        generator = torch.Generator(device=env.device)
-        generator.manual_seed(int(v["seed"]))
-        handlers.append(EpisodicMetricHandler())
-        configs.append(config)
-        members.append((env, handlers[-1], ring, policy, trainer, scheduler, experiment_dir, generator))
-    # which learner the members' train steps take: the sweep call where it serves all training members, else each member's own
-    training = [m for m in members if any(m[4].trained)]
-    swept = bool(training) and DeviceDQNSweepTrainer([m[4] for m in training]).uses_spatial([m[2] for m in training])
-    for (env, _, ring, _, trainer, _, experiment_dir, _), config in zip(members, configs):
-        own = "susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step"
-        config["train_step"] = ("susnet_spatial_train_sweep" if swept else own) if any(trainer.trained) else None
-        experiment_dir.mkdir(parents=True, exist_ok=True)
-        (experiment_dir / "config.json").write_text(json.dumps(config, indent=4, default=str))
-        if replay_prepopulate_steps > 0:
-            ring.populate_fused(env, replay_prepopulate_steps)
-    train_sweep(members, num_steps, train_step_interval=train_step_interval, batch_size=batch_size, num_saves=num_checkpoint_saves,
-                target_update_interval=target_update_interval, per_episode_info=True)
-    for handler, experiment_dir in zip(handlers, dirs):
-        handler.save_metrics(save_file_path=experiment_dir / "metrics.json")
-    return handlers
+def _evaluate_blocks(env, n_ticks: int, block_ticks: int, gamma: float, capacity: Optional[int], begin, refresh_obs: bool) -> dict:
+    """The frame of ``evaluate``: reset, an ``EpisodeLog`` and a feed of ``n_block`` ticks, then per block ``act(feed, n)`` -- ``act`` is
+    what ``begin(n_block)`` returns, called once behind the reset -- and ``EpisodeLog.update``; ONE read-back at the end."""
+    n_block = max(1, min(int(block_ticks), n_ticks))
+    env.reset()
+    if capacity is None:  # an episode takes at least one tick
+        capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
+    log = EpisodeLog(env, gamma=gamma, capacity=capacity)
+    feed = env.alloc_feed(n_block)
+    act = begin(n_block)
+    t = 0
+    while t < n_ticks:
+        n = min(n_block, n_ticks - t)
+        act(feed, n)
+        log.update(feed, n, tick_base=t)
+        t += n
+    if refresh_obs:
+        env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
+    return summarize_episodes(log.records(), ticks=n_ticks)
 
 
 @torch.no_grad()
@@ -580,11 +550,29 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     read."""
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
+    last = None  # the feed slot of the previous tick
     if featurizer is not None:
-        return _evaluate_spatial(env, imposter_model, crew_model, featurizer, int(n_ticks), epsilon, block_ticks, mask_dead, gamma, capacity,
-                                 int(sequence_length))
-    components = list(components)
-    policy = PolicyRollout(env, imposter_model, crew_model, components=components, epsilon=epsilon, mask_dead=mask_dead, dense=True,
+        n_ticks, T = int(n_ticks), int(sequence_length)
+        if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8:
+            raise ValueError("evaluate: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
+        _check_spatial_models("evaluate", env, featurizer, imposter_model, crew_model, T)
+        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, epsilon=epsilon, mask_dead=mask_dead, kernels=True)
+
+        def act_spatial(feed, n):  # collect's acting loop, without a ring
+            nonlocal last
+            for k in range(n):
+                if last is not None:
+                    policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
+                q_imp, q_crew = policy.q_rows()
+                env.agent_policy_tick_into(feed, k, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                last = k
+
+        def begin(n_block):
+            policy.reset_window()  # train.py:318-322: the fresh state T times
+            return act_spatial
+
+        return _evaluate_blocks(env, n_ticks, block_ticks, gamma, capacity, begin, True)
+    policy = PolicyRollout(env, imposter_model, crew_model, components=list(components), epsilon=epsilon, mask_dead=mask_dead, dense=True,
                            sequence_length=sequence_length)
     windowed = policy.sequence_length > 1
     imp_served, crew_served, dense = served_by_kernels(policy)
@@ -599,75 +587,33 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
             raise ValueError("evaluate: a random crew draws from the production stream: build the env with rng='philox'")
     elif not env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon):
         raise ValueError("evaluate: this env / model pair / epsilon is not served by the one-kernel policy tick (susnet_qnet_policy_step)")
-    n_ticks = int(n_ticks)
-    n_block = max(1, min(int(block_ticks), n_ticks))
-    fused = not dense and (n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0)
-    env.reset()
-    if capacity is None:  # an episode takes at least one tick
-        capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
-    log = EpisodeLog(env, gamma=gamma, capacity=capacity)
-    feed = env.alloc_feed(n_block)
-    t = 0
-    last = None  # the feed slot of the previous tick
-    while t < n_ticks:
-        n = min(n_block, n_ticks - t)
-        if fused:
-            env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
-        elif dense:  # the dense forward(s) on the current flat observation, then susnet_policy_step into the feed
-            for k in range(n):
-                env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
-                if windowed:  # the first tick acts on the fresh state T times (train.py:318-322), later ones on the pushed window
-                    if last is None:
-                        policy.reset_window()
-                    else:
-                        policy.push(feed["done"][last], feed["truncated"][last])
-                q_imp, q_crew = policy.q_rows()
-                env.policy_tick_into(feed, k, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
-                last = k
-        else:
-            for k in range(n):
-                env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
-        log.update(feed, n, tick_base=t)
-        t += n
-    if dense:
-        env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
-    rec = log.records()
-    return summarize_episodes(rec, ticks=n_ticks)
 
+    def act_rollout(feed, n):  # the fused rollout: one launch per block
+        env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
 
-def _evaluate_spatial(env, imposter_model, crew_model, featurizer, n_ticks, epsilon, block_ticks, mask_dead, gamma, capacity, T) -> dict:
-    """``evaluate`` for ``SpatialDQN`` models: ``collect``'s acting loop into a feed + ``EpisodeLog``, without a ring."""
-    if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8:
-        raise ValueError("evaluate: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
-    for team, model, n_actions in (("imposter", imposter_model, env.n_imposter_actions), ("crew", crew_model, env.n_crew_actions)):
-        if team == "crew" and model is None:
-            continue
-        why = spatial_unserved_reason(env, featurizer, model, n_actions, T)
-        if why is not None:
-            raise ValueError(f"evaluate: the {team} model is not served by the spatial kernels: {why}")
-    if crew_model is None and env.rng_kind != "philox":
-        raise ValueError("evaluate: a random crew draws from the production stream: build the env with rng='philox'")
-    policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, epsilon=epsilon, mask_dead=mask_dead, kernels=True)
-    n_block = max(1, min(int(block_ticks), n_ticks))
-    env.reset()
-    if capacity is None:
-        capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
-    log = EpisodeLog(env, gamma=gamma, capacity=capacity)
-    feed = env.alloc_feed(n_block)
-    policy.reset_window()  # train.py:318-322: the fresh state T times
-    t, last = 0, None
-    while t < n_ticks:
-        n = min(n_block, n_ticks - t)
+    def act_dense(feed, n):  # the dense forward(s) on the current flat observation, then susnet_policy_step into the feed
+        nonlocal last
         for k in range(n):
-            if last is not None:
-                policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
+            env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
+            if windowed:  # the first tick acts on the fresh state T times (train.py:318-322), later ones on the pushed window
+                if last is None:
+                    policy.reset_window()
+                else:
+                    policy.push(feed["done"][last], feed["truncated"][last])
             q_imp, q_crew = policy.q_rows()
-            env.agent_policy_tick_into(feed, k, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
+            env.policy_tick_into(feed, k, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
             last = k
-        log.update(feed, n, tick_base=t)
-        t += n
-    env.refresh_obs()
-    return summarize_episodes(log.records(), ticks=n_ticks)
+
+    def act_ticks(feed, n):  # the one-kernel policy tick, tick by tick
+        for k in range(n):
+            env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
+
+    def begin(n_block):
+        if dense:
+            return act_dense
+        return act_rollout if n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0 else act_ticks
+
+    return _evaluate_blocks(env, int(n_ticks), block_ticks, gamma, capacity, begin, dense)
 
 
 def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:

@@ -131,25 +131,25 @@ class DeviceDQNTeamTrainer:
                 self.exp_avg[t] = torch.zeros_like(self.flat[t])
                 self.exp_avg_sq[t] = torch.zeros_like(self.flat[t])
                 self.step_count[t] = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._optim: List[Optional[torch.optim.Adam]] = [None, None]
+        # where each team's Adam state currently lives: "flat" (the buffers the kernels update) or "optim" (the torch optimizer)
+        self._owner = ["flat", "flat"]
         self._dims = [self._mlp_dims(m) if tr else None for m, tr in zip(self.models, self.trained)]
         self.hip = (self.device.type == "cuda" and any(self.trained) and all(d is not None for d, tr in zip(self._dims, self.trained) if tr)
-                    and self._hip_served())
+                    and self._served(self._io(), env.lib.susnet_dqn_workspace_bytes))
         if policy is not None and any(self._policy_image(t) is not None for t in range(2)) and list(policy.components) != self.components:
             raise ValueError(f"policy reads components {list(policy.components)}, the trainer {self.components}: the rewritten images would "
                              "belong to another feature layout")
         self._featurizer = featurizer
-        self._optim: List[Optional[torch.optim.Adam]] = [None, None]
-        # where each team's Adam state currently lives: "flat" (the buffers the kernels update) or "optim" (the torch optimizer)
-        self._owner = ["flat", "flat"]
         self._ws, self._losses = None, None
         # the dense step: each trained team's [F, h.., n_actions] where susnet_mlp_train_step serves it
         stacks = [dense_stack(m) if tr else None for m, tr in zip(self.models, self.trained)]
         self._dense_dims = [s and s[2] for s in stacks]
         self.sequence_length = None if sequence_length is None else int(sequence_length)  # (the dense step's T: settled by _dense_served)
+        self._gathered = None  # (n, T, gathered states, gathered next states, their featurized rows, the next states'): _gather
         self.dense = (bool(dense) and self.device.type == "cuda" and any(self.trained) and featurizer is None
                       and all(c in L.FLAT_COMPONENTS for c in self.components)
                       and all(d is not None for d, tr in zip(self._dense_dims, self.trained) if tr) and self._dense_served())
-        self._dense_bufs = None  # (n, gathered states, gathered next states, spec + rows of states, spec + rows of next states)
         # the spatial step: each trained team's SpatialDQN as susnet_spatial_train_step reads it
         self.rnn_dropout_seed = None if rnn_dropout_seed is None else int(rnn_dropout_seed) & (2**64 - 1)
         self.dropout_steps = 0
@@ -157,7 +157,6 @@ class DeviceDQNTeamTrainer:
                               for m, tr in zip(self.models, self.trained)]
         self.spatial = (bool(spatial) and self.device.type == "cuda" and any(self.trained) and self._spatial_featurizer() is not None
                         and all(d is not None for d, tr in zip(self._spatial_nets, self.trained) if tr) and self._spatial_served())
-        self._spatial_bufs = None  # (n, T, gathered states, gathered next states, SpatialFeed of the states, of the next states)
 
     # ---- configuration ----
     @staticmethod
@@ -172,7 +171,9 @@ class DeviceDQNTeamTrainer:
         return stack[2] if stack is not None and len(stack[0]) == 5 else None
 
     def _fill_team(self, tm, t: int, dims) -> None:
-        """One trained team's ``susnet_dqn_team``: its stack, the Adam constants and the flat buffers the kernels update."""
+        """One trained team's ``susnet_dqn_team``: its stack, the Adam constants and the flat buffers the kernels update (the team's Adam
+        state is brought back into them first, where the torch optimizer holds it)."""
+        self._state_to_flat(t)
         tm.enabled, tm.n_dims = 1, len(dims)
         for i, v in enumerate(dims):
             tm.dims[i] = v
@@ -195,19 +196,26 @@ class DeviceDQNTeamTrainer:
             net = self._policy_image(t)
             tm.packed = net.packed.data_ptr() if net is not None else None
         if ring is not None:
-            io.states, io.next_states = ring.states.data_ptr(), ring.next_states.data_ptr()
-            io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
-            io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
-            io.max_size = ring.max_size
-        if idx is not None:
-            io.indices, io.n = idx.data_ptr(), idx.numel()
+            self._fill_ring(io, ring, idx)
         return io
 
-    def _hip_served(self) -> bool:
-        io = self._io()
+    def _fill_ring(self, io, ring, idx=None) -> None:
+        """``ring`` and the sampled ``idx`` into any learner's io: the three structs name these fields alike (``DqnIO`` reads the raw states
+        in place as well)."""
+        if isinstance(io, L.DqnIO):
+            io.states, io.next_states = ring.states.data_ptr(), ring.next_states.data_ptr()
+        io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
+        io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
+        io.max_size = ring.max_size
+        if idx is not None:
+            io.indices, io.n = idx.data_ptr(), idx.numel()
+
+    def _served(self, io, workspace_bytes) -> bool:
+        """Whether the library takes ``io`` -- a learner's io without ring or indices -- at ``max_size = n = 1``: ``workspace_bytes`` is the
+        learner's own probe, which makes every check that reads no pointer."""
         io.max_size, io.n = 1, 1
         nbytes = C.c_uint64()
-        return self.env.lib.susnet_dqn_workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
+        return workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
 
     def _policy_image(self, team):
         p = self.policy
@@ -247,10 +255,7 @@ class DeviceDQNTeamTrainer:
         if widths != {T * F} or not 1 <= T <= L.WINDOW_MAX_T or T * F > L.MLP_MAX_F:
             return False  # the networks do not read windows of this featurizer's rows
         self.sequence_length = T
-        io = self._dense_io()
-        io.max_size, io.n = 1, 1
-        nbytes = C.c_uint64()
-        return self.env.lib.susnet_mlp_train_workspace_bytes(self.env._h, C.byref(io), C.byref(nbytes)) == 0
+        return self._served(self._dense_io(), self.env.lib.susnet_mlp_train_workspace_bytes)
 
     # ---- the spatial step's configuration ----
     def _spatial_featurizer(self):
@@ -306,10 +311,7 @@ class DeviceDQNTeamTrainer:
         for t, n_actions in enumerate((env.n_imposter_actions, env.n_crew_actions)):
             if self.trained[t] and spatial_feed_mismatch(env, self._featurizer, self._spatial_nets[t], n_actions) is not None:
                 return False  # the networks do not read this featurizer's tensors
-        io = self._spatial_io(1)
-        io.max_size, io.n = 1, 1
-        nbytes = C.c_uint64()
-        return env.lib.susnet_spatial_train_workspace_bytes(env._h, C.byref(io), C.byref(nbytes)) == 0
+        return self._served(self._spatial_io(1), env.lib.susnet_spatial_train_workspace_bytes)
 
     def uses_spatial(self, ring) -> bool:
         """Whether ``ring`` is trained on by ``susnet_spatial_train_step``: a ``spatial=True`` trainer of served ``SpatialDQN``s with a Global
@@ -349,8 +351,6 @@ class DeviceDQNTeamTrainer:
 
     def _hip_io(self, ring, idx) -> "L.DqnIO":
         """The complete ``susnet_dqn_io`` of one step on ``ring`` at ``idx``: Adam state in the flat buffers, workspace and losses allocated."""
-        for t in range(2):
-            self._state_to_flat(t)
         io = self._io(ring, idx)
         self._workspace_and_losses(io, self.env.lib.susnet_dqn_workspace_bytes)
         return io
@@ -363,6 +363,18 @@ class DeviceDQNTeamTrainer:
         self._sync_policy_version()
         return self._losses.clone()  # (a new tensor per step, as the torch path returns; enqueued, no host wait)
 
+    def _gather(self, ring, idx, make_rows):
+        """The batch's ``[n, T, S]`` windows and next windows, gathered into buffers that are reused while ``(n, T)`` stays; ``make_rows()``
+        builds what the step featurizes them into, once per pair of buffers.  Returns ``(windows, next windows, rows, next rows)``."""
+        n, T = int(idx.numel()), ring.trajectory_size
+        if self._gathered is None or self._gathered[:2] != (n, T):
+            self._gathered = (n, T, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
+                              torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
+                              make_rows(), make_rows())
+        torch.index_select(ring.states, 0, idx, out=self._gathered[2])
+        torch.index_select(ring.next_states, 0, idx, out=self._gathered[3])
+        return self._gathered[2:]
+
     def _dense_step(self, ring, idx):
         """Gather + featurize the batch's windows and next windows (``[n, T, S]``, as ``n * T`` rows) into reused buffers, then
         ``susnet_mlp_train_step`` on the ``[n][T * F]`` rows: nothing waits on the host (with ``env.check_errors`` the featurizer's row
@@ -370,22 +382,12 @@ class DeviceDQNTeamTrainer:
         from .env import ObsConfig
 
         env, n, T = self.env, int(idx.numel()), ring.trajectory_size
-        for t in range(2):
-            self._state_to_flat(t)
         io = self._dense_io()
         if n > 0:
-            if self._dense_bufs is None or self._dense_bufs[0] != n:
-                oc = ObsConfig("flat", self.components)
-                self._dense_bufs = (n, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
-                                    torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
-                                    env._make_obs(oc, 1, rows=n * T), env._make_obs(oc, 1, rows=n * T))
-            _, rows, next_rows, (spec, feat, _), (next_spec, next_feat, _) = self._dense_bufs
-            torch.index_select(ring.states, 0, idx, out=rows)
-            torch.index_select(ring.next_states, 0, idx, out=next_rows)
+            rows, next_rows, (spec, feat, _), (next_spec, next_feat, _) = self._gather(
+                ring, idx, lambda: env._make_obs(ObsConfig("flat", self.components), 1, rows=n * T))
             io.feat, io.next_feat = feat.data_ptr(), next_feat.data_ptr()
-        io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
-        io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
-        io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
+        self._fill_ring(io, ring, idx)
         self._workspace_and_losses(io, env.lib.susnet_mlp_train_workspace_bytes)
         with torch.cuda.device(self.device):
             if n > 0:
@@ -406,25 +408,15 @@ class DeviceDQNTeamTrainer:
         ``_spatial_step`` launches, and what a ``DeviceDQNSweepTrainer`` collects from every member before its one launch.  Nothing waits
         on the host (with ``env.check_errors`` the featurizer's row check is polled)."""
         env, n, T, A = self.env, int(idx.numel()), ring.trajectory_size, self.env.n_agents
-        for t in range(2):
-            self._state_to_flat(t)
         io = self._spatial_io(T)
         if n > 0:
-            if self._spatial_bufs is None or self._spatial_bufs[:2] != (n, T):
-                self._spatial_bufs = (n, T, torch.empty(n, *ring.states.shape[1:], dtype=ring.states.dtype, device=self.device),
-                                      torch.empty(n, *ring.next_states.shape[1:], dtype=ring.next_states.dtype, device=self.device),
-                                      SpatialFeed(env, self._featurizer, n, T), SpatialFeed(env, self._featurizer, n, T))
-            _, _, rows, next_rows, feed, next_feed = self._spatial_bufs
-            torch.index_select(ring.states, 0, idx, out=rows)
-            torch.index_select(ring.next_states, 0, idx, out=next_rows)
+            rows, next_rows, feed, next_feed = self._gather(ring, idx, lambda: SpatialFeed(env, self._featurizer, n, T))
             io.spatial, io.next_spatial = feed.spatial.data_ptr(), next_feed.spatial.data_ptr()
             io.non_spatial, io.next_non_spatial = feed.non_spatial.data_ptr(), next_feed.non_spatial.data_ptr()
             sp, ns = feed.strides(A)
             for d in range(3):
                 io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
-        io.actions, io.rewards = ring.actions.data_ptr(), ring.rewards.data_ptr()
-        io.dones, io.imposters = ring.dones.data_ptr(), ring.imposters.data_ptr()
-        io.max_size, io.indices, io.n = ring.max_size, idx.data_ptr(), n
+        self._fill_ring(io, ring, idx)
         drop = self._spatial_dropout()
         self._workspace_and_losses(io, env.lib.susnet_spatial_train_workspace_bytes if drop is None
                                    else env.lib.susnet_spatial_train_dropout_workspace_bytes)
@@ -646,48 +638,50 @@ class DeviceDQNSweepTrainer:
         if not (self.uses_hip(rings) and same_n):
             return torch.stack([t.train_step_on_indices(r, i) for t, r, i in zip(self.trainers, rings, idxs)])
         first = self.trainers[0]
-        if self._losses is None or self._losses.shape[0] != K:
-            self._losses = torch.zeros(K, 2, dtype=torch.float32, device=first.device)
-        row_bytes = self._losses.stride(0) * self._losses.element_size()
-        for lo, hi in sweep_chunks(K):
-            n = hi - lo
-            ios, envs = (L.DqnIO * n)(), (C.c_void_p * n)()
-            for j, k in enumerate(range(lo, hi)):
-                io = self.trainers[k]._hip_io(rings[k], idxs[k])
-                io.losses_out = self._losses.data_ptr() + k * row_bytes
-                ios[j], envs[j] = io, self.trainers[k].env._h
-            with torch.cuda.device(first.device):
-                L.check(first.env.lib.susnet_dqn_train_sweep(envs, ios, n, first.env._stream()))
+        lib, stream = first.env.lib, first.env._stream
+        out = self._chunked_step(L.DQN_MAX_LEARNERS, L.DqnIO, lambda k: (self.trainers[k]._hip_io(rings[k], idxs[k]), None),
+                                 lambda envs, ios, drops, n: lib.susnet_dqn_train_sweep(envs, ios, n, stream()))
         for t in self.trainers:
             t._sync_policy_version()
-        return self._losses.clone()
+        return out
 
     def _spatial_sweep_step(self, rings, idxs) -> torch.Tensor:
         """Every member's ``_spatial_prepare``, then one ``susnet_spatial_train_sweep`` per chunk of ``SPATIAL_SWEEP_MAX_LEARNERS``."""
-        K, first = len(self.trainers), self.trainers[0]
-        lib = first.env.lib
-        if self._losses is None or self._losses.shape[0] != K:
-            self._losses = torch.zeros(K, 2, dtype=torch.float32, device=first.device)
+        first = self.trainers[0]
+        lib, stream = first.env.lib, first.env._stream
         if self._table is None:
             nbytes = C.c_uint64()
             L.check(lib.susnet_spatial_train_sweep_table_bytes(L.SPATIAL_SWEEP_MAX_LEARNERS, C.byref(nbytes)))
             self._table = torch.empty(int(nbytes.value), dtype=torch.uint8, device=first.device)
+        table = self._table
+        return self._chunked_step(L.SPATIAL_SWEEP_MAX_LEARNERS, L.SpatialTrainIO, lambda k: self.trainers[k]._spatial_prepare(rings[k], idxs[k]),
+                                  lambda envs, ios, drops, n: lib.susnet_spatial_train_sweep(envs, ios, drops, n, table.data_ptr(), table.numel(),
+                                                                                             stream()))
+
+    def _chunked_step(self, limit: int, io_type, prepare, call) -> torch.Tensor:
+        """The members' steps in library calls of at most ``limit`` learners each.  ``prepare(k)``: member k's complete io and its two dropout
+        structs (or None) -- compatible(): all members pass them, or none does --; its losses go to row k of the trainer's ``[K, 2]``
+        tensor.  ``call(envs, ios, drops, n)``: the library call on one chunk.  A chunk's members that passed dropout structs advance their
+        ``dropout_steps`` after the checked call, as a member's own step does: a refused call uses up no offset."""
+        K, first = len(self.trainers), self.trainers[0]
+        if self._losses is None or self._losses.shape[0] != K:
+            self._losses = torch.zeros(K, 2, dtype=torch.float32, device=first.device)
         row_bytes = self._losses.stride(0) * self._losses.element_size()
-        for lo, hi in sweep_chunks(K, L.SPATIAL_SWEEP_MAX_LEARNERS):
+        for lo, hi in sweep_chunks(K, limit):
             n = hi - lo
-            ios, envs, drops = (L.SpatialTrainIO * n)(), (C.c_void_p * n)(), None
+            ios, envs, drops = (io_type * n)(), (C.c_void_p * n)(), None
             for j, k in enumerate(range(lo, hi)):
-                io, drop = self.trainers[k]._spatial_prepare(rings[k], idxs[k])
+                io, drop = prepare(k)
                 io.losses_out = self._losses.data_ptr() + k * row_bytes
                 ios[j], envs[j] = io, self.trainers[k].env._h
-                if drop is not None:  # (compatible(): all members pass dropout structs, or none does)
+                if drop is not None:
                     drops = drops if drops is not None else (L.RnnDropout * (2 * n))()
                     drops[2 * j], drops[2 * j + 1] = drop[0], drop[1]
             with torch.cuda.device(first.device):
-                L.check(lib.susnet_spatial_train_sweep(envs, ios, drops, n, self._table.data_ptr(), self._table.numel(), first.env._stream()))
+                L.check(call(envs, ios, drops, n))
             if drops is not None:
                 for k in range(lo, hi):
-                    self.trainers[k].dropout_steps += 1  # (after the check, as the member's own step: a refused call uses up no offset)
+                    self.trainers[k].dropout_steps += 1
         return self._losses.clone()
 
     @torch.no_grad()
