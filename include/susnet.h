@@ -753,6 +753,34 @@ typedef struct susnet_mlp_train_io {
 int susnet_mlp_train_workspace_bytes(const susnet_env *env, const susnet_mlp_train_io *io, uint64_t *bytes_out);
 int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream);
 
+/* A sweep's dense train step: what susnet_dqn_train_sweep does for the fused learner, for susnet_mlp_train_step.  The reference's sweeps
+ * (notebooks/experiment_mlp.ipynb: `for config in configs: run_experiment(**config)` over gamma on ImposterTrainingGround with four feature
+ * sets, [F, 256, 128, 64, 16, n_actions]; every MLP run at the default sequence_length 2) mostly lie off the compiled-in layouts, so each
+ * run's DQNTeamTrainer.train_step (src/train.py:50-149) is the dense step: at the reference's batch of 32 rows a chain of
+ * 1 + 2 x agents x enabled teams launches in which one workgroup works.  This call runs the steps of n_learners independent learners of
+ * one shape in the SAME launches, the learner being the grid's second dimension.
+ *   ios[k] is a complete susnet_mlp_train_io as susnet_mlp_train_step takes it -- its own feature rows, ring pointers, indices, gamma,
+ * Adam constants, parameters, losses_out and its own workspace of susnet_mlp_train_workspace_bytes(envs[k], &ios[k]) bytes -- and passes
+ * every check of that call (the same plan and pointer checks run per learner; a learner's own message is carried through behind
+ * "learner k: ").  The handles supply configuration only.
+ *   Served: 1 .. SUSNET_MLP_SWEEP_MAX_LEARNERS learners, each one served by the single call, that AGREE on what shapes the step: agent and
+ * imposter count, n, both teams' `enabled` and the enabled teams' n_dims / dims -- hence on the grid and on the workspace layout.  gamma,
+ * the Adam constants, max_size and every pointer may differ.  No two learners share `params` (of either team), `workspace` or
+ * `losses_out`.  A learner's record (the pointers that differ and gamma, 128 bytes) times 16 and one network description fit the 4 KB of a
+ * launch's arguments: the records travel by value, there is no table argument.  Anything else: SUSNET_E_INVALID before anything is
+ * launched, the message naming the entry point, the first offending learner and the field ("susnet_mlp_train_sweep: learner 1:
+ * team[0].dims differs from learner 0's ..").
+ *   After the call every learner's params, exp_avg, exp_avg_sq, step (of either team) and losses_out hold BIT FOR BIT what its own
+ * susnet_mlp_train_step(envs[k], &ios[k], stream) would have left: workgroup (g, k) walks the tiles workgroup g of that call walks, in the
+ * same order, into the same partial slot and pre-activation slice.  A learner whose (agent, team) list is empty skips that update
+ * (train.py:101) and keeps its step count, whatever the others do.
+ *   Launches: 1 to split the batches, then 2 per (agent, enabled team) update (gradient partials; the fused learner's sweep form of
+ * k_train_adam over the learners): 1 + 2 x agents x enabled teams per call whatever n_learners and the data are (n == 0: the first launch
+ * alone, which zeroes every learner's losses).  All on `stream`, no host synchronisation, no parallel branches, no atomics: a call can be
+ * captured as a hipGraph (after one eager call, which sets the gradient kernel's LDS ceiling). */
+#define SUSNET_MLP_SWEEP_MAX_LEARNERS 16
+int susnet_mlp_train_sweep(susnet_env *const *envs, const susnet_mlp_train_io *ios, int32_t n_learners, void *stream);
+
 /* The same train step once more -- DQNTeamTrainer.train_step (src/train.py:50-149) with exactly the semantics of susnet_dqn_train_step and
  * susnet_mlp_train_step above: agents in order, imposter team then crew team, gradients accumulating over the agents (one zero_grad per
  * call), y = r + gamma max_a target(s') with y = r on done rows, mean MSE, torch's single-tensor Adam with the step count on the device, no

@@ -16,6 +16,7 @@ ABI_VERSION = 8
 MAX_AGENTS, MAX_JOBS, MAX_GRID, N_METRICS, N_LIFETIME = 16, 16, 16, 13, 12
 DQN_MAX_LEARNERS = 16  # SUSNET_DQN_MAX_LEARNERS
 SPATIAL_SWEEP_MAX_LEARNERS = 16  # SUSNET_SPATIAL_SWEEP_MAX_LEARNERS: learners of one susnet_spatial_train_sweep call
+MLP_SWEEP_MAX_LEARNERS = 16  # SUSNET_MLP_SWEEP_MAX_LEARNERS: learners of one susnet_mlp_train_sweep call
 MLP_MAX_F, MLP_ROW_TILE, MLP_MAX_GRID = 1024, 64, 512  # SUSNET_MLP_*: susnet_mlp_forward's input width cap, rows per tile, grid cap
 MLP_MAX_HIDDEN, MLP_MAX_OUT = 256, 32
 WINDOW_MAX_T = 8  # susnet_window_push: states per window
@@ -47,7 +48,7 @@ EXPORTS = [
     "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_agent_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_window_push", "susnet_state_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
-    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_spatial_train_dropout_workspace_bytes", "susnet_spatial_train_step_dropout", "susnet_rnn_dropout_mask", "susnet_spatial_train_sweep_table_bytes", "susnet_spatial_train_sweep", "susnet_episode_stats_bytes", "susnet_episode_stats",
+    "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_mlp_train_sweep", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_spatial_train_dropout_workspace_bytes", "susnet_spatial_train_step_dropout", "susnet_rnn_dropout_mask", "susnet_spatial_train_sweep_table_bytes", "susnet_spatial_train_sweep", "susnet_episode_stats_bytes", "susnet_episode_stats",
 ]
 
 
@@ -293,6 +294,7 @@ def lib():
     L.susnet_dqn_train_sweep.argtypes = [P(C.c_void_p), P(DqnIO), C.c_int32, C.c_void_p]
     L.susnet_mlp_train_workspace_bytes.argtypes = [C.c_void_p, P(MlpTrainIO), P(C.c_uint64)]
     L.susnet_mlp_train_step.argtypes = [C.c_void_p, P(MlpTrainIO), C.c_void_p]
+    L.susnet_mlp_train_sweep.argtypes = [P(C.c_void_p), P(MlpTrainIO), C.c_int32, C.c_void_p]
     L.susnet_spatial_train_workspace_bytes.argtypes = [C.c_void_p, P(SpatialTrainIO), P(C.c_uint64)]
     L.susnet_spatial_train_step.argtypes = [C.c_void_p, P(SpatialTrainIO), C.c_void_p]
     L.susnet_spatial_train_dropout_workspace_bytes.argtypes = [C.c_void_p, P(SpatialTrainIO), P(C.c_uint64)]

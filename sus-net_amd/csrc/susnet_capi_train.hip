@@ -1,6 +1,6 @@
 // susnet_capi_train.hip -- the DQN learners of the C ABI: susnet_dqn_train_step and susnet_dqn_train_sweep (the fused learner on the
-// compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step (the dense learner on any served stack;
-// its gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step / susnet_spatial_train_sweep (the SpatialDQN learner and its sweep
+// compiled-in feature layouts; its kernels: susnet_train.h, compiled here) and susnet_mlp_train_step / susnet_mlp_train_sweep (the dense
+// learner on any served stack and its sweep form; their gradient kernels: inst_mlp_train.hip) and susnet_spatial_train_step / susnet_spatial_train_sweep (the SpatialDQN learner and its sweep
 // form; their kernels: inst_spatial_train.hip).  All
 // carve their workspace with tr_buffers and the single learners end every update with launch_adam (this unit's k_train_adam); the dense and
 // the SpatialDQN learner share their handle, Adam-constant, pointer and workspace checks (check_*, below).
@@ -90,7 +90,7 @@ static int plan_bytes(const char *entry, uint64_t *bytes_out, const FILL &plan) 
     *bytes_out = pl.bytes;
     return SUSNET_OK;
 }
-// The checks the two sweeps make alike, in the same words: the learner count ...
+// The checks the three sweeps make alike, in the same words: the learner count ...
 static int check_n_learners(const char *entry, int32_t n_learners, int32_t most) {
     if (n_learners < 1 || n_learners > most)
         return fail(SUSNET_E_INVALID, std::string(entry) + ": n_learners " + std::to_string(n_learners) + " outside 1 .. " + std::to_string(most));
@@ -99,7 +99,7 @@ static int check_n_learners(const char *entry, int32_t n_learners, int32_t most)
 static std::string sweep_learner(const char *entry, int k, const std::string &what) { // (how a sweep names the learner it refuses)
     return std::string(entry) + ": learner " + std::to_string(k) + ": " + what;
 }
-// ... and that no two learners write the same memory (susnet_dqn_io, susnet_spatial_train_io: the same field names)
+// ... and that no two learners write the same memory (susnet_dqn_io, susnet_mlp_train_io, susnet_spatial_train_io: the same field names)
 template <class IO>
 static int check_learners_apart(const char *entry, const IO *ios, int K) {
     for (int k = 1; k < K; k++)
@@ -357,9 +357,8 @@ extern "C" int susnet_mlp_train_workspace_bytes(const susnet_env *env, const sus
     return plan_bytes<MlpTrainPlan>("susnet_mlp_train_workspace_bytes", bytes_out, [&](MlpTrainPlan &pl) { return mlp_train_plan(env, io, pl); });
 }
 
-// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
-extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
-    MlpTrainPlan pl;
+// the checks of one call, shared with the sweep, which asks them of every learner: the plan, the workspace and every pointer
+static int mlp_train_check(const susnet_env *env, const susnet_mlp_train_io *io, MlpTrainPlan &pl) {
     if (int rc = mlp_train_plan(env, io, pl)) return rc;
     const Refuse bad{env, "susnet_mlp_train_step"};
     if (int rc = check_workspace(bad, io->workspace, io->workspace_bytes, pl.bytes, "susnet_mlp_train_workspace_bytes")) return rc;
@@ -368,7 +367,12 @@ extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io 
         if (!io->feat || misaligned(io->feat)) return bad("feat is NULL or not 4-byte aligned");
         if (!io->next_feat || misaligned(io->next_feat)) return bad("next_feat is NULL or not 4-byte aligned");
     }
-    if (int rc = check_team_ptrs(bad, io->team)) return rc;
+    return check_team_ptrs(bad, io->team);
+}
+// everything is checked here, before the first launch; the handle gives the configuration (A, n_imposters) and the error conventions only
+extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io *io, void *stream) {
+    MlpTrainPlan pl;
+    if (int rc = mlp_train_check(env, io, pl)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const TrBuffers w = tr_buffers(io->workspace, pl);
     float *zsave = reinterpret_cast<float *>(static_cast<char *>(io->workspace) + pl.off_z);
@@ -383,6 +387,75 @@ extern "C" int susnet_mlp_train_step(susnet_env *env, const susnet_mlp_train_io 
             HIP_TRY(mlp_train_grad_launch(b, pl.net[tm], T.params, T.target_params, w.lists, w.counts, agent, tm, (float)io->gamma, w.partial, zsave,
                                           T.step, (int)pl.G, st));
             HIP_TRY(launch_adam(pl.net[tm], w, agent, tm, (int)pl.G, T, io->losses_out, st));
+        }
+    return SUSNET_OK;
+}
+
+// ---- a sweep's dense train step: K learners in the launches of one (susnet_mlp_train.h, k_mlp_train_sweep_*) ----
+static_assert(kMtSweepMaxLearners <= kTrMaxLearners, "the reduce + Adam launch is k_train_sweep_adam: its table carries the learners");
+
+extern "C" int susnet_mlp_train_sweep(susnet_env *const *envs, const susnet_mlp_train_io *ios, int32_t n_learners, void *stream) {
+    if (!envs || !ios) return fail(SUSNET_E_INVALID, "susnet_mlp_train_sweep: null envs / ios");
+    if (int rc = check_n_learners("susnet_mlp_train_sweep", n_learners, SUSNET_MLP_SWEEP_MAX_LEARNERS)) return rc;
+    const int K = n_learners;
+    const auto who = [](int k, const std::string &what) { return sweep_learner("susnet_mlp_train_sweep", k, what); };
+    std::vector<MlpTrainPlan> pls((size_t)K);
+    for (int k = 0; k < K; k++) { // each learner passes susnet_mlp_train_step's checks ...
+        if (!envs[k]) return fail(SUSNET_E_INVALID, who(k, "null handle"));
+        if (int rc = mlp_train_check(envs[k], &ios[k], pls[(size_t)k])) return fail(rc, who(k, g_err));
+    }
+    const susnet_env *e0 = envs[0];
+    const susnet_mlp_train_io &i0 = ios[0];
+    const MlpTrainPlan &pl = pls[0];
+    for (int k = 1; k < K; k++) { // ... and all agree on what shapes the step
+        const susnet_env *e = envs[k];
+        const susnet_mlp_train_io &io = ios[k];
+        std::string field;
+        if (e->c.A != e0->c.A || e->c.n_imp != e0->c.n_imp) field = "agent count";
+        else if (io.n != i0.n) field = "n";
+        for (int tm = 0; tm < 2 && field.empty(); tm++)
+            if ((io.team[tm].enabled != 0) != (i0.team[tm].enabled != 0)) field = "team[" + std::to_string(tm) + "].enabled";
+        for (int tm = 0; tm < 2 && field.empty(); tm++) {
+            if (!i0.team[tm].enabled) continue;
+            if (io.team[tm].n_dims != i0.team[tm].n_dims) field = "team[" + std::to_string(tm) + "].n_dims";
+            else if (memcmp(io.team[tm].dims, i0.team[tm].dims, sizeof(int32_t) * (size_t)i0.team[tm].n_dims) != 0) field = "team[" + std::to_string(tm) + "].dims";
+        }
+        if (!field.empty()) return fail(SUSNET_E_INVALID, who(k, field + " differs from learner 0's (a sweep runs learners of one shape)"));
+        if (pls[(size_t)k].bytes != pl.bytes || pls[(size_t)k].G != pl.G || pls[(size_t)k].off_z != pl.off_z)
+            return fail(SUSNET_E_INVALID, who(k, "workspace plan differs from learner 0's"));
+    }
+    if (int rc = check_learners_apart("susnet_mlp_train_sweep", ios, K)) return rc;
+    // each learner's own: the select launch's record, and per team the gradient launch's and the reduce + Adam launch's
+    MlpSweepSelTable sel{};
+    MlpSweepTable grad[2] = {};
+    TrainTable adam[2] = {};
+    TrainNet anet[2] = {};
+    for (int tm = 0; tm < 2; tm++) anet[tm].P = pl.net[tm].P, anet[tm].Pp = pl.net[tm].Pp;
+    for (int k = 0; k < K; k++) {
+        const susnet_mlp_train_io &io = ios[k];
+        const TrBuffers w = tr_buffers(io.workspace, pl);
+        float *zsave = reinterpret_cast<float *>(static_cast<char *>(io.workspace) + pl.off_z);
+        sel.l[k] = MlpSweepSelLearner{io.imposters, io.indices, io.max_size, w.lists, w.counts, w.gacc[0], w.gacc[1], io.losses_out};
+        for (int tm = 0; tm < 2; tm++) {
+            const susnet_dqn_team &T = io.team[tm];
+            if (!T.enabled) continue;
+            grad[tm].l[k] = MlpSweepLearner{io.feat, io.next_feat, io.actions, io.rewards, io.dones, io.imposters, io.indices, io.max_size, T.params,
+                                            T.target_params, w.lists, w.counts, w.partial, zsave, T.step, (float)io.gamma, 0};
+            adam[tm].l[k] = TrainLearner{TrainRing{}, T.params, T.target_params, T.exp_avg, T.exp_avg_sq, T.step, w.lists, w.counts, w.gacc[tm], w.partial,
+                                         io.losses_out, nullptr, T.lr, T.beta1, T.beta2, T.eps, (float)io.gamma, 0};
+        }
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int A = (int)e0->c.A, n_imp = (int)e0->c.n_imp;
+    HIP_TRY(mlp_train_sweep_select_launch(sel, K, i0.n, A, n_imp, pl.net[0].P, pl.net[1].P, st));
+    if (i0.n == 0) return SUSNET_OK;
+    for (int agent = 0; agent < A; agent++)
+        for (int tm = 0; tm < 2; tm++) { // imposter team, then crew team (train.py:91-99)
+            if (!i0.team[tm].enabled) continue;
+            HIP_TRY(mlp_train_sweep_grad_launch(grad[tm], K, pl.net[tm], i0.n, A, n_imp, agent, tm, (int)pl.G, st));
+            hipLaunchKernelGGL(k_train_sweep_adam, dim3((unsigned)((pl.net[tm].P + 1 + 255) / 256), (unsigned)K), dim3(256), 0, st, adam[tm], anet[tm], agent, tm,
+                               (int)pl.G);
+            HIP_TRY(hipGetLastError());
         }
     return SUSNET_OK;
 }

@@ -21,6 +21,15 @@
 //                         - the layer loops are unrolled over the 7 possible layers with guards (the stack travels as a kernel argument).
 //   k_train_adam        susnet_train.h's, as it is (susnet_capi_train.hip launches it): sums the partials in workgroup order, accumulates, Adam.
 // Grid: G = min(kMtMaxGrid, tiles of n, kMtMaxPartialBytes / (4 Pp)) workgroups, at least 1: the partials stay at or below 64 MiB.
+//
+// A sweep (susnet_mlp_train_sweep): K learners of one shape in the launches of one, the learner is blockIdx.y.  k_mlp_train_sweep_select
+// calls the same tr_select and k_mlp_train_sweep_grad includes the same body text (susnet_mlp_train_grad_body.h) as the single learner's
+// kernels, so workgroup (g, k) does what workgroup g of learner k's own call does -- the same tiles g, g + G, .., the same partial slot
+// and pre-activation slice, the same read-modify-write order -- and a learner's results are bitwise those of susnet_mlp_train_step.  A
+// learner whose (agent, team) list is empty returns at once, whatever the others do, and its step count stays.  What the learners agree
+// on travels once (the team's MlpTrainNet, n, A, n_imp; G is the grid); what differs is a per-learner record in a table passed BY VALUE
+// as a kernel argument (no device table, no host copy: the call stays capturable).  The reduce + Adam launch is susnet_train.h's
+// k_train_sweep_adam as it is: it reads P and Pp of its net argument only.  Learners never touch one another's memory.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,10 +65,45 @@ struct MlpTrainBatch {
     int32_t A, n_imp;
 };
 
+// ---- the sweep's tables: one entry per learner, passed by value ----
+constexpr int kMtSweepMaxLearners = SUSNET_MLP_SWEEP_MAX_LEARNERS;
+struct MlpSweepSelLearner { // k_mlp_train_sweep_select
+    const int16_t *imposters;
+    const int64_t *idx;
+    int64_t max_size;
+    int32_t *lists, *counts;
+    float *gacc0, *gacc1, *losses;
+};
+struct MlpSweepSelTable {
+    MlpSweepSelLearner l[kMtSweepMaxLearners];
+};
+struct MlpSweepLearner { // one team of one learner: k_mlp_train_sweep_grad -- the MlpTrainBatch fields that differ, then the kernel's own arguments
+    const float *feat, *next_feat;
+    const int64_t *actions;
+    const float *rewards;
+    const uint8_t *dones;
+    const int16_t *imposters;
+    const int64_t *idx;
+    int64_t max_size;
+    const float *prm, *tgt;
+    const int32_t *lists, *counts;
+    float *partial, *zsave, *step;
+    float gamma;
+    int32_t pad_;
+};
+struct MlpSweepTable {
+    MlpSweepLearner l[kMtSweepMaxLearners];
+};
+static_assert(sizeof(MlpSweepTable) + sizeof(MlpTrainNet) + 64 <= 4096 && sizeof(MlpSweepSelTable) + 64 <= 4096, "the tables are kernel arguments: 4 KB");
+
 // the launches (inst_mlp_train.hip); arguments validated by the caller
 hipError_t mlp_train_select_launch(const MlpTrainBatch &b, int32_t *lists, int32_t *counts, float *gacc0, int P0, float *gacc1, int P1, float *losses,
                                    hipStream_t st);
 hipError_t mlp_train_grad_launch(const MlpTrainBatch &b, const MlpTrainNet &net, const float *prm, const float *tgt, const int32_t *lists,
                                  const int32_t *counts, int agent, int team, float gamma, float *partial, float *zsave, float *step, int G, hipStream_t st);
+// the sweep forms: grid (1, K) and (G, K); n, A, n_imp and `net` are the learners' common ones
+hipError_t mlp_train_sweep_select_launch(const MlpSweepSelTable &tab, int K, int64_t n, int A, int n_imp, int P0, int P1, hipStream_t st);
+hipError_t mlp_train_sweep_grad_launch(const MlpSweepTable &tab, int K, const MlpTrainNet &net, int64_t n, int A, int n_imp, int agent, int team, int G,
+                                       hipStream_t st);
 
 } // namespace susnet

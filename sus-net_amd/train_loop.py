@@ -216,7 +216,8 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
     models and generator.  Per block every member first does what ``train()`` does before the train step -- its saves, its target sync,
     its ``collect`` at its own epsilon, its ``EpisodeLog.update`` -- then ONE ``DeviceDQNSweepTrainer.train_step`` steps all members
     (``susnet_dqn_train_sweep``, or for ``WindowedPolicyRollout(kernels=True)`` members with ``spatial=True`` trainers
-    ``susnet_spatial_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
+    ``susnet_spatial_train_sweep``, or for members with ``dense=True`` trainers off the fused learner's ground
+    ``susnet_mlp_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
     ``batch_size``, ``num_saves``, ``target_update_interval``) is shared.  Each member's metrics, losses, checkpoints and ``EpisodeLog``
     (returned, in member order) are what ``train()`` alone produces for it: its step is bitwise its own, and its random streams are
     its own (give every member a generator: without one the draws come from the device's global generator, in member order)."""
@@ -336,7 +337,9 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
     built ``featurizer=..., spatial=True``; ``components`` is not read, and ``config.json`` also names the learner the run takes
     (``train_step``) and the dropout seed.  What the two callers do differently, on purpose:
     * flat ``run_experiment`` acts and trains through the dense kernels wherever the fused ones do not serve, on windows of T states too;
-      a flat sweep member is built for the fused kernels, one state (``dense_train`` alone sends its trainer to the dense step);
+      a flat sweep member is built for the fused kernels, one state (``dense_train`` alone sends its trainer to the dense step) -- unless
+      ``dense_train`` is set and the member reads windows of T > 1 states or the fused kernels do not serve one of its acting models: then
+      it is built as ``run_experiment``'s run is, and its ``config.json`` also names the learner it takes (``train_step``);
     * a sweep member's ``config.json`` carries its ``seed``, and its ``generator`` is made here from that seed (``run_experiment`` passes
       its caller's, or None: the device's global generator)."""
     from .features import GlobalFeaturizer
@@ -349,9 +352,13 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
         if not isinstance(imposter_model, MLP) or not (crew_model is None or isinstance(crew_model, MLP)):
             raise ValueError(f"{who}: served are reference MLPs (a crew model of None acts randomly)")
         # (at sequence_length > 1 a network that is not dense-served is refused here, naming sequence_length and the input width T * F it needs)
+        as_run = not sweep or (s.dense_train and T > 1)  # built as run_experiment's run: acting and training through the dense kernels
         policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True,
-                               **({} if sweep else {"dense": True, "sequence_length": T}))
-        learner = {"dense": s.dense_train} if sweep else {"dense": s.dense_train or T > 1, "sequence_length": T if T > 1 else None}
+                               **({"dense": True, "sequence_length": T} if as_run else {}))
+        if not as_run and s.dense_train and (policy.fused_imposter is None or (crew_model is not None and policy.fused_crew is None)):
+            as_run = True  # a dense_train sweep member whose acting models the fused kernels do not serve: collect would refuse it
+            policy = PolicyRollout(env, imposter_model, crew_model, components=components, mask_dead=True, dense=True, sequence_length=T)
+        learner = {"dense": s.dense_train or T > 1, "sequence_length": T if T > 1 else None} if as_run else {"dense": s.dense_train}
         featurizer_type = None
     else:
         if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8 or not env.auto_reset:
@@ -373,6 +380,10 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
         config["seed"] = s.seed
         generator = torch.Generator(device=env.device)
         generator.manual_seed(int(s.seed))
+    if featurizer is None and sweep and as_run:
+        # which learner the member's own train steps take (run_sweep names the sweep call instead where that serves the training members)
+        own = "susnet_dqn_train_step" if trainer.uses_hip(ring) else "susnet_mlp_train_step" if trainer.uses_dense(ring) else "torch_train_step"
+        config["train_step"] = own if any(trainer.trained) else None
     if featurizer is not None:
         # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
         config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
@@ -476,16 +487,21 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     ``experiment_base_dir/<name or index>/<timestamp>/`` with ``config.json`` (carrying the variant's values and ``seed``), the
     checkpoints and ``metrics.json`` as ``run_experiment`` writes them, so plotting over one directory per gamma keeps working.  Returns
     the members' metric handlers.  How a member differs from ``run_experiment``'s run:
-    * without ``featurizer_factory`` the sweep is MLP-only as it was (a ``SpatialDQN`` is a ``ValueError`` there) and a window of one state
-      is served, through the fused kernels: ``sequence_length=1``, and
-      ``dense_train`` only sends members whose step the sweep call does not serve to their dense steps, one after another;
+    * without ``featurizer_factory`` the sweep is MLP-only as it was (a ``SpatialDQN`` is a ``ValueError`` there).  Without ``dense_train``
+      a window of one state is served, through the fused kernels: ``sequence_length=1``.  With ``dense_train=True`` a member on a
+      compiled-in layout at ``sequence_length=1`` is built and swept as before (``susnet_dqn_train_sweep``); a member that reads windows
+      of ``sequence_length`` > 1 states, or one of whose acting models the fused kernels do not serve (another game, feature set or
+      layer stack), is built as ``run_experiment`` builds its run -- ``PolicyRollout(dense=True, sequence_length=T)``, a trainer
+      ``dense=True, sequence_length=T``, a ring of ``trajectory_size=T``, the same refusal of stacks the dense step does not serve at
+      T > 1 -- and its ``config.json`` carries ``train_step``: ``susnet_mlp_train_sweep`` -- one call per chunk of
+      ``MLP_SWEEP_MAX_LEARNERS`` -- where that serves the training members, else the member's own learner;
     * with ``featurizer_factory`` (``SpatialDQN`` members, ``sequence_length`` 1 .. ``SPATIAL_MAX_T``) there is no dropout seed
       (``config.json`` says None): members with dropout between their RNN layers take ``torch_train_step`` one after another (a
       ``DeviceDQNSweepTrainer`` over trainers built with ``rnn_dropout_seed`` does sweep them);
     * ``train_step`` in a ``SpatialDQN`` member's ``config.json`` is ``susnet_spatial_train_sweep`` -- one call per chunk of
       ``SPATIAL_SWEEP_MAX_LEARNERS`` -- where that serves the training members, else the member's own learner."""
     components, variants, spatial = list(components), check_variants(variants), featurizer_factory is not None
-    if not spatial and sequence_length != 1:
+    if not spatial and not dense_train and sequence_length != 1:
         raise ValueError("run_sweep: a window of one state is served (sequence_length=1): the Q-network kernel and "
                          "susnet_dqn_train_sweep read one state")
     sequence_length = int(sequence_length)
@@ -507,6 +523,12 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
         for m in members:
             own = m.config.pop("train_step")  # (put back as the last key, behind seed and rnn_dropout_seed, where it has always stood)
             m.config["train_step"] = "susnet_spatial_train_sweep" if swept and own is not None else own
+    elif any("train_step" in m.config for m in members):  # (dense_train members built as run_experiment's run: _build_member)
+        training = [m for m in members if any(m.trainer.trained)]
+        swept = bool(training) and DeviceDQNSweepTrainer([m.trainer for m in training]).uses_dense([m.ring for m in training])
+        for m in members:
+            if m.config.get("train_step") is not None and swept:
+                m.config["train_step"] = "susnet_mlp_train_sweep"
     _start(members, shared)
     train_sweep([m[:8] for m in members], num_steps, **shared.train_keywords())
     for m in members:

@@ -11,6 +11,7 @@ from a ``DeviceReplayBuffer`` (``ReplayBuffer.sample``, src/replay_memory.py:75-
   gathered and featurized as ``n * T`` rows (the FLAT featurizer kernel) into reused buffers -- ``[n * T, F]`` IS the ``[n][T * F]``
   layout the step reads --, then one call: the same launches per update, no host synchronisation.
   There is no packed image: a ``PolicyRollout(dense=True)`` reads the parameters in place and follows the step without a refresh.
+  A ``DeviceDQNSweepTrainer`` over such trainers of one shape takes their steps in ONE call (``susnet_mlp_train_sweep``).
 * spatial HIP path (``susnet_spatial_train_step``, csrc/susnet_spatial_train.h; opt-in: ``DeviceDQNTeamTrainer(..., spatial=True)``):
   reference ``SpatialDQN``s (CNN, tanh ``nn.RNN``, PReLU head) within ``susnet_spatial_forward``'s bounds on a ``GlobalFeaturizer`` or
   ``PerspectiveFeaturizer``, one imposter, no dropout between RNN layers.  The batch's windows and next windows are gathered and featurized
@@ -375,10 +376,11 @@ class DeviceDQNTeamTrainer:
         torch.index_select(ring.next_states, 0, idx, out=self._gathered[3])
         return self._gathered[2:]
 
-    def _dense_step(self, ring, idx):
-        """Gather + featurize the batch's windows and next windows (``[n, T, S]``, as ``n * T`` rows) into reused buffers, then
-        ``susnet_mlp_train_step`` on the ``[n][T * F]`` rows: nothing waits on the host (with ``env.check_errors`` the featurizer's row
-        check is polled, as ``env.featurize`` does)."""
+    def _dense_prepare(self, ring, idx) -> "L.MlpTrainIO":
+        """The dense step up to its launch: gather + featurize the batch's windows and next windows (``[n, T, S]``, as ``n * T`` rows) into
+        reused buffers and fill the ``susnet_mlp_train_io`` on the ``[n][T * F]`` rows (workspace and losses allocated).  What
+        ``_dense_step`` launches, and what a ``DeviceDQNSweepTrainer`` collects from every member before its one launch.  Nothing waits on
+        the host (with ``env.check_errors`` the featurizer's row check is polled, as ``env.featurize`` does)."""
         from .env import ObsConfig
 
         env, n, T = self.env, int(idx.numel()), ring.trajectory_size
@@ -396,9 +398,20 @@ class DeviceDQNTeamTrainer:
                 L.check(env.lib.susnet_featurize(env._h, next_rows.data_ptr(), dt, n * T, C.byref(next_spec), env._stream()))
                 if env.check_errors:
                     env.poll_errors()
-            L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
+        return io
+
+    def _dense_finish(self) -> None:
+        """What follows a dense step's launch (the member's own, or a sweep's): a fused image of the trained weights is re-packed."""
         if self.policy is not None and any(self._policy_image(t) is not None for t in range(2)):
             self.policy.refresh_weights(force=True)  # (a fused image of these weights: only where the fused step was switched off by hand)
+
+    def _dense_step(self, ring, idx):
+        """``_dense_prepare``, then ``susnet_mlp_train_step`` on the rows where they lie."""
+        env = self.env
+        io = self._dense_prepare(ring, idx)
+        with torch.cuda.device(self.device):
+            L.check(env.lib.susnet_mlp_train_step(env._h, C.byref(io), env._stream()))
+        self._dense_finish()
         return self._losses.clone()
 
     def _spatial_prepare(self, ring, idx):
@@ -562,8 +575,12 @@ class DeviceDQNSweepTrainer:
     have one shape and the index counts agree, every member prepares its own batch (gather, featurize: ``_spatial_prepare``) and the step
     is ONE ``susnet_spatial_train_sweep`` call per chunk of at most ``SPATIAL_SWEEP_MAX_LEARNERS`` members, again bitwise each member's
     own step, dropout masks included (a member's ``dropout_steps`` advances as its own steps would advance it).  The trainer owns the
-    call's table buffer and the ``[K, 2]`` losses.  Otherwise the members' own ``train_step_on_indices`` run one after another (the
-    torch path for CPU tensors and anything else unserved)."""
+    call's table buffer and the ``[K, 2]`` losses.  When every member takes the dense step (``DeviceDQNTeamTrainer(dense=True)`` over
+    served MLP stacks: ``uses_dense``) on windows of one length, with one shape and equal index counts, every member prepares its own
+    batch (gather, featurize: ``_dense_prepare``) and the step is ONE ``susnet_mlp_train_sweep`` call per chunk of at most
+    ``MLP_SWEEP_MAX_LEARNERS`` members, bitwise each member's own step; a member's fused image of the trained weights, where one
+    exists, is re-packed behind it as the member's own step does.  The order is: fused sweep, spatial sweep, dense sweep.  Otherwise
+    the members' own ``train_step_on_indices`` run one after another (the torch path for CPU tensors and anything else unserved)."""
 
     def __init__(self, trainers: Sequence[DeviceDQNTeamTrainer]):
         self.trainers = list(trainers)
@@ -590,11 +607,21 @@ class DeviceDQNSweepTrainer:
                 for d, tr in zip(t._spatial_nets, t.trained)]
         return t._spatial_featurizer(), nets, t._spatial_dropout() is None
 
+    @staticmethod
+    def _dense_shape(t: DeviceDQNTeamTrainer):
+        """What ``susnet_mlp_train_sweep`` requires its learners to agree on beyond the env, of a ``dense=True`` trainer: each trained
+        team's layer stack ``[T * F, h.., n_actions]`` and the window length T.  None otherwise."""
+        if not getattr(t, "dense", False):
+            return None
+        return t._dense_dims, t.sequence_length
+
     def compatible(self) -> bool:
-        """Whether the members agree on what shapes the step (what ``susnet_dqn_train_sweep`` and ``susnet_spatial_train_sweep`` require):
-        device, agent and imposter count, raw row size, grid, components, which teams train and their layer dims; of ``spatial=True``
-        members also the featurizer's layout, the networks and which teams are under a dropout mask (``_spatial_shape``).  gamma,
-        learning rate, weights, and the dropout probability and seed may differ."""
+        """Whether the members agree on what shapes the step (what ``susnet_dqn_train_sweep``, ``susnet_spatial_train_sweep`` and
+        ``susnet_mlp_train_sweep`` require): device, agent and imposter count, raw row size, grid, components, which teams train and their
+        layer dims; of ``spatial=True`` members also the featurizer's layout, the networks and which teams are under a dropout mask
+        (``_spatial_shape``); of two ``dense=True`` members also the dense stacks and the window length (``_dense_shape``; a member
+        without ``dense`` never takes the dense step, so it constrains nothing there).  gamma, learning rate, weights, and the dropout
+        probability and seed may differ."""
         a = self.trainers[0]
         for b in self.trainers[1:]:
             ea, eb = a.env, b.env
@@ -602,6 +629,9 @@ class DeviceDQNSweepTrainer:
                     or eb.flattened_state_size != ea.flattened_state_size or eb.grid.shape != ea.grid.shape or not (eb.grid == ea.grid).all()
                     or b.components != a.components or b.trained != a.trained or b._dims != a._dims
                     or self._spatial_shape(b) != self._spatial_shape(a)):
+                return False
+            da, db = self._dense_shape(a), self._dense_shape(b)
+            if da is not None and db is not None and da != db:
                 return False
         return True
 
@@ -613,6 +643,12 @@ class DeviceDQNSweepTrainer:
         """Whether a step on ``rings`` (one per member) is served by ``susnet_spatial_train_sweep`` for ALL members: every member takes
         the spatial step on its ring, the rings' windows have one length, and the members have one shape (else: the per-member loop)."""
         return (len(rings) == len(self.trainers) and all(t.uses_spatial(r) for t, r in zip(self.trainers, rings))
+                and len(set(r.trajectory_size for r in rings)) == 1 and self.compatible())
+
+    def uses_dense(self, rings) -> bool:
+        """Whether a step on ``rings`` (one per member) is served by ``susnet_mlp_train_sweep`` for ALL members: every member takes the
+        dense step on its ring, the rings' windows have one length, and the members have one shape (else: the per-member loop)."""
+        return (len(rings) == len(self.trainers) and all(t.uses_dense(r) for t, r in zip(self.trainers, rings))
                 and len(set(r.trajectory_size for r in rings)) == 1 and self.compatible())
 
     def train_step(self, rings, batch_size: int, generators=None) -> torch.Tensor:
@@ -635,6 +671,8 @@ class DeviceDQNSweepTrainer:
         same_n = len(set(int(i.numel()) for i in idxs)) == 1
         if same_n and not self.uses_hip(rings) and self.uses_spatial(rings):
             return self._spatial_sweep_step(rings, idxs)
+        if same_n and not self.uses_hip(rings) and self.uses_dense(rings):
+            return self._dense_sweep_step(rings, idxs)
         if not (self.uses_hip(rings) and same_n):
             return torch.stack([t.train_step_on_indices(r, i) for t, r, i in zip(self.trainers, rings, idxs)])
         first = self.trainers[0]
@@ -657,6 +695,17 @@ class DeviceDQNSweepTrainer:
         return self._chunked_step(L.SPATIAL_SWEEP_MAX_LEARNERS, L.SpatialTrainIO, lambda k: self.trainers[k]._spatial_prepare(rings[k], idxs[k]),
                                   lambda envs, ios, drops, n: lib.susnet_spatial_train_sweep(envs, ios, drops, n, table.data_ptr(), table.numel(),
                                                                                              stream()))
+
+    def _dense_sweep_step(self, rings, idxs) -> torch.Tensor:
+        """Every member's ``_dense_prepare``, then one ``susnet_mlp_train_sweep`` per chunk of ``MLP_SWEEP_MAX_LEARNERS``; behind it every
+        member's ``_dense_finish``, as its own step ends."""
+        first = self.trainers[0]
+        lib, stream = first.env.lib, first.env._stream
+        out = self._chunked_step(L.MLP_SWEEP_MAX_LEARNERS, L.MlpTrainIO, lambda k: (self.trainers[k]._dense_prepare(rings[k], idxs[k]), None),
+                                 lambda envs, ios, drops, n: lib.susnet_mlp_train_sweep(envs, ios, n, stream()))
+        for t in self.trainers:
+            t._dense_finish()
+        return out
 
     def _chunked_step(self, limit: int, io_type, prepare, call) -> torch.Tensor:
         """The members' steps in library calls of at most ``limit`` learners each.  ``prepare(k)``: member k's complete io and its two dropout
