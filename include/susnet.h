@@ -16,6 +16,7 @@
  *   susnet_qnet_*          MLP.forward on the flat features src/models/dqn.py:72-108, 322-329
  *   susnet_mlp_forward     MLP.forward of any served layer stack on caller-supplied feature rows  src/models/dqn.py:72-108, 322-329
  *   susnet_spatial_forward SpatialDQN.forward (eval mode) on the planes / perspective features     src/models/dqn.py:141-301
+ *   susnet_spatial_forward_dropout  the same in training mode: nn.RNN's dropout between layers, as the trainer's agents act  src/train.py:104, 355-381
  *   susnet_window_push     the acting loop's state window, one tick on (as feature rows)  src/train.py:318-322, 388-389, 441-445
  *   susnet_state_window_push  the acting loop's RAW state window [B][T][S] uint8, one tick on, in place  src/train.py:388-389, 441-445
  *   susnet_policy_step     argmax per team + env.step        src/visualize.py:547-582
@@ -480,7 +481,8 @@ int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void *stream);
  *        the last layer's hidden state at t = T - 1 (dqn.py:298-299): q_out [n][dims[n_dims-1]].
  *   The PERSPECTIVE featurizer's buffers are served in place (spatial [B][T][A][C][N][N]: strides T*A*C*N*N, C*N*N, A*C*N*N), and so are the
  * GLOBAL featurizer's shared planes ([B][T][C][N][N] with an agent stride of 0: the image's convolution is then recomputed per agent).
- *   EVAL-mode semantics: there is no dropout in the kernels (nn.RNN's dropout between layers acts in training mode only).
+ *   EVAL-mode semantics: there is no dropout in these kernels (nn.RNN's dropout between layers acts in training mode only);
+ * susnet_spatial_forward_dropout, declared with the dropout entry points below, is the training-mode form of this call.
  *   Parameters are read where torch keeps them, as susnet_mlp_forward reads them: conv_weight[l] [conv_out[l]][C_in][k][k], w_ih[l]
  * [rnn_hidden][R or rnn_hidden], w_hh[l] [rnn_hidden][rnn_hidden], the head's weight[l] [dims[l+1]][dims[l]], all row-major and only 4-byte
  * aligned; no packed image, no host step: after an in-place optimizer step the next launch reads the new values.
@@ -853,8 +855,9 @@ int susnet_spatial_train_workspace_bytes(const susnet_env *env, const susnet_spa
 int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io, void *stream);
 
 /* Dropout between the layers of the SpatialDQN's nn.RNN in the TRAIN STEP (training mode, rnn_dropout = p > 0, rnn_layers = L > 1), opt-in:
- * the three entry points below.  susnet_spatial_train_step and its kernels are as they were (no dropout); susnet_spatial_forward stays the
- * EVAL-mode forward (no dropout form of it exists: a model acts in eval mode on the device).
+ * the entry points below.  susnet_spatial_train_step and its kernels are as they were (no dropout); susnet_spatial_forward stays the
+ * EVAL-mode forward, and susnet_spatial_forward_dropout (further down) is its training-mode form: the reference never calls eval(), so
+ * its agents ACT under this dropout too (train.py:104, 355-381).
  *   What torch computes (nn.RNN, batch_first, training): the output sequence of every layer l < L - 1 is multiplied elementwise by a mask m_l of
  * values 0 (probability p) and 1 / (1 - p), and the product feeds layer l + 1 ONLY: layer l's own recurrence W_hh h_l[t-1] reads the
  * undropped h_l, and the last layer's output -- what the head reads -- is not dropped.  torch's mask stream cannot be reproduced on the
@@ -884,9 +887,33 @@ int susnet_spatial_train_step(susnet_env *env, const susnet_spatial_train_io *io
  * serve the dropout step).  With every p of the enabled teams 0 the call runs susnet_spatial_train_step's kernels.
  * susnet_rnn_dropout_mask: the multipliers out[layers - 1][n][T][H] (device float32, 4-byte aligned) that the call above uses for the
  * same `drop`, `net` (p = drop->p[net]) and `agent`, rows row_base .. row_base + n - 1.  Served: net 0 / 1, agent 0 .. 4095, layers 2 .. 4,
- * n >= 1, T 1 .. 8, H 1 .. 256.  One launch. */
+ * n >= 1, T 1 .. 8, H 1 .. 256.  One launch.
+ *
+ * ACTING under dropout.  The mask function is the one above; an acting call with io->agents = A gives row r of its n rows the coordinates
+ *     agent  = r % A
+ *     row G  = drop->row_base + r / A      (the env id: a sharded batch passes its first env id as row_base)
+ *     t      = the window step, layer = the masked layer (0 .. L - 2), offset = drop->offset: the caller's ACTING-TICK counter
+ *     net    = 2 for the imposters' acting network, 3 for the crew's
+ * Nets 0 and 1 stay the train step's online and target network, so an acting mask never coincides with a training mask of the same seed,
+ * and the two teams' forwards of one tick (same offset) use different masks.
+ * susnet_spatial_forward_dropout: susnet_spatial_forward with the recurrence in nn.RNN's TRAINING mode -- layer l + 1 reads
+ * m[l][t] * h[l][t], layer l's own recurrence the undropped h[l][t], the head the undropped top layer; the convolutions are the plain
+ * call's kernel -- with p = drop->p[net - 2] (p[0] the imposters' acting network, p[1] the crew's; the other p is not looked at).  The
+ * summation orders are the plain call's; the product m * h is one float32 multiplication, made where h is written.  With p == 0,
+ * floor(p * 2^32) == 0 or rnn_layers == 1 the call launches susnet_spatial_forward's kernels: the result is that call's bit for bit.
+ * Otherwise the recurrence kernel is k_spatial_rnn_dropout, which keeps the products in LDS behind the hidden states: its LDS rule is
+ * (rnn_layers + 2) x 64 rows x max(rnn_hidden, the head's hidden widths) floats at rnn_layers == 2 and (rnn_layers + 3) x ... from
+ * rnn_layers == 3 on, within a workgroup's 160 KiB (so rnn_hidden 128 is served with up to two layers under dropout, 64 with up to four).
+ * Equal (inputs, seed, offset, row_base, net) give equal bytes, whatever the grid; rows [k A, (k + m) A) of a batch forwarded alone with
+ * row_base + k give those rows' bytes.  Refused (SUSNET_E_INVALID, the field named, before any launch): drop NULL, net outside 2 .. 3,
+ * p outside [0, 1) or NaN, offset >= 2^56, row_base < 0 or row_base + ceil(n / agents) > 2^40, agents > 4096, the LDS rule above (the
+ * bytes in the message), and everything susnet_spatial_forward refuses, with that call's messages behind this call's name.
+ * susnet_spatial_act_dropout_mask: the multipliers out[layers - 1][n][T][H] (device float32, 4-byte aligned) that call applies to rows
+ * 0 .. n - 1 for the same `drop`, `net` and `agents`.  Served: net 2 / 3, agents 1 .. 4096, layers 2 .. 4, n >= 1, T 1 .. 8, H 1 .. 256.
+ * One launch.  (susnet_rnn_dropout_mask serves nets 0 / 1 only, as before.) */
 typedef struct susnet_rnn_dropout {
-    float p[2];                      /* [0] the online network, [1] the target network; 0 switches that net's mask off */
+    float p[2];                      /* [0] the online network, [1] the target network; 0 switches that net's mask off.  The acting
+                                        calls: [0] the imposters' acting network (net 2), [1] the crew's (net 3) */
     uint64_t seed;
     uint64_t offset;                 /* below 2^56: the caller's call counter */
     int64_t row_base;                /* added to every row index */
@@ -895,6 +922,9 @@ int susnet_spatial_train_dropout_workspace_bytes(const susnet_env *env, const su
 int susnet_spatial_train_step_dropout(susnet_env *env, const susnet_spatial_train_io *io, const susnet_rnn_dropout *drop, void *stream);
 int susnet_rnn_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agent, int32_t layers, int64_t n, int32_t T,
                             int32_t H, float *out, void *stream);
+int susnet_spatial_forward_dropout(susnet_env *env, const susnet_spatial_io *io, const susnet_rnn_dropout *drop, int32_t net, void *stream);
+int susnet_spatial_act_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agents, int32_t layers, int64_t n,
+                                    int32_t T, int32_t H, float *out, void *stream);
 
 /* A sweep's train step for the SpatialDQN.  The reference's users run sweeps -- notebooks/experiment_1v1.ipynb and
  * notebooks/experiment_mlp.ipynb loop `for config in configs: run_experiment(**config)` over gamma ([0.99, 0.9, 0.8]) and the learning

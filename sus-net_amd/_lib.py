@@ -45,7 +45,7 @@ LIFETIME_NAMES = ["episodes", "crew_won", "imposter_won", "truncated", "imp_kill
 # every symbol include/susnet.h declares
 EXPORTS = [
     "susnet_abi_version", "susnet_last_error", "susnet_create", "susnet_destroy", "susnet_get_layout",
-    "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_agent_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_window_push", "susnet_state_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
+    "susnet_bind_state", "susnet_bind_tape", "susnet_seed", "susnet_tick", "susnet_reset", "susnet_sample_actions", "susnet_policy_actions", "susnet_agent_policy_actions", "susnet_qnet_packed_floats", "susnet_qnet_pack", "susnet_qnet_forward", "susnet_mlp_forward", "susnet_spatial_forward", "susnet_spatial_forward_dropout", "susnet_spatial_act_dropout_mask", "susnet_window_push", "susnet_state_window_push", "susnet_step", "susnet_policy_step", "susnet_qnet_policy_step", "susnet_qnet_policy_rollout",
     "susnet_rollout", "susnet_record_layout", "susnet_record_layout_of", "susnet_set_launch_limit", "susnet_observe", "susnet_obs_size", "susnet_featurize", "susnet_export_state", "susnet_import_state",
     "susnet_reduce_lifetime", "susnet_device_tick", "susnet_poll_errors", "susnet_ring_append", "susnet_scent",
     "susnet_dqn_workspace_bytes", "susnet_dqn_train_step", "susnet_dqn_train_sweep", "susnet_mlp_train_workspace_bytes", "susnet_mlp_train_step", "susnet_mlp_train_sweep", "susnet_spatial_train_workspace_bytes", "susnet_spatial_train_step", "susnet_spatial_train_dropout_workspace_bytes", "susnet_spatial_train_step_dropout", "susnet_rnn_dropout_mask", "susnet_spatial_train_sweep_table_bytes", "susnet_spatial_train_sweep", "susnet_episode_stats_bytes", "susnet_episode_stats",
@@ -301,6 +301,9 @@ def lib():
     L.susnet_spatial_train_step_dropout.argtypes = [C.c_void_p, P(SpatialTrainIO), P(RnnDropout), C.c_void_p]
     L.susnet_rnn_dropout_mask.argtypes = [C.c_void_p, P(RnnDropout), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                           C.c_void_p]
+    L.susnet_spatial_forward_dropout.argtypes = [C.c_void_p, P(SpatialIO), P(RnnDropout), C.c_int32, C.c_void_p]
+    L.susnet_spatial_act_dropout_mask.argtypes = [C.c_void_p, P(RnnDropout), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_void_p]
     L.susnet_spatial_train_sweep_table_bytes.argtypes = [C.c_int32, P(C.c_uint64)]
     L.susnet_spatial_train_sweep.argtypes = [P(C.c_void_p), P(SpatialTrainIO), P(RnnDropout), C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
     L.susnet_episode_stats_bytes.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint64), P(C.c_uint64)]

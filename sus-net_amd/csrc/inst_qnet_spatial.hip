@@ -97,75 +97,16 @@ __global__ __launch_bounds__(kSpThreads) void k_spatial_conv(SpatialConvArgs a) 
 
 // ---- the recurrence and the head --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kDnThreads) void k_spatial_rnn(SpatialRnnArgs a) {
-    extern __shared__ float sr_smem[];
-    const int t_ = threadIdx.x, lane = t_ & 63, i = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(t_ >> 6);
-    const int L = a.L, H = a.H, nb = L + 1, nl = a.n_dims - 1;
-    const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
-    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int64_t base = tile * kDnRows;
-        int c = 0; // step t L + l writes buffer c mod (L + 1); h_{l-1}[t] is one buffer back, h_l[t-1] one buffer on
-        for (int t = 0; t < a.T; t++) {
-            for (int l = 0; l < L; l++, c = c + 1 == nb ? 0 : c + 1) {
-                float *hout = sr_smem + (size_t)c * a.buf;
-                const float *below = sr_smem + (size_t)(c == 0 ? nb - 1 : c - 1) * a.buf;
-                const float *before = sr_smem + (size_t)(c + 1 == nb ? 0 : c + 1) * a.buf;
-                const float *Wih = a.w_ih[l], *Whh = a.w_hh[l], *bih = a.b_ih[l], *bhh = a.b_hh[l];
-                const int items = ((H + 31) >> 5) * 2;
-                for (int it = wave; it < items; it += kDnWaves) {
-                    const int n0 = (it >> 1) * 32, st = it & 1;
-                    const int64_t s = base + st * 32 + i;
-                    const bool svalid = s < a.n;
-                    dn_f32x16 acc = dn_bias(bih, bhh, H, n0, lane);
-                    if (l == 0) {
-                        const float *xrow = a.rnn_in + ((size_t)(svalid ? s : a.n - 1) * a.T + t) * a.R;
-                        acc = dn_chain<true>(acc, Wih, a.R, H, n0, st, xrow, svalid, nullptr, lane);
-                    } else {
-                        acc = dn_chain<false>(acc, Wih, H, H, n0, st, nullptr, svalid, below, lane);
-                    }
-                    if (t > 0) acc = dn_chain<false>(acc, Whh, H, H, n0, st, nullptr, svalid, before, lane);
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int u = n0 + dn_row(r, lane);
-                        if (u < H) hout[dn_lds(u, st * 32 + i)] = sp_tanh(acc[r]);
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // the head (dqn.py:298-299) on h_{L-1}[T-1], which the last step left one buffer back; its layers alternate between that buffer and c
-        int zi = c == 0 ? nb - 1 : c - 1, zo = c;
-        for (int l = 0; l < nl; l++) {
-            const int dk = a.d[l], dn = a.d[l + 1];
-            const float *W = a.W[l], *bias = a.B[l];
-            const bool last = l == nl - 1;
-            const float slope = last ? 1.0f : a.A[l][0];
-            const float *zin = sr_smem + (size_t)zi * a.buf;
-            float *zout = sr_smem + (size_t)zo * a.buf;
-            const int items = ((dn + 31) >> 5) * 2;
-            for (int it = wave; it < items; it += kDnWaves) {
-                const int n0 = (it >> 1) * 32, st = it & 1;
-                const int64_t s = base + st * 32 + i;
-                const bool svalid = s < a.n;
-                const dn_f32x16 acc = dn_block<false>(W, bias, dk, dn, n0, st, nullptr, svalid, zin, lane);
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int u = n0 + dn_row(r, lane);
-                    if (u < dn) {
-                        if (last) {
-                            if (svalid) a.q[(size_t)s * dn + u] = acc[r];
-                        } else {
-                            zout[dn_lds(u, st * 32 + i)] = dn_prelu(acc[r], slope);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            const int sw = zi;
-            zi = zo;
-            zo = sw;
-        }
-    }
+#define SP_RNN_DROPOUT 0
+#include "susnet_spatial_rnn_body.h"
+#undef SP_RNN_DROPOUT
+}
+
+// the training-mode form: dropout between the layers (the body's header says how)
+__global__ __launch_bounds__(kDnThreads) void k_spatial_rnn_dropout(SpatialRnnArgs a, SpActDrop dr) {
+#define SP_RNN_DROPOUT 1
+#include "susnet_spatial_rnn_body.h"
+#undef SP_RNN_DROPOUT
 }
 
 // susnet_rnn_dropout_mask: a thread per (layer, row, t, four units) writes the multipliers the dropout train step generates for itself
@@ -178,6 +119,24 @@ __global__ __launch_bounds__(256) void k_rnn_dropout_mask(SpDrop dr, int net, in
         const int layer = (int)(e / HQ / T / n);
         float m[4];
         sp_drop4(dr, net, row, t, layer, q, m);
+        float *dst = out + (((int64_t)layer * n + row) * T + t) * H;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (4 * q + j < H) dst[4 * q + j] = m[j];
+    }
+}
+
+// susnet_spatial_act_dropout_mask: the same thread shape over the acting rows, row r = (env r / agents, agent r % agents)
+__global__ __launch_bounds__(256) void k_spatial_act_dropout_mask(SpActDrop dr, int layers, int64_t n, int T, int H, float *__restrict__ out) {
+    const int HQ = (H + 3) >> 2;
+    const int64_t total = (int64_t)(layers - 1) * n * T * HQ;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int q = (int)(e % HQ), t = (int)(e / HQ % T);
+        const int64_t row = e / HQ / T % n, env = row / dr.agents;
+        const int layer = (int)(e / HQ / T / n);
+        float m[4];
+        sp_drop4_at(dr.k0, dr.k1, dr.off_lo, dr.off_hi, dr.thr, dr.scale, dr.net, (int)(row - env * dr.agents), (uint64_t)(dr.row_base + env), t, layer,
+                    q, m);
         float *dst = out + (((int64_t)layer * n + row) * T + t) * H;
 #pragma unroll
         for (int j = 0; j < 4; j++)
@@ -207,6 +166,11 @@ size_t spatial_rnn_lds(SpatialRnnArgs &a) {
     for (int l = 1; l + 1 < a.n_dims; l++) w = a.d[l] > w ? a.d[l] : w;
     a.buf = w * kDnRows;
     return (size_t)(a.L + 1) * a.buf * sizeof(float);
+}
+
+size_t spatial_rnn_dropout_lds(SpatialRnnArgs &a) {
+    const size_t plain = spatial_rnn_lds(a);
+    return plain + (size_t)(a.L > 2 ? 2 : 1) * a.buf * sizeof(float);
 }
 
 template <int CB, int K>
@@ -249,9 +213,26 @@ hipError_t spatial_rnn_launch(SpatialRnnArgs a, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t spatial_rnn_dropout_launch(SpatialRnnArgs a, const SpActDrop &d, hipStream_t st) {
+    const size_t lds = spatial_rnn_dropout_lds(a);
+    if (lds > kDnLdsNoOptIn) {
+        static LdsOptIn opted;
+        if (hipError_t e = lds_opt_in(reinterpret_cast<const void *>(&k_spatial_rnn_dropout), (int)kSpLdsBudget, opted)) return e;
+    }
+    const int64_t tiles = (a.n + kDnRows - 1) / kDnRows;
+    hipLaunchKernelGGL(k_spatial_rnn_dropout, dim3((unsigned)(tiles < kDnMaxGrid ? tiles : kDnMaxGrid)), dim3(kDnThreads), lds, st, a, d);
+    return hipGetLastError();
+}
+
 hipError_t rnn_dropout_mask_launch(const SpDrop &d, int net, int layers, int64_t n, int T, int H, float *out, hipStream_t st) {
     const int64_t total = (int64_t)(layers - 1) * n * T * ((H + 3) >> 2), blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_rnn_dropout_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, d, net, layers, n, T, H, out);
+    return hipGetLastError();
+}
+
+hipError_t act_dropout_mask_launch(const SpActDrop &d, int layers, int64_t n, int T, int H, float *out, hipStream_t st) {
+    const int64_t total = (int64_t)(layers - 1) * n * T * ((H + 3) >> 2), blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_spatial_act_dropout_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, d, layers, n, T, H, out);
     return hipGetLastError();
 }
 

@@ -153,10 +153,20 @@ extern "C" int susnet_mlp_forward(susnet_env *env, const susnet_mlp_io *io, void
 
 // susnet_spatial_forward: SpatialDQN.forward in eval mode (the kernels: inst_qnet_spatial.hip).  Everything is checked here, before the first
 // launch; the handle gives the error conventions only.
-extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *io, void *stream) {
-    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_forward: null env / io");
-    const Refuse bad{env, "susnet_spatial_forward"};
+// susnet_spatial_forward_dropout (act != nullptr) is the same call with nn.RNN's training-mode dropout between the layers: the same checks
+// with the same messages behind its own name, then the mask's (drop->p[net - 2], offset, row_base over the call's envs, agents) and the
+// LDS rule of the form that is launched -- the plain kernels' where floor(p 2^32) == 0 or there is one layer.
+struct SpatialAct {
+    const susnet_rnn_dropout *drop;
+    int32_t net; // 2 the imposters' acting network, 3 the crew's
+};
+static int spatial_forward(susnet_env *env, const susnet_spatial_io *io, const char *entry, const SpatialAct *act, void *stream) {
+    const Refuse bad{env, entry};
     const auto S = [](long long v) { return std::to_string(v); };
+    if (act) {
+        if (!act->drop) return bad("drop is NULL");
+        if (act->net < 2 || act->net > 3) return bad("net = " + S(act->net) + " (served: 2 .. 3, the imposters' and the crew's acting network)");
+    }
     SpatialGeom g;
     if (int rc = check_spatial_net(bad, "", "", *io, io->n_dims, io->dims, kDnMaxHidden, kDnMaxOut, g)) return rc;
     if (io->n < 1) return bad("n = " + S(io->n) + " (at least one row)");
@@ -224,16 +234,50 @@ extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *
     ra.rnn_in = io->rnn_in;
     ra.n = io->n;
     ra.q = io->q_out;
-    const size_t conv_lds = spatial_conv_lds(ca), rnn_lds = spatial_rnn_lds(ra);
+    SpActDrop dr{};
+    if (act) {
+        const susnet_rnn_dropout &d = *act->drop;
+        const int team = act->net - 2;
+        const float p = d.p[team];
+        if (!(p >= 0.0f && p < 1.0f)) return bad("drop->p[" + S(team) + "] = " + std::to_string(p) + " (served: 0 <= p < 1)");
+        if (d.offset >> 56) return bad("drop->offset = " + std::to_string((unsigned long long)d.offset) + " (served: below 2^56)");
+        const int64_t envs = (io->n + io->agents - 1) / io->agents;
+        if (d.row_base < 0 || d.row_base > (1ll << 40) - envs)
+            return bad("drop->row_base = " + S(d.row_base) + " (served: row_base >= 0, row_base + n / agents <= 2^40)");
+        if (io->agents > 4096) return bad("agents = " + S(io->agents) + " (served under dropout: at most 4096, the mask's agent coordinate)");
+        dr.thr = (uint32_t)((double)p * 4294967296.0); // floor, as drop_check (susnet_dropout.h)
+        dr.scale = 1.0f / (1.0f - p);
+        dr.k0 = (uint32_t)d.seed, dr.k1 = (uint32_t)(d.seed >> 32);
+        dr.off_lo = (uint32_t)d.offset, dr.off_hi = (uint32_t)(d.offset >> 32);
+        dr.row_base = d.row_base;
+        dr.agents = io->agents;
+        dr.net = act->net;
+    }
+    const bool dropout = act && dr.thr != 0u && io->rnn_layers > 1; // else: susnet_spatial_forward's kernels, bit for bit
+    const size_t conv_lds = spatial_conv_lds(ca), rnn_lds = dropout ? spatial_rnn_dropout_lds(ra) : spatial_rnn_lds(ra);
     if (conv_lds > kSpLdsBudget)
         return bad("LDS: one image's activation buffers take " + S((long long)conv_lds) + " bytes of a workgroup's " + S((long long)kSpLdsBudget) +
                    " (C, N, conv_out, conv_padding)");
     if (rnn_lds > kSpLdsBudget)
-        return bad("LDS: (rnn_layers + 1) x 64 rows x max(rnn_hidden, head widths) floats = " + S((long long)rnn_lds) + " bytes of a workgroup's " +
-                   S((long long)kSpLdsBudget));
+        return bad(std::string(dropout ? (io->rnn_layers > 2 ? "LDS under dropout: (rnn_layers + 3)" : "LDS under dropout: (rnn_layers + 2)") : "LDS: (rnn_layers + 1)") +
+                   " x 64 rows x max(rnn_hidden, head widths) floats = " + S((long long)rnn_lds) + " bytes of a workgroup's " + S((long long)kSpLdsBudget));
     HIP_TRY(spatial_conv_launch(ca, static_cast<hipStream_t>(stream)));
-    HIP_TRY(spatial_rnn_launch(ra, static_cast<hipStream_t>(stream)));
+    if (dropout)
+        HIP_TRY(spatial_rnn_dropout_launch(ra, dr, static_cast<hipStream_t>(stream)));
+    else
+        HIP_TRY(spatial_rnn_launch(ra, static_cast<hipStream_t>(stream)));
     return SUSNET_OK;
+}
+
+extern "C" int susnet_spatial_forward(susnet_env *env, const susnet_spatial_io *io, void *stream) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_forward: null env / io");
+    return spatial_forward(env, io, "susnet_spatial_forward", nullptr, stream);
+}
+
+extern "C" int susnet_spatial_forward_dropout(susnet_env *env, const susnet_spatial_io *io, const susnet_rnn_dropout *drop, int32_t net, void *stream) {
+    if (!env || !io) return fail(SUSNET_E_INVALID, "susnet_spatial_forward_dropout: null env / io");
+    const SpatialAct act{drop, net};
+    return spatial_forward(env, io, "susnet_spatial_forward_dropout", &act, stream);
 }
 
 // susnet_rnn_dropout_mask: the multipliers susnet_spatial_train_step_dropout applies, written out (the kernel: inst_qnet_spatial.hip)
@@ -256,6 +300,40 @@ extern "C" int susnet_rnn_dropout_mask(susnet_env *env, const susnet_rnn_dropout
     if (!out || misaligned(out)) return bad("out is NULL or not 4-byte aligned");
     dr.agent = agent;
     HIP_TRY(rnn_dropout_mask_launch(dr, net, layers, n, T, H, out, static_cast<hipStream_t>(stream)));
+    return SUSNET_OK;
+}
+
+// susnet_spatial_act_dropout_mask: the multipliers susnet_spatial_forward_dropout applies to rows 0 .. n - 1 of a call with `agents`
+extern "C" int susnet_spatial_act_dropout_mask(susnet_env *env, const susnet_rnn_dropout *drop, int32_t net, int32_t agents, int32_t layers, int64_t n,
+                                               int32_t T, int32_t H, float *out, void *stream) {
+    if (!env) return fail(SUSNET_E_INVALID, "susnet_spatial_act_dropout_mask: null env");
+    const Refuse bad{env, "susnet_spatial_act_dropout_mask"};
+    const auto range = [&](const char *field, long long v, long long lo, long long hi) {
+        return std::string(field) + " = " + std::to_string(v) + " (served: " + std::to_string(lo) + " .. " + std::to_string(hi) + ")";
+    };
+    if (!drop) return bad("drop is NULL");
+    if (net < 2 || net > 3) return bad(range("net", net, 2, 3));
+    if (agents < 1 || agents > 4096) return bad(range("agents", agents, 1, 4096));
+    if (layers < 2 || layers > kSpMaxRnn) return bad(range("layers", layers, 2, kSpMaxRnn));
+    if (n < 1 || n > (1ll << 40)) return bad(range("n", n, 1, 1ll << 40));
+    if (T < 1 || T > SUSNET_SPATIAL_MAX_T) return bad(range("T", T, 1, SUSNET_SPATIAL_MAX_T));
+    if (H < 1 || H > kDnMaxHidden) return bad(range("H", H, 1, kDnMaxHidden));
+    const float p = drop->p[net - 2];
+    if (!(p >= 0.0f && p < 1.0f)) return bad("drop->p[" + std::to_string(net - 2) + "] = " + std::to_string(p) + " (served: 0 <= p < 1)");
+    if (drop->offset >> 56) return bad("drop->offset = " + std::to_string((unsigned long long)drop->offset) + " (served: below 2^56)");
+    const int64_t envs = (n + agents - 1) / agents;
+    if (drop->row_base < 0 || drop->row_base > (1ll << 40) - envs)
+        return bad("drop->row_base = " + std::to_string((long long)drop->row_base) + " (served: row_base >= 0, row_base + n / agents <= 2^40)");
+    if (!out || misaligned(out)) return bad("out is NULL or not 4-byte aligned");
+    SpActDrop dr{};
+    dr.thr = (uint32_t)((double)p * 4294967296.0);
+    dr.scale = 1.0f / (1.0f - p);
+    dr.k0 = (uint32_t)drop->seed, dr.k1 = (uint32_t)(drop->seed >> 32);
+    dr.off_lo = (uint32_t)drop->offset, dr.off_hi = (uint32_t)(drop->offset >> 32);
+    dr.row_base = drop->row_base;
+    dr.agents = agents;
+    dr.net = net;
+    HIP_TRY(act_dropout_mask_launch(dr, layers, n, T, H, out, static_cast<hipStream_t>(stream)));
     return SUSNET_OK;
 }
 

@@ -3,7 +3,9 @@
 // function, sp_drop4 below: the multiplier of (net, agent, row, t, layer, unit) is a pure function of those six, the seed and the offset
 // -- include/susnet.h states the counter and key layout -- so it does not depend on the grid, the tile, the wave or the order of a list.
 // The train step generates a tile's multipliers once, at the tanh write, and keeps them in its workspace for the next layer's operands,
-// the backward pass and the weight gradient; susnet_rnn_dropout_mask's kernel generates the same values.
+// the backward pass and the weight gradient; susnet_rnn_dropout_mask's kernel generates the same values.  The acting forward under
+// dropout (k_spatial_rnn_dropout, susnet_spatial.h) evaluates the same function at its own coordinates (sp_drop4_at, SpActDrop below:
+// nets 2 / 3), also at the tanh write, and keeps the PRODUCT m h in LDS for the next layer; susnet_spatial_act_dropout_mask writes those multipliers out.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,7 +55,33 @@ __device__ __forceinline__ void sp_drop4(const SpDrop &d, int net, int64_t row, 
 #pragma unroll
     for (int j = 0; j < 4; j++) m[j] = w[j] >= thr ? s : 0.0f;
 }
+
+// the same function of (net, agent, row G) given one by one, for the acting forward, whose agent and row differ from lane to lane (SpActDrop
+// below): the counter and the keep rule are sp_drop4's, word for word.  (sp_drop4 is not written as a call of this one: passed thr[net] and
+// scale[net] as values, the train step's kernels index the by-value struct through scratch memory, which the build refuses.)
+__device__ __forceinline__ void sp_drop4_at(uint32_t k0, uint32_t k1, uint32_t off_lo, uint32_t off_hi, uint32_t thr, float scale, int net, int agent,
+                                            uint64_t g, int t, int layer, int q, float (&m)[4]) {
+    if (thr == 0u) {
+        m[0] = m[1] = m[2] = m[3] = 1.0f;
+        return;
+    }
+    uint32_t w[4];
+    sp_philox(k0, k1, (uint32_t)q | (uint32_t)layer << 8 | (uint32_t)t << 12 | (uint32_t)net << 16 | (uint32_t)agent << 20, (uint32_t)g,
+              ((uint32_t)(g >> 32) & 0xFFu) | off_hi << 8, off_lo, w);
+#pragma unroll
+    for (int j = 0; j < 4; j++) m[j] = w[j] >= thr ? scale : 0.0f;
+}
 #endif
+
+// the acting forward's coordinates (susnet_spatial_forward_dropout, susnet_spatial_act_dropout_mask): row r of the call is
+// (agent r % agents, row G = row_base + r / agents: the env), net 2 the imposters' acting network, 3 the crew's
+struct SpActDrop { // by value: part of the kernels' arguments
+    uint32_t k0, k1, off_lo, off_hi;
+    uint32_t thr; // floor(p 2^32), not 0: the p == 0 forms launch the plain kernels
+    float scale;  // 1.0f / (1.0f - p)
+    int64_t row_base;
+    int32_t agents, net;
+};
 
 // host: one susnet_rnn_dropout (`who` names it: "drop->", "drop[1].") checked for a call that masks `rows` rows, and turned into kernel
 // arguments.  BAD: susnet_host.h's Refuse
@@ -77,5 +105,7 @@ inline int drop_check(const BAD &bad, const std::string &who, const susnet_rnn_d
 
 // susnet_rnn_dropout_mask's kernel (inst_qnet_spatial.hip): out [layers - 1][n][T][H]
 hipError_t rnn_dropout_mask_launch(const SpDrop &d, int net, int layers, int64_t n, int T, int H, float *out, hipStream_t st);
+// susnet_spatial_act_dropout_mask's kernel (inst_qnet_spatial.hip): out [layers - 1][n][T][H] of the acting rows 0 .. n - 1
+hipError_t act_dropout_mask_launch(const SpActDrop &d, int layers, int64_t n, int T, int H, float *out, hipStream_t st);
 
 } // namespace susnet

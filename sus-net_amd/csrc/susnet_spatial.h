@@ -22,6 +22,12 @@
 //                   applied at the write into LDS.  Hidden states live in LDS only, in L + 1 buffers of the dense kernel's [unit][64 rows]
 //                   layout that rotate: step c = t L + l writes buffer c mod (L + 1), h_{l-1}[t] is in buffer c - 1 and h_l[t-1] in
 //                   buffer c + 1 (mod L + 1).  The head runs on the last buffer as the dense kernel's layers do.
+//   k_spatial_rnn_dropout   the same text (susnet_spatial_rnn_body.h, included twice) in nn.RNN's TRAINING mode, for
+//                   susnet_spatial_forward_dropout: the output of every layer below the top one also goes, multiplied by its dropout mask
+//                   (susnet_dropout.h: sp_drop4_at, one Philox block per four consecutive units of a row -- registers 4 q .. 4 q + 3 of the
+//                   accumulator), into a buffer D behind the rotation, which the layer above reads in place of h_{l-1}[t]; the layer's own
+//                   recurrence and the head read the undropped values.  Layer l writes D[l & 1] and reads D[(l - 1) & 1]: one buffer at
+//                   L = 2, two from L = 3 on (a step's waves read and write D between the same two barriers).
 //   tanh            sp_tanh below: e = expm1f(-2 |x|), tanh = copysign(-e / (e + 2), x): no cancellation near 0 (tanh(+-0) = +-0 exactly),
 //                   and for |x| >= 16 the result is set to +-1 (expm1f has long returned -1 exactly there: e^-32 < 2^-25).
 #pragma once
@@ -31,6 +37,7 @@
 
 #include "../../include/susnet.h"
 #include "susnet_dense.h"
+#include "susnet_dropout.h"
 
 namespace susnet {
 
@@ -76,8 +83,10 @@ __device__ __forceinline__ float sp_tanh(float x) {
 // LDS bytes of a call's two kernels; they also fill in G / slot0 / slot1 and buf
 size_t spatial_conv_lds(SpatialConvArgs &a);
 size_t spatial_rnn_lds(SpatialRnnArgs &a);
+size_t spatial_rnn_dropout_lds(SpatialRnnArgs &a); // (L + 2) buffers at L = 2, (L + 3) from L = 3 on
 // the launches (inst_qnet_spatial.hip); arguments validated by the caller, LDS within kSpLdsBudget
 hipError_t spatial_conv_launch(SpatialConvArgs a, hipStream_t st);
 hipError_t spatial_rnn_launch(SpatialRnnArgs a, hipStream_t st);
+hipError_t spatial_rnn_dropout_launch(SpatialRnnArgs a, const SpActDrop &d, hipStream_t st); // a.L >= 2, d.thr != 0
 
 } // namespace susnet

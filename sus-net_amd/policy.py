@@ -474,9 +474,13 @@ class SpatialQNet:
 
     Like ``DenseQNet`` nothing is packed or cached: every ``forward`` takes the parameters' ``data_ptr()``s afresh, so ``optimizer.step`` and
     ``load_state_dict`` are followed without a refresh.  The RNN-input workspace ``[n, T, R]`` and the default output buffer are owned and
-    re-made when the shape changes."""
+    re-made when the shape changes.
 
-    def __new__(cls, env, model):
+    ``SpatialQNet(env, model, act_dropout_seed=s)`` (opt-in) also serves the module's TRAINING-mode forward: ``forward`` then follows
+    ``model.training`` as torch does -- nn.RNN's dropout between the layers through ``susnet_spatial_forward_dropout`` under the library's
+    masks of seed ``s``, or the eval-mode call -- which is how the reference's never-``eval()``ed models act (train.py:104, 355-381)."""
+
+    def __new__(cls, env, model, act_dropout_seed: Optional[int] = None):
         desc = spatial_desc(model)
         if desc is None:
             return None
@@ -484,18 +488,36 @@ class SpatialQNet:
         self.env, self.model, self.desc = env, model, desc
         self.N, self.C, self.Fn, self.R, self.k, self.dims = (desc[f] for f in ("N", "C", "Fn", "R", "k", "dims"))
         self._q = self._rnn_in = None
+        self.act_dropout_seed = None if act_dropout_seed is None else int(act_dropout_seed) & (2**64 - 1)
         return self
 
+    def act_dropout_p(self) -> float:
+        """The dropout probability the next ``forward`` acts under, following the module's mode as torch does: ``rnn.dropout`` for a
+        training-mode model with several RNN layers on an object built with ``act_dropout_seed``, else 0 (``model.eval()``, one layer,
+        ``rnn_dropout = 0``, no seed: the eval-mode forward)."""
+        rnn = self.desc["rnn"]
+        if self.act_dropout_seed is None or not self.model.training or rnn.num_layers < 2:
+            return 0.0
+        return float(rnn.dropout)
+
     @torch.no_grad()
-    def forward(self, spatial: torch.Tensor, non_spatial: torch.Tensor, agents: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, spatial: torch.Tensor, non_spatial: torch.Tensor, agents: int = 1, out: Optional[torch.Tensor] = None,
+                net: int = 2, offset: int = 0, row_base: int = 0) -> torch.Tensor:
         """Q rows ``[B * agents, n_actions]`` (row ``b * agents + i`` = env b, agent i) of the featurizers' tensors as they are:
         ``spatial`` ``[B, T, A, C, N, N]`` (PerspectiveFeaturizer) or ``[B, T, C, N, N]`` (GlobalFeaturizer's shared planes: every agent
         reads the same image), ``non_spatial`` ``[B, T, A, Fn]`` or ``[B, T, Fn]``.  ``out``: where they go (default: a buffer this object
-        keeps: a result is valid until the next call).  Two launches, asynchronous."""
+        keeps: a result is valid until the next call).  Two launches, asynchronous.
+
+        Built with ``act_dropout_seed`` the call follows the module's mode (``act_dropout_p``): a training-mode model with
+        ``rnn_dropout > 0`` between several layers acts under nn.RNN's inter-layer dropout (``susnet_spatial_forward_dropout``), its mask
+        that of ``net`` (2: the imposters' acting network, 3: the crew's), the acting tick ``offset`` and the envs
+        ``row_base .. row_base + B - 1`` (include/susnet.h); otherwise the three are not looked at.  Without a seed such a model is refused,
+        as it always was."""
         env, model, desc, rnn = self.env, self.model, self.desc, self.desc["rnn"]
-        if model.training and rnn.dropout > 0 and rnn.num_layers > 1:
+        if self.act_dropout_seed is None and model.training and rnn.dropout > 0 and rnn.num_layers > 1:
             raise RuntimeError("SpatialQNet: the model is in training mode with rnn_dropout > 0 between its RNN layers; the kernels compute the "
                                "eval-mode forward (no dropout): call model.eval(), or run the torch module")
+        p = self.act_dropout_p()
         dev = env.device
         assert spatial.device == dev and non_spatial.device == dev, f"SpatialQNet: inputs on {dev}"
         agents = int(agents)
@@ -523,7 +545,13 @@ class SpatialQNet:
             io.spatial_stride[d], io.non_spatial_stride[d] = sp[d], ns[d]
         io.agents, io.n, io.rnn_in, io.q_out = agents, n, self._rnn_in.data_ptr(), out.data_ptr()
         with env._on_device():
-            L.check(env.lib.susnet_spatial_forward(env._h, C.byref(io), env._stream()))
+            if p > 0.0:
+                drop = L.RnnDropout()
+                drop.p[int(net) - 2 if int(net) in (2, 3) else 0] = p  # (a net outside 2 .. 3 is the library's to refuse)
+                drop.seed, drop.offset, drop.row_base = self.act_dropout_seed, int(offset), int(row_base)
+                L.check(env.lib.susnet_spatial_forward_dropout(env._h, C.byref(io), C.byref(drop), int(net), env._stream()))
+            else:
+                L.check(env.lib.susnet_spatial_forward(env._h, C.byref(io), env._stream()))
         return out
 
 
@@ -846,7 +874,7 @@ class WindowedPolicyRollout:
     """
 
     def __init__(self, env, featurizer, imposter_model: nn.Module, crew_model: Optional[nn.Module], sequence_length: int = 2,
-                 epsilon: float = 0.0, mask_dead: bool = True, seed: int = 0, kernels: bool = False):
+                 epsilon: float = 0.0, mask_dead: bool = True, seed: int = 0, kernels: bool = False, act_dropout_seed: Optional[int] = None):
         assert env.obs_config.mode == "raw" and env.obs_config.dtype == torch.uint8 and env.auto_reset, (
             "construct the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
         self.env, self.featurizer = env, featurizer
@@ -854,6 +882,11 @@ class WindowedPolicyRollout:
         self.T, self.epsilon, self.mask_dead = int(sequence_length), float(epsilon), mask_dead
         # kernels=True: a team whose model SpatialQNet serves gets its Q rows for all B * A (env, agent) rows from ONE susnet_spatial_forward
         # per tick, on the featurizer's buffers in place; a model that is not served keeps the torch modules below, per team.  Off by default
+        # act_dropout_seed (with kernels=True): the SpatialQNets are built with it, so a team whose model is in training mode acts under
+        # nn.RNN's dropout between its layers, as the reference's agents do (train.py never calls eval()): net 2 the imposters', net 3 the
+        # crew's.  act_ticks is the mask offset of the NEXT q_rows() / act(): it advances by one per call that ran a team under dropout
+        self.act_dropout_seed = None if act_dropout_seed is None else int(act_dropout_seed) & (2**64 - 1)
+        self.act_ticks = 0
         self.spatial_imposter = self._spatial(imposter_model, env.n_imposter_actions) if kernels else None
         self.spatial_crew = self._spatial(crew_model, env.n_crew_actions) if kernels else None
         self._gen = torch.Generator(device=env.device)
@@ -869,7 +902,7 @@ class WindowedPolicyRollout:
     def _spatial(self, model, n_actions):
         from .features import GlobalFeaturizer, PerspectiveFeaturizer
 
-        net = SpatialQNet(self.env, model)
+        net = SpatialQNet(self.env, model, act_dropout_seed=self.act_dropout_seed)
         if net is None or not isinstance(self.featurizer, (GlobalFeaturizer, PerspectiveFeaturizer)) or self.T > L.SPATIAL_MAX_T:
             return None
         return net if spatial_feed_mismatch(self.env, self.featurizer, net.desc, n_actions) is None else None
@@ -935,7 +968,8 @@ class WindowedPolicyRollout:
     def q_rows(self):
         """``(q_imposter [B * A, n], q_crew [B * A, n] or None)`` of the acting window: ONE ``susnet_featurize`` launch over its ``B * T`` rows
         into reused buffers (a ``SpatialFeed``), and one ``SpatialQNet.forward`` per team that has a model.  Row ``b * A + i`` = env b, agent i; a
-        result is valid until the next call."""
+        result is valid until the next call.  With ``act_dropout_seed`` a team in training mode acts under dropout at offset ``act_ticks``
+        (net 2 the imposters, 3 the crew), and ``act_ticks`` then advances by one; a call that is refused uses up no offset."""
         env, A = self.env, self.env.n_agents
         assert self.spatial_imposter is not None and (self.crew_model is None or self.spatial_crew is not None), (
             "q_rows: susnet_spatial_forward does not serve this policy (WindowedPolicyRollout(kernels=True) with SpatialDQN models)")
@@ -947,9 +981,21 @@ class WindowedPolicyRollout:
             # (the window's rows were written by the stepping kernel: valid by construction, the featurizer's row check is not polled)
             feed.featurize(self.window)
         feed.finish()
-        q_imp = self.spatial_imposter.forward(feed.spatial, feed.non_spatial, A)
-        q_crew = self.spatial_crew.forward(feed.spatial, feed.non_spatial, A) if self.spatial_crew is not None else None
+        q_imp, q_crew = self._team_forwards(feed.spatial, feed.non_spatial)
         return q_imp, q_crew
+
+    def _team_forwards(self, spatial, non_spatial):
+        """One ``SpatialQNet.forward`` per served team on one tick's inputs (None for a team without one), imposters as net 2 and crew as
+        net 3 at offset ``act_ticks``, which advances once if a team ran under dropout."""
+        A, out, dropped = self.env.n_agents, [], False
+        for net, qnet in ((2, self.spatial_imposter), (3, self.spatial_crew)):
+            if qnet is None:
+                out.append(None)
+                continue
+            out.append(qnet.forward(spatial, non_spatial, A, net=net, offset=self.act_ticks))
+            dropped = dropped or qnet.act_dropout_p() > 0.0
+        self.act_ticks += int(dropped)  # (behind both forwards: a refusal raised above has used up no offset)
+        return out
 
     @torch.no_grad()
     def act(self) -> torch.Tensor:
@@ -974,9 +1020,9 @@ class WindowedPolicyRollout:
                 views = self.featurizer.generate_featurized_states()
             spatial, non_spatial = self.kernel_inputs()
             greedy = []
-            for net, model in ((self.spatial_imposter, self.imposter_model), (self.spatial_crew, self.crew_model)):
-                if net is not None:
-                    greedy.append(net.forward(spatial, non_spatial, A).argmax(dim=1).view(B, A))
+            for q, model in zip(self._team_forwards(spatial, non_spatial), (self.imposter_model, self.crew_model)):
+                if q is not None:
+                    greedy.append(q.argmax(dim=1).view(B, A))
                 else:
                     greedy.append(torch.stack([model(sp, ns).argmax(dim=1) for sp, ns in views], dim=1))
             torch.where(imp_mask, greedy[0], greedy[1], out=self._actions)

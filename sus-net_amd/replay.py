@@ -173,7 +173,10 @@ class DeviceReplayBuffer:
         policy's acting window is loaded from the carried raw window (its own buffer); per tick ``susnet_state_window_push`` moves it on from
         the previous slot, ``policy.q_rows()`` gives one Q row per (env, agent), and ``env.agent_policy_tick_into`` writes the slot
         (``susnet_agent_policy_actions`` + ``susnet_step``).  With ``batch=1``, ``rng='numpy'`` and two networks the ring equals the
-        reference's (tests/golden/spatial_collect/*.npz)."""
+        reference's (tests/golden/spatial_collect/*.npz).  A policy built with ``act_dropout_seed`` whose models are in training mode acts
+        under dropout between the RNN layers: every tick is one ``q_rows()``, so a call of ``num_steps`` ticks consumes the mask offsets
+        ``policy.act_ticks .. policy.act_ticks + num_steps - 1`` (as they stand when the call starts) and leaves ``act_ticks`` behind them;
+        nothing here counts offsets itself."""
         import ctypes as C
 
         from . import _lib as L

@@ -245,7 +245,8 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
 @dataclasses.dataclass(frozen=True)
 class _Settings:
     """What ``run_experiment`` and ``run_sweep`` share of a run's settings; a sweep member's are the shared record with its variant's keys
-    replaced.  ``seed`` is a sweep member's (None: ``run_experiment``); ``run_sweep`` has no ``rnn_dropout_seed``."""
+    replaced.  ``seed`` is a sweep member's (None: ``run_experiment``); ``run_sweep`` has no ``rnn_dropout_seed`` and no
+    ``act_dropout_seed``."""
     num_steps: int
     sequence_length: int
     replay_buffer_size: int
@@ -263,6 +264,7 @@ class _Settings:
     target_update_interval: int
     dense_train: bool = False
     rnn_dropout_seed: Optional[int] = None
+    act_dropout_seed: Optional[int] = None
     seed: Optional[int] = None
 
     @classmethod
@@ -366,7 +368,8 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
                              "obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
         _check_spatial_models(f"{who}: variant {variant}" if sweep else who, env, featurizer, imposter_model, crew_model, T)
         components = []
-        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True)
+        policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True,
+                                       act_dropout_seed=s.act_dropout_seed)
         learner = {"featurizer": featurizer, "spatial": True, "rnn_dropout_seed": s.rnn_dropout_seed}
         featurizer_type = "global" if isinstance(featurizer, GlobalFeaturizer) else "perspective"
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=s.learning_rate, gamma=s.gamma, train_imposter=s.train_imposter,
@@ -388,6 +391,8 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
         # which learner the run's train steps take: susnet_spatial_train_step where it serves the trained teams, else torch_train_step
         config["train_step"] = ("susnet_spatial_train_step" if trainer.uses_spatial(ring) else "torch_train_step") if any(trainer.trained) else None
         config["rnn_dropout_seed"] = s.rnn_dropout_seed
+        if s.act_dropout_seed is not None:  # (only then: a run without it writes the config.json it always wrote)
+            config["act_dropout_seed"] = s.act_dropout_seed
     scheduler = ExponentialSchedule(s.scheduler_start_eps, s.scheduler_end_eps, s.scheduler_time_steps)
     return _Member(env, EpisodicMetricHandler(), ring, policy, trainer, scheduler, experiment_dir, generator, config)
 
@@ -411,7 +416,8 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
                    generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
-                   dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
+                   dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None,
+                   act_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: builds ring, policy, trainer and schedule
     (``_build_member``; a run that is refused there has written nothing), writes ``config.json``, pre-populates the ring with
     ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
@@ -431,10 +437,19 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     act for is a ``ValueError`` that says which bound failed.  ``rnn_dropout_seed`` (with ``featurizer``; None: models with dropout between
     their RNN layers train through ``torch_train_step``): the trainer is built with it, so such models -- the reference's own
     ``rnn_layers: 3, rnn_dropout: 0.2`` -- LEARN under the library's dropout masks (``susnet_spatial_train_step_dropout``), online and target
-    network; they ACT in eval mode (put them there with ``model.eval()``: ``susnet_spatial_forward`` is the eval-mode forward and refuses a
-    training-mode model with dropout, as before; the device train step does not put them back into training mode).  The seed is written
-    into ``config.json``."""
+    network.  The seed is written into ``config.json``.  How they ACT follows ``act_dropout_seed`` (with ``featurizer``; without one it is
+    a ``ValueError``): None -- such models act in eval mode (put them there with ``model.eval()``: ``susnet_spatial_forward`` is the
+    eval-mode forward and refuses a training-mode model with dropout, as before); a seed -- the policy is built with it
+    (``WindowedPolicyRollout(kernels=True, act_dropout_seed=...)``), and every acting forward follows its module's mode as torch does: a
+    model left in training mode, which is what the reference's never-``eval()``ed models are (train.py:104, 355-381), acts under nn.RNN's
+    dropout between its layers (``susnet_spatial_forward_dropout``; net 2 the imposters, net 3 the crew, one mask offset per acting tick),
+    a model in ``eval()`` acts without.  The models are left in the mode the caller gave them (the device train step changes no mode),
+    and ``config.json`` carries ``act_dropout_seed`` only when it is given.  ``evaluate()`` / ``evaluate_checkpoints()`` stay eval-mode --
+    evaluation is greedy play -- and keep refusing a training-mode model; ``run_sweep`` has no such argument, as it has no
+    ``rnn_dropout_seed``; torch's own mask stream cannot be reproduced (include/susnet.h)."""
     sequence_length = int(sequence_length)
+    if act_dropout_seed is not None and featurizer is None:
+        raise ValueError("run_experiment: act_dropout_seed is for SpatialDQN runs (featurizer=...): reference MLPs have no dropout")
     s = _Settings.of(locals())
     base = _base_dir(experiment_base_dir)
     m = _build_member(None, env, (imposter_model, crew_model), list(components), featurizer, s, (base, base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")),
@@ -569,7 +584,8 @@ def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks
     inputs), acting as in ``DeviceReplayBuffer.collect``: the dense kernel on the policy's feature window, ``susnet_window_push`` between
     ticks.  ``featurizer`` (a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env``, which then fuses ``ObsConfig('raw', torch.uint8)``):
     ``SpatialDQN`` models acting as in ``collect`` through ``WindowedPolicyRollout(kernels=True, sequence_length=T)``; ``components`` is not
-    read."""
+    read.  Evaluation is greedy play in EVAL mode: there is no ``act_dropout_seed`` here, and a training-mode model with dropout between its
+    RNN layers is refused (call ``model.eval()``), whatever ``run_experiment`` acted under."""
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
     last = None  # the feed slot of the previous tick
