@@ -38,7 +38,7 @@ through stock PyTorch-ROCm -- which is the faster of the two at large batches --
 from __future__ import annotations
 
 import ctypes as C
-from functools import partial
+from functools import cached_property, partial
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -577,6 +577,94 @@ def acts_per_agent(policy) -> bool:
     """Whether ``policy`` gives one Q row per (env, agent) -- a ``WindowedPolicyRollout``: its ticks go through
     ``env.agent_policy_tick_into`` -- and not one per env (``PolicyRollout``: ``env.policy_tick_into``)."""
     return isinstance(policy, WindowedPolicyRollout)
+
+
+def acting_kind(policy):
+    """``(kind, imposters served, crew served)``: ``served_by_kernels`` / ``acts_per_agent`` in one answer, for ``BlockActor`` and the training run's
+    checks -- ``'per_agent'``, ``'dense'`` (a ``PolicyRollout`` with a dense network: ``q_rows()``) or ``'fused'`` (the compiled-in layouts)."""
+    imp, crew, dense = served_by_kernels(policy)
+    return ("per_agent" if acts_per_agent(policy) else "dense" if dense else "fused"), imp, crew
+
+
+def check_random_crew_stream(who: str, env, policy) -> None:
+    """A crew without a model, acting through ``susnet_policy_step`` / ``susnet_agent_policy_actions``, draws from the philox stream."""
+    if policy.crew_model is None and env.rng_kind != "philox":
+        raise ValueError(f"{who}: a random crew draws from the production stream: build the env with rng='philox'")
+
+
+def check_policy_step_actions(who: str, env, tail: str = "") -> None:
+    """``susnet_policy_step``'s limit for Q rows the caller hands in (``tail``: what a caller adds to the message)."""
+    if max(env.n_imposter_actions, env.n_crew_actions) > 16:
+        raise ValueError(f"{who}: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
+                         f"{env.n_crew_actions}{tail}")
+
+
+class BlockActor:
+    """THE acting loop of ``DeviceReplayBuffer.collect`` and ``evaluate``: fills slots ``0 .. n - 1`` of a feed (``env.alloc_feed``) with
+    policy ticks, block after block.  Built once per sequence of blocks; ``form`` is decided here, once:
+
+    * ``'block'``: the whole block in ONE launch (``env.policy_rollout_into``: ``susnet_qnet_policy_rollout``) -- a fused policy on an env
+      that serves the whole tick in one kernel (``one_kernel``), ``one_launch_per_block``, and the block's observation slots 16-byte
+      aligned (``n_block == 1 or (B * state_size) % 16 == 0``);
+    * ``'ticks'``: every other fused policy, tick by tick (``env.policy_tick_into(net_imposter=...)``: one kernel where ``one_kernel``, else
+      the network launch(es) + ``susnet_policy_step``; ``evaluate`` refuses the latter, ``collect`` takes it);
+    * ``'dense'``: per tick ``env.refresh_obs()`` (``policy_tick_into`` writes the raw state into the feed, not ``env.obs``), at T > 1
+      ``policy.push`` with the PREVIOUS slot's flags, ``policy.q_rows()``, then the ``'ticks'`` form's call with Q rows for networks;
+    * ``'per_agent'``: per tick ``policy.push`` from the previous slot (flags and state), ``policy.q_rows()`` (one row per (env, agent)),
+      ``env.agent_policy_tick_into``.
+
+    ``last`` is the previous slot of this sequence (None before its first tick) and carries over block boundaries: one feed per sequence.
+    ``refresh_obs_after``: the caller ends with ``env.refresh_obs()`` (dense, per-agent).  Nothing is refused here: the callers refuse."""
+
+    def __init__(self, env, policy, epsilon: float, mask_dead: bool, n_block: int, one_launch_per_block: bool = True):
+        self.env, self.policy, self.epsilon, self.mask_dead, self.n_block = env, policy, epsilon, mask_dead, n_block
+        self.kind, self.imp_served, self.crew_served = acting_kind(policy)
+        self.windowed = self.kind != "per_agent" and getattr(policy, "sequence_length", 1) > 1
+        aligned = n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0
+        self.form = self.kind if self.kind != "fused" else "block" if one_launch_per_block and self.one_kernel and aligned else "ticks"
+        self.refresh_obs_after = self.kind != "fused"
+        self.start()
+
+    @cached_property
+    def one_kernel(self) -> bool:
+        """Whether the env serves this fused, served policy's whole tick in one kernel: asked of the env on first use, not before."""
+        return (self.kind == "fused" and self.imp_served and self.crew_served and
+                self.env.supports_qnet_policy_step(self.policy.fused_imposter, self.policy.fused_crew, self.epsilon))
+
+    def start(self, fill_window: bool = False) -> None:
+        """A new sequence of blocks.  ``fill_window``: the caller has not loaded the policy's window, it becomes the env's current state T
+        times (train.py:318-322) -- per agent here and now, dense at the first tick behind its ``refresh_obs`` (no extra launch)."""
+        self.last, self.fill_window = None, fill_window
+        if fill_window and self.form == "per_agent":
+            self.policy.reset_window()
+
+    def fill(self, feed, n: int) -> None:
+        """Slots ``0 .. n - 1`` of ``feed``, ``n <= n_block``: one block."""
+        env, policy, epsilon, mask_dead, last = self.env, self.policy, self.epsilon, self.mask_dead, self.last
+        if self.form == "block":
+            env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
+        elif self.form == "per_agent":
+            for t in range(n):
+                if last is not None:
+                    policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
+                q_imp, q_crew = policy.q_rows()
+                env.agent_policy_tick_into(feed, t, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                last = t
+        else:  # 'ticks' / 'dense': env.policy_tick_into by the packed networks, or by the Q rows of the tick's q_rows()
+            dense, windowed, fill_window = self.form == "dense", self.windowed, self.fill_window
+            net_imp, net_crew = (None, None) if dense else (policy.fused_imposter, policy.fused_crew)
+            q_imp = q_crew = None
+            for t in range(n):
+                if dense:
+                    env.refresh_obs()
+                    if windowed and last is not None:
+                        policy.push(feed["done"][last], feed["truncated"][last])
+                    elif windowed and fill_window:  # the first tick of the sequence only: `last` is a slot from here on
+                        policy.reset_window()
+                    q_imp, q_crew = policy.q_rows()
+                env.policy_tick_into(feed, t, net_imposter=net_imp, net_crew=net_crew, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
+                last = t  # (read by the dense form's push alone)
+        self.last = last
 
 
 class PolicyRollout:

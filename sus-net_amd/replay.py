@@ -25,9 +25,14 @@ imposter, and with the shuffle off, the rows are identical.
 """
 from __future__ import annotations
 
+import ctypes as C
 from collections import namedtuple
 
 import torch
+
+from . import _lib as L
+from .env import ObsConfig
+from .policy import BlockActor, check_policy_step_actions, check_random_crew_stream
 
 Batch = namedtuple("Batch", ("states", "actions", "rewards", "next_states", "imposters", "dones"))  # replay_memory.py:6-8
 
@@ -53,6 +58,8 @@ class DeviceReplayBuffer:
         for field, (shape, dtype) in self._FIELDS.items():
             setattr(self, field, torch.empty((max_size, *shape(self)), dtype=dtype, device=dev))
         self.idx = self.size = 0  # ring cursor and fill level
+        # collect(): the env the carried raw window and the feed block belong to, the two, and how many slots of the feed the last block filled
+        self._collect_owner, self._collect_window, self._collect_feed, self._collect_feed_ticks = (None, None, None), None, None, 0
 
     def add_batch(self, state, action, reward, next_state, done, imposters) -> None:
         """N transitions at once; equivalent to N reference ``add`` calls in row order (replay_memory.py:50-73)."""
@@ -86,11 +93,6 @@ class DeviceReplayBuffer:
         ``rng='numpy'`` the ring equals the reference's for the same numpy seed.  ``env`` must auto-reset.  ``packed`` (True / "compact";
         handles that store whole records: the 1v1 kernels): the rollout writes packed records and ``susnet_ring_append`` reads them in
         place -- no separate trajectory tensors."""
-        import ctypes as C
-
-        from . import _lib as L
-        from .env import ObsConfig
-
         assert env.auto_reset, "populate_fused needs an auto-resetting env (episodes restart inside the launch)"
         assert env.flattened_state_size == self.state_size and env.n_agents == self.n_agents and env.n_imposters == self.n_imposters
         T, B, S = self.trajectory_size, env.batch, self.state_size
@@ -100,19 +102,7 @@ class DeviceReplayBuffer:
         window = first.unsqueeze(1).repeat(1, T, 1).contiguous()  # replay_memory.py:108-113: the first state T times
         n_launch = max(1, min(int(ticks_per_launch), int(num_steps)))
         bufs = env.alloc_rollout(n_launch, obs=raw8, replay_feed=True, packed=packed)
-        io = L.RingIO()
-        io.trajectory_size = T
-        if packed:
-            io.record, io.record_format, io.term_obs = bufs["record"].data_ptr(), bufs["_record_format"], bufs["term_obs"].data_ptr()
-        else:
-            io.actions, io.rewards = bufs["actions"].data_ptr(), bufs["rewards"].data_ptr()
-            io.done, io.truncated = bufs["done"].data_ptr(), bufs["truncated"].data_ptr()
-            io.obs, io.term_obs, io.roles = bufs["obs"].data_ptr(), bufs["term_obs"].data_ptr(), bufs["roles"].data_ptr()
-        io.window = window.data_ptr()
-        io.max_size = self.max_size
-        io.states, io.next_states = self.states.data_ptr(), self.next_states.data_ptr()
-        io.ring_actions, io.ring_rewards = self.actions.data_ptr(), self.rewards.data_ptr()
-        io.ring_dones, io.ring_imposters = self.dones.data_ptr(), self.imposters.data_ptr()
+        io = self._ring_io(env, bufs, window, packed=packed)
         done_ticks = 0
         while done_ticks < num_steps:
             n = min(n_launch, num_steps - done_ticks)
@@ -126,16 +116,17 @@ class DeviceReplayBuffer:
         torch.cuda.current_stream(env.device).synchronize()  # (the trajectory buffers die with this call)
         return num_steps * B
 
-    def _ring_io(self, env, feed, window):
-        import ctypes as C
-
-        from . import _lib as L
-
+    def _ring_io(self, env, feed, window, packed=False):
+        """The ``RingIO`` of ``susnet_ring_append`` over this ring: the trajectory block ``feed`` (``env.alloc_feed`` / ``env.alloc_rollout``'s
+        tensors, or with ``packed`` the rollout's whole records) and the carried raw ``window``; ``n_ticks`` / ``idx`` are the caller's, per append."""
         io = L.RingIO()
         io.trajectory_size = self.trajectory_size
-        io.actions, io.rewards = feed["actions"].data_ptr(), feed["rewards"].data_ptr()
-        io.done, io.truncated = feed["done"].data_ptr(), feed["truncated"].data_ptr()
-        io.obs, io.term_obs, io.roles = feed["obs"].data_ptr(), feed["term_obs"].data_ptr(), feed["roles"].data_ptr()
+        if packed:
+            io.record, io.record_format, io.term_obs = feed["record"].data_ptr(), feed["_record_format"], feed["term_obs"].data_ptr()
+        else:
+            io.actions, io.rewards = feed["actions"].data_ptr(), feed["rewards"].data_ptr()
+            io.done, io.truncated = feed["done"].data_ptr(), feed["truncated"].data_ptr()
+            io.obs, io.term_obs, io.roles = feed["obs"].data_ptr(), feed["term_obs"].data_ptr(), feed["roles"].data_ptr()
         io.window = window.data_ptr()
         io.max_size = self.max_size
         io.states, io.next_states = self.states.data_ptr(), self.next_states.data_ptr()
@@ -151,12 +142,11 @@ class DeviceReplayBuffer:
         transition ``(window, actions, rewards, next window, done, imposters)`` goes to the ring with ``ReplayBuffer.add``'s semantics
         (replay_memory.py:50-73; windows as train.py:318-322, 388-389, 441-445).  ``policy``: a ``PolicyRollout`` over ``env`` whose
         models are reference MLPs a network kernel serves (``policy.fused_imposter`` / ``fused_crew`` on the compiled-in layouts, else
-        ``dense_imposter`` / ``dense_crew``: any game with at most 16 actions per team; a crew without a model is random).  With a dense
-        network, per tick: ``susnet_observe`` (the flat observation of the current state), the dense forward(s) on ``env.obs``, then
-        ``susnet_policy_step``.  On the compiled-in layouts, per tick ONE kernel where the env serves the whole tick
-        (``susnet_qnet_policy_step``), else the network launch(es) + ``susnet_policy_step``.  Either way every ``ticks_per_append`` ticks
-        end with ONE ``susnet_ring_append``.  ``one_launch_per_block``: the block's ticks in ONE launch where the env serves it
-        (``susnet_qnet_policy_rollout``: the weights are fixed within a block anyway).  The sequence window carries over between calls
+        ``dense_imposter`` / ``dense_crew``: any game with at most 16 actions per team; a crew without a model is random).  The ticks
+        of a block are ``policy.BlockActor``'s -- the launches of a tick, for each kind of policy, are stated there, once for this loop and
+        ``evaluate``'s --; here every ``ticks_per_append`` ticks end with ONE ``susnet_ring_append``.  ``one_launch_per_block``: the block's
+        ticks in ONE launch where the env serves it (``susnet_qnet_policy_rollout``: the weights are fixed within a block anyway; a fused
+        policy the one-kernel tick does not serve acts tick by tick here).  The sequence window carries over between calls
         (``reset_collection`` after an ``env.reset()``).  Row order = tick-major, env-minor; with ``batch=1``,
         ``rng='numpy'`` and two networks the ring equals the reference's for the same numpy seed and weights
         (tests/golden/collect_*.npz).
@@ -164,63 +154,50 @@ class DeviceReplayBuffer:
         ``policy.sequence_length`` = T > 1 (``PolicyRollout(dense=True, sequence_length=T)``; it must equal ``trajectory_size``): the
         networks act on the window of the last T states.  At the start of every call the policy's feature window is derived from the
         carried raw window (ONE ``susnet_featurize`` launch over its ``B * T`` rows), so it follows the raw window under every rule above;
-        per tick after the first, ``susnet_window_push`` moves it one tick on, reading the flags ``policy_tick_into`` wrote into the feed in
-        place (tests/golden/window/wcollect_*.npz pin the ring against the reference's at T = 2 and 3).  Returns the number of
-        transitions added.
+        the actor moves it on per tick after the first (tests/golden/window/wcollect_*.npz pin the ring against the reference's at T = 2
+        and 3).  Returns the number of transitions added.
 
         ``policy`` a ``WindowedPolicyRollout(kernels=True)`` whose ``SpatialDQN``s ``susnet_spatial_forward`` serves (a crew without a model is
         random): the env is ``ObsConfig('raw', torch.uint8)``, ``policy.T == trajectory_size`` for every T.  At the start of a call the
-        policy's acting window is loaded from the carried raw window (its own buffer); per tick ``susnet_state_window_push`` moves it on from
-        the previous slot, ``policy.q_rows()`` gives one Q row per (env, agent), and ``env.agent_policy_tick_into`` writes the slot
-        (``susnet_agent_policy_actions`` + ``susnet_step``).  With ``batch=1``, ``rng='numpy'`` and two networks the ring equals the
+        policy's acting window is loaded from the carried raw window (its own buffer: the ring append needs the carried one as it stood
+        at the block's start); the actor's per-agent ticks follow.  With ``batch=1``, ``rng='numpy'`` and two networks the ring equals the
         reference's (tests/golden/spatial_collect/*.npz).  A policy built with ``act_dropout_seed`` whose models are in training mode acts
         under dropout between the RNN layers: every tick is one ``q_rows()``, so a call of ``num_steps`` ticks consumes the mask offsets
         ``policy.act_ticks .. policy.act_ticks + num_steps - 1`` (as they stand when the call starts) and leaves ``act_ticks`` behind them;
         nothing here counts offsets itself."""
-        import ctypes as C
-
-        from . import _lib as L
-        from .env import ObsConfig
-
-        from .policy import acts_per_agent, served_by_kernels
-
-        imp_served, crew_served, dense = served_by_kernels(policy)
-        per_agent = acts_per_agent(policy)  # a WindowedPolicyRollout: one Q row per (env, agent), susnet_spatial_forward
-        assert policy.env is env and imp_served, ("collect: the imposters' model must be a reference MLP one of the network kernels "
+        n_block = max(1, min(int(ticks_per_append), int(num_steps)))
+        actor = BlockActor(env, policy, epsilon, mask_dead, n_block, one_launch_per_block)  # (reads of an unserved policy what acting_kind reads)
+        per_agent, windowed = actor.kind == "per_agent", actor.windowed
+        assert policy.env is env and actor.imp_served, ("collect: the imposters' model must be a reference MLP one of the network kernels "
                                                               "serves (PolicyRollout.fused_imposter, or dense_imposter: dense=True), or a "
                                                               "SpatialDQN susnet_spatial_forward serves (WindowedPolicyRollout(kernels=True))")
-        assert crew_served, ("collect: the crew's model must be a reference MLP one of the network kernels serves "
+        assert actor.crew_served, ("collect: the crew's model must be a reference MLP one of the network kernels serves "
                                     "(PolicyRollout.fused_crew / dense_crew), a SpatialDQN susnet_spatial_forward serves "
                                     "(WindowedPolicyRollout(kernels=True)), or None: random crew")
-        if per_agent and policy.crew_model is None and env.rng_kind != "philox":
-            raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
-        if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
-            raise ValueError(f"collect: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
-                             f"{env.n_crew_actions}: only the compiled-in games are collected from at that size")
-        if dense and policy.crew_model is None and env.rng_kind != "philox":
-            raise ValueError("collect: a random crew draws from the production stream: build the env with rng='philox'")
+        if actor.kind == "dense":
+            check_policy_step_actions("collect", env, ": only the compiled-in games are collected from at that size")
+        if actor.kind != "fused":
+            check_random_crew_stream("collect", env, policy)
         assert env.flattened_state_size == self.state_size and env.n_agents == self.n_agents and env.n_imposters == self.n_imposters
         T, B = self.trajectory_size, env.batch
-        windowed = not per_agent and getattr(policy, "sequence_length", 1) > 1
         if per_agent:  # (every T, 1 included: the recurrent network reads the window as a sequence)
             assert policy.T == T, f"collect: the policy acts on windows of {policy.T} states, the ring stores windows of {T} (trajectory_size)"
         if windowed:
-            assert dense, "collect: a policy with sequence_length > 1 acts through the dense kernel"
+            assert actor.kind == "dense", "collect: a policy with sequence_length > 1 acts through the dense kernel"
             assert policy.sequence_length == T, (f"collect: the policy acts on windows of {policy.sequence_length} states, the ring stores "
                                                  f"windows of {T} (trajectory_size)")
         # the carried window and the feed block belong to ONE env (identity, device) between two of its resets: another env of the same
         # batch, or the same env after reset(), starts from its own current state
         owner = (id(env), str(env.device), getattr(env, "reset_generation", 0))
-        if getattr(self, "_collect_owner", None) != owner:
+        if self._collect_owner != owner:
             self._collect_window = None
-            if getattr(self, "_collect_owner", (None, None, None))[:2] != owner[:2]:
+            if self._collect_owner[:2] != owner[:2]:
                 self._collect_feed = None
             self._collect_owner = owner
-        if getattr(self, "_collect_window", None) is None:  # train.py:318-322: the current state T times
+        if self._collect_window is None:  # train.py:318-322: the current state T times
             first = env.observe(ObsConfig("raw", dtype=torch.uint8))
             self._collect_window = first.unsqueeze(1).repeat(1, T, 1).contiguous()
-        n_block = max(1, min(int(ticks_per_append), int(num_steps)))
-        feed = getattr(self, "_collect_feed", None)
+        feed = self._collect_feed
         if feed is None or feed["n_ticks"] != n_block or feed["actions"].shape[1] != B:
             feed = self._collect_feed = env.alloc_feed(n_block)
         io = self._ring_io(env, feed, self._collect_window)
@@ -232,34 +209,11 @@ class DeviceReplayBuffer:
                 L.check(env.lib.susnet_featurize(env._h, rows.data_ptr(), env._ROW_DTYPES[rows.dtype], B * T, C.byref(spec), env._stream()))
         if per_agent:  # the policy's own acting window: the ring append needs the carried one as it stood at the block's start
             policy.load_window(self._collect_window)
-        last = None  # the feed slot of the previous tick of this call
-        # one launch per BLOCK where the env serves the whole tick in one kernel and the block's observation slots are 16-byte aligned
-        fused_block = (one_launch_per_block and not dense and not per_agent and env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon)
-                       and (n_block == 1 or (B * self.state_size) % 16 == 0))
-        done_ticks = 0
+        done_ticks = 0  # (the actor is new with this call: its sequence of blocks starts here, behind the windows loaded above)
         while done_ticks < num_steps:
             n = min(n_block, num_steps - done_ticks)
             policy.refresh_weights(force=False)  # (the optimizer may have stepped since the last block)
-            if fused_block:  # the whole block in ONE launch (susnet_qnet_policy_rollout)
-                env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
-            elif per_agent:  # the acting window one tick on (from the previous slot), both spatial forwards on it, actions + step into the slot
-                for t in range(n):
-                    if last is not None:
-                        policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
-                    q_imp, q_crew = policy.q_rows()
-                    env.agent_policy_tick_into(feed, t, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
-                    last = t
-            elif dense:  # a game / layer stack without a fused path: the dense forward(s) on the current flat observation, then the tick
-                for t in range(n):
-                    env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
-                    if windowed and last is not None:  # the previous tick's flags, read where the stepping kernel wrote them
-                        policy.push(feed["done"][last], feed["truncated"][last])
-                    q_imp, q_crew = policy.q_rows()
-                    env.policy_tick_into(feed, t, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
-                    last = t
-            else:
-                for t in range(n):
-                    env.policy_tick_into(feed, t, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
+            actor.fill(feed, n)
             io.n_ticks, io.idx = n, self.idx
             with torch.cuda.device(env.device):
                 L.check(env.lib.susnet_ring_append(env._h, C.byref(io), env._stream()))
@@ -267,7 +221,7 @@ class DeviceReplayBuffer:
             self.size = min(self.size + n * B, self.max_size)
             done_ticks += n
             self._collect_feed_ticks = n
-        if dense or per_agent:
+        if actor.refresh_obs_after:
             env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
         return num_steps * B
 
@@ -275,7 +229,7 @@ class DeviceReplayBuffer:
     def last_feed(self):
         """``(feed, n_ticks)``: the ``[T][B]`` block the last ``collect`` filled last (``env.alloc_feed``'s tensors; slots ``0 .. n_ticks - 1`` are
         valid) -- what ``EpisodeLog.update`` reads.  The next ``collect`` overwrites it."""
-        feed = getattr(self, "_collect_feed", None)
+        feed = self._collect_feed
         if feed is None:
             raise RuntimeError("last_feed: no collect() has run on this buffer")
         return feed, self._collect_feed_ticks

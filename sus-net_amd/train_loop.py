@@ -28,8 +28,8 @@ import torch
 from . import _lib as L
 from .episodes import EpisodeLog
 from .metrics import EpisodicMetricHandler, SusMetrics
-from .policy import (MLP, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout, acts_per_agent, served_by_kernels, spatial_desc,
-                     spatial_feed_mismatch)
+from .policy import (MLP, BlockActor, PolicyRollout, RandomEquiprobable, SpatialDQN, WindowedPolicyRollout, acting_kind, check_policy_step_actions,
+                     check_random_crew_stream, spatial_desc, spatial_feed_mismatch)
 from .replay import DeviceReplayBuffer
 from .scheduler import ExponentialSchedule
 from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer
@@ -112,17 +112,16 @@ class _Run:
             raise ValueError(f"{who}: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
         if policy.env is not env or trainer.env is not env:
             raise ValueError(f"{who}: policy and trainer must be built over the env that is trained on")
-        imp_served, crew_served, dense = served_by_kernels(policy)
+        kind, imp_served, crew_served = acting_kind(policy)
         if not imp_served or not crew_served:
             raise ValueError(f"{who}: served are reference MLPs a network kernel runs (PolicyRollout.fused_imposter / fused_crew on the compiled-in "
                              "feature layouts, dense_imposter / dense_crew elsewhere: PolicyRollout(..., dense=True)) and SpatialDQNs "
                              "susnet_spatial_forward runs (spatial_imposter / spatial_crew: WindowedPolicyRollout(..., kernels=True)); a crew "
                              "model of None acts randomly")
-        if acts_per_agent(policy) and policy.crew_model is None and env.rng_kind != "philox":
-            raise ValueError(f"{who}: a random crew draws from the production stream: build the env with rng='philox'")
-        if dense and max(env.n_imposter_actions, env.n_crew_actions) > 16:
-            raise ValueError(f"{who}: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
-                             f"{env.n_crew_actions}")
+        if kind == "per_agent":
+            check_random_crew_stream(who, env, policy)
+        if kind == "dense":  # (a random crew off the philox stream is collect's to refuse)
+            check_policy_step_actions(who, env)
         self.env, self.metrics, self.num_steps, self.ring, self.policy, self.trainer = env, metrics, num_steps, replay_buffer, policy, trainer
         self.scheduler, self.generator, self.per_episode_info = scheduler, generator, per_episode_info
         self.save_dir = pathlib.Path(save_directory_path)
@@ -551,23 +550,23 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     return [m.metrics for m in members]
 
 
-def _evaluate_blocks(env, n_ticks: int, block_ticks: int, gamma: float, capacity: Optional[int], begin, refresh_obs: bool) -> dict:
-    """The frame of ``evaluate``: reset, an ``EpisodeLog`` and a feed of ``n_block`` ticks, then per block ``act(feed, n)`` -- ``act`` is
-    what ``begin(n_block)`` returns, called once behind the reset -- and ``EpisodeLog.update``; ONE read-back at the end."""
-    n_block = max(1, min(int(block_ticks), n_ticks))
+def _evaluate_blocks(env, actor: BlockActor, n_ticks: int, gamma: float, capacity: Optional[int]) -> dict:
+    """The frame of ``evaluate``: reset, an ``EpisodeLog`` and a feed of ``actor.n_block`` ticks, then -- one sequence of the actor's, its
+    window filled from the fresh state -- per block ``actor.fill`` and ``EpisodeLog.update``; ONE read-back at the end."""
+    n_block = actor.n_block
     env.reset()
     if capacity is None:  # an episode takes at least one tick
         capacity = min(env.batch * max(n_ticks, 1), 1 << 22)
     log = EpisodeLog(env, gamma=gamma, capacity=capacity)
     feed = env.alloc_feed(n_block)
-    act = begin(n_block)
+    actor.start(fill_window=True)
     t = 0
     while t < n_ticks:
         n = min(n_block, n_ticks - t)
-        act(feed, n)
+        actor.fill(feed, n)
         log.update(feed, n, tick_base=t)
         t += n
-    if refresh_obs:
+    if actor.refresh_obs_after:
         env.refresh_obs()  # leave env.obs on the state the last tick produced, as step() does
     return summarize_episodes(log.records(), ticks=n_ticks)
 
@@ -575,83 +574,41 @@ def _evaluate_blocks(env, n_ticks: int, block_ticks: int, gamma: float, capacity
 @torch.no_grad()
 def evaluate(env, imposter_model, crew_model, components: Sequence[str], n_ticks: int, epsilon: float = 0.0, block_ticks: int = 64,
              mask_dead: bool = True, gamma: float = 1.0, capacity: Optional[int] = None, sequence_length: int = 1, featurizer=None) -> dict:
-    """How a pair of models plays: ``env.reset()``, then the acting loop for ``n_ticks`` lockstep ticks in blocks of ``block_ticks`` (one
-    policy rollout launch into a feed + one ``EpisodeLog.update`` per block; no ring, no trainer), and ONE read-back at the end.
+    """How a pair of models plays: ``env.reset()``, then the acting loop for ``n_ticks`` lockstep ticks in blocks of ``block_ticks``
+    (``policy.BlockActor`` fills a feed, as it does for ``DeviceReplayBuffer.collect`` -- one rollout launch per block where the env serves
+    it --, + one ``EpisodeLog.update`` per block; no ring, no trainer), and ONE read-back at the end.
     ``crew_model=None``: a random crew.  Returns ``episodes``, ``imposter_win_rate``, ``crew_win_rate``, ``truncation_rate``,
     ``mean_imposter_return``, ``mean_crew_return`` (``gamma``-discounted; 1.0 = plain sums), ``mean_length`` and the mean of every info
     counter per finished episode (``mean_<counter>``), plus ``dropped`` (episodes beyond ``capacity``, not in the means) and ``ticks``.
     Rates and means of zero episodes are NaN.  ``sequence_length`` = T > 1: models that read the window of the last T states (``T * F``
-    inputs), acting as in ``DeviceReplayBuffer.collect``: the dense kernel on the policy's feature window, ``susnet_window_push`` between
-    ticks.  ``featurizer`` (a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env``, which then fuses ``ObsConfig('raw', torch.uint8)``):
+    inputs), acting as in ``DeviceReplayBuffer.collect``: the actor's dense ticks on the policy's feature window, which starts as the fresh
+    state T times.  ``featurizer`` (a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` over ``env``, which then fuses ``ObsConfig('raw', torch.uint8)``):
     ``SpatialDQN`` models acting as in ``collect`` through ``WindowedPolicyRollout(kernels=True, sequence_length=T)``; ``components`` is not
     read.  Evaluation is greedy play in EVAL mode: there is no ``act_dropout_seed`` here, and a training-mode model with dropout between its
     RNN layers is refused (call ``model.eval()``), whatever ``run_experiment`` acted under."""
     if not env.auto_reset:
         raise ValueError("evaluate: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
-    last = None  # the feed slot of the previous tick
+    n_ticks = int(n_ticks)
+    n_block = max(1, min(int(block_ticks), n_ticks))
     if featurizer is not None:
-        n_ticks, T = int(n_ticks), int(sequence_length)
+        T = int(sequence_length)
         if env.obs_config.mode != "raw" or env.obs_config.dtype != torch.uint8:
             raise ValueError("evaluate: with a featurizer, build the env with obs=ObsConfig('raw', dtype=torch.uint8), auto_reset=True")
         _check_spatial_models("evaluate", env, featurizer, imposter_model, crew_model, T)
         policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, epsilon=epsilon, mask_dead=mask_dead, kernels=True)
-
-        def act_spatial(feed, n):  # collect's acting loop, without a ring
-            nonlocal last
-            for k in range(n):
-                if last is not None:
-                    policy.push(feed["done"][last], feed["truncated"][last], feed["obs"][last])
-                q_imp, q_crew = policy.q_rows()
-                env.agent_policy_tick_into(feed, k, q_imp, q_crew, epsilon=epsilon, mask_dead=mask_dead)
-                last = k
-
-        def begin(n_block):
-            policy.reset_window()  # train.py:318-322: the fresh state T times
-            return act_spatial
-
-        return _evaluate_blocks(env, n_ticks, block_ticks, gamma, capacity, begin, True)
+        return _evaluate_blocks(env, BlockActor(env, policy, epsilon, mask_dead, n_block), n_ticks, gamma, capacity)
     policy = PolicyRollout(env, imposter_model, crew_model, components=list(components), epsilon=epsilon, mask_dead=mask_dead, dense=True,
                            sequence_length=sequence_length)
-    windowed = policy.sequence_length > 1
-    imp_served, crew_served, dense = served_by_kernels(policy)
-    if not imp_served or not crew_served:
+    actor = BlockActor(env, policy, epsilon, mask_dead, n_block)
+    if not actor.imp_served or not actor.crew_served:
         raise ValueError("evaluate: served are reference MLPs a network kernel runs (the compiled-in feature layouts, or the dense kernel); "
                          "a crew model of None acts randomly")
-    if dense:
-        if max(env.n_imposter_actions, env.n_crew_actions) > 16:
-            raise ValueError(f"evaluate: susnet_policy_step takes at most 16 actions per team, this game has {env.n_imposter_actions} / "
-                             f"{env.n_crew_actions}")
-        if crew_model is None and env.rng_kind != "philox":
-            raise ValueError("evaluate: a random crew draws from the production stream: build the env with rng='philox'")
-    elif not env.supports_qnet_policy_step(policy.fused_imposter, policy.fused_crew, epsilon):
+    if actor.kind == "dense":
+        check_policy_step_actions("evaluate", env)
+        check_random_crew_stream("evaluate", env, policy)
+    elif not actor.one_kernel:  # (collect acts tick by tick with such a policy: the network launch(es) + susnet_policy_step)
         raise ValueError("evaluate: this env / model pair / epsilon is not served by the one-kernel policy tick (susnet_qnet_policy_step)")
-
-    def act_rollout(feed, n):  # the fused rollout: one launch per block
-        env.policy_rollout_into(feed, n, policy.fused_imposter, epsilon=epsilon, mask_dead=mask_dead, net_crew=policy.fused_crew)
-
-    def act_dense(feed, n):  # the dense forward(s) on the current flat observation, then susnet_policy_step into the feed
-        nonlocal last
-        for k in range(n):
-            env.refresh_obs()  # (policy_tick_into writes the raw state into the feed, not env.obs)
-            if windowed:  # the first tick acts on the fresh state T times (train.py:318-322), later ones on the pushed window
-                if last is None:
-                    policy.reset_window()
-                else:
-                    policy.push(feed["done"][last], feed["truncated"][last])
-            q_imp, q_crew = policy.q_rows()
-            env.policy_tick_into(feed, k, q_imposter=q_imp, q_crew=q_crew, epsilon=epsilon, mask_dead=mask_dead)
-            last = k
-
-    def act_ticks(feed, n):  # the one-kernel policy tick, tick by tick
-        for k in range(n):
-            env.policy_tick_into(feed, k, net_imposter=policy.fused_imposter, net_crew=policy.fused_crew, epsilon=epsilon, mask_dead=mask_dead)
-
-    def begin(n_block):
-        if dense:
-            return act_dense
-        return act_rollout if n_block == 1 or (env.batch * env.flattened_state_size) % 16 == 0 else act_ticks
-
-    return _evaluate_blocks(env, int(n_ticks), block_ticks, gamma, capacity, begin, dense)
+    return _evaluate_blocks(env, actor, n_ticks, gamma, capacity)
 
 
 def summarize_episodes(rec, ticks: Optional[int] = None) -> dict:

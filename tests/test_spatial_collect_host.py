@@ -134,6 +134,66 @@ def test_served_by_kernels_knows_the_per_agent_kind(pkg):
     assert w.refresh_weights() is False and w.refresh_weights(force=True) is False
 
 
+def test_block_actor_decides_the_form_once(pkg):
+    P = pkg.policy
+
+    class Env:  # what the decision reads of an env
+        def __init__(self, batch, one_kernel=True):
+            self.batch, self.flattened_state_size, self.one_kernel, self.asked = batch, 21, one_kernel, []
+
+        def supports_qnet_policy_step(self, net, net_crew, epsilon):
+            self.asked.append((net, net_crew, epsilon))
+            return self.one_kernel
+
+    class Fused:
+        fused_imposter, fused_crew, dense_imposter, dense_crew, crew_model = "imp", None, None, None, None
+
+    class Dense(Fused):
+        fused_imposter, dense_imposter, sequence_length = None, object(), 2
+
+    spatial = object.__new__(P.WindowedPolicyRollout)
+    spatial.spatial_imposter, spatial.spatial_crew, spatial.crew_model, spatial.T = object(), None, None, 2
+
+    def form(env, policy, n_block, **kw):
+        actor = P.BlockActor(env, policy, 0.25, True, n_block, **kw)
+        assert actor.last is None and actor.n_block == n_block and (actor.imp_served, actor.crew_served) == (True, True)
+        assert actor.refresh_obs_after == (actor.form in ("dense", "per_agent"))
+        return actor.form
+
+    aligned, unaligned = Env(16), Env(3)
+    assert (16 * 21) % 16 == 0 and (3 * 21) % 16 != 0
+    assert form(aligned, Fused(), 4) == "block"
+    assert aligned.asked == [("imp", None, 0.25)]
+    assert form(unaligned, Fused(), 4) == "ticks"
+    assert form(unaligned, Fused(), 1) == "block"  # one slot: nothing to align
+    unserved = Env(16, one_kernel=False)
+    assert form(unserved, Fused(), 4) == "ticks"
+    assert P.BlockActor(unserved, Fused(), 0.0, True, 4).one_kernel is False and P.BlockActor(aligned, Fused(), 0.0, True, 4).one_kernel is True
+    n_asked = len(aligned.asked)
+    assert form(aligned, Fused(), 4, one_launch_per_block=False) == "ticks"
+    assert len(aligned.asked) == n_asked  # the env is asked where the answer is used
+
+    class Unserved(Fused):
+        fused_imposter = None
+
+    lost = P.BlockActor(aligned, Unserved(), 0.0, True, 4)
+    assert (lost.imp_served, lost.form, lost.one_kernel) == (False, "ticks", False) and len(aligned.asked) == n_asked
+    assert form(aligned, Dense(), 4) == "dense" and form(aligned, spatial, 4) == "per_agent"
+    assert len(aligned.asked) == n_asked  # only a fused policy asks the env
+    assert P.BlockActor(aligned, Dense(), 0.0, True, 4).windowed and not P.BlockActor(aligned, spatial, 0.0, True, 4).windowed
+    assert P.acting_kind(Fused()) == ("fused", True, True) and P.acting_kind(Dense()) == ("dense", True, True)
+    assert P.acting_kind(spatial) == ("per_agent", True, True)
+    # the shared refusals: the words behind `who:` are one text
+    tape = type("E", (), dict(rng_kind="numpy", n_imposter_actions=17, n_crew_actions=5))()
+    with pytest.raises(ValueError, match="^x: a random crew draws from the production stream: build the env with rng='philox'$"):
+        P.check_random_crew_stream("x", tape, Fused())
+    with pytest.raises(ValueError, match="^x: susnet_policy_step takes at most 16 actions per team, this game has 17 / 5: tail$"):
+        P.check_policy_step_actions("x", tape, ": tail")
+    tape.rng_kind, tape.n_imposter_actions = "philox", 16
+    P.check_random_crew_stream("x", tape, Fused())
+    P.check_policy_step_actions("x", tape)
+
+
 def test_docs_no_longer_say_the_path_stays_out():
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         text = open(os.path.join(ROOT, doc)).read()
