@@ -112,6 +112,17 @@ extern "C" {
 #define SUSNET_OBS_PERSP 4  /* PerspectiveFeaturizer (model_ready.py:82-216): per agent i the planes with the agent channels in
                                the order i, 0, .., i-1, i+1, .., A-1 (then the two job channels): spatial [A][A+2][N][N];
                                non_spatial [A][A(+A)+J] = alive (and tag counts) in that same agent order, then job status */
+/* The PERSP views under partial observability (PartiallyObservableFeaturizer, src/features/component.py:162-197 with ROOM_MASKS 8-17,
+ * made total).  The room of cell (x, y) is (x <= w, y <= w), w = (N - 1) / 2: at N = 9 the reference's four quadrants, the wall row and
+ * column with the top and the left rooms; a function of N alone, not of the wall map.  Every plane of agent i's view is multiplied by
+ * the mask of the room that holds agent i's position in THAT state row (a dead agent keeps its stored position: its own channel is
+ * blank, its mask is still its room's).  non_spatial (out2) is PERSP's, unmasked: the alive flags stay global.
+ * out / out2 need only be aligned to their element type here (16 bytes gives vector stores; otherwise every element is stored singly).
+ * Served by susnet_featurize and susnet_obs_size only: susnet_reset / susnet_step / susnet_rollout / susnet_observe and the policy
+ * ticks refuse the two modes (SUSNET_E_INVALID) before any launch -- their kernels share one observation writer, which stays as it is. */
+#define SUSNET_OBS_PERSP_ROOM 5      /* spatial [A][A+2][N][N]: the PERSP planes times the observer's room mask */
+#define SUSNET_OBS_PERSP_ROOM_MASK 6 /* spatial [A][A+3][N][N]: the same, then the mask itself as the last channel
+                                        (add_obs_mask_feature, the reference's default) */
 
 /* flat components (src/features/component.py) */
 #define SUSNET_F_ONEHOT_POS 0
@@ -193,7 +204,8 @@ typedef struct susnet_obs_spec {
     int32_t dtype;                /* SUSNET_F32 (reference layouts) or SUSNET_U8 (compact) */
     int32_t n_components;         /* FLAT only */
     int32_t components[16];       /* SUSNET_F_* in concatenation order */
-    void *out;                    /* [B][obs_size]; PLANES: spatial [B][A+2][N][N]; PERSP: [B][A][A+2][N][N] */
+    void *out;                    /* [B][obs_size]; PLANES: spatial [B][A+2][N][N]; PERSP, PERSP_ROOM: [B][A][A+2][N][N];
+                                     PERSP_ROOM_MASK: [B][A][A+3][N][N] */
     void *out2;                   /* PLANES: non_spatial [B][A(+A)+J]; PERSP: [B][A][A(+A)+J]; else NULL */
 } susnet_obs_spec;
 
@@ -622,7 +634,7 @@ int susnet_obs_size(const susnet_env *env, const susnet_obs_spec *obs, int32_t *
  * rows: device pointer, [n_rows][S] contiguous, S = susnet_layout.obs_raw_size (flatten_state order, base.py:234:
  * x0,y0,.. alive.. jobxy.. jobdone.. (, used, counts, timer_left)), rows_dtype one of SUSNET_U8 / I32 / I64 / F32 /
  * F64 (integer-valued).  obs->out (/out2) receive [n_rows][obs_size] in the layouts of susnet_observe; obs->mode
- * FLAT or PLANES.  A row with a coordinate outside the grid is written as all zeros and reported by
+ * FLAT, PLANES, PERSP, PERSP_ROOM or PERSP_ROOM_MASK.  A row with a coordinate outside the grid is written as all zeros and reported by
  * susnet_poll_errors (SUSNET_E_ROW).  The handle supplies the configuration (A, J, N, wall map) only; its
  * environments are not touched. */
 int susnet_featurize(susnet_env *env, const void *rows, int32_t rows_dtype, int64_t n_rows, const susnet_obs_spec *obs,

@@ -32,6 +32,7 @@ RNG_TAPE, RNG_PHILOX = 1, 2
 U8, I32, I64, F32, F64 = 0, 1, 2, 3, 4
 LAYOUT_AB, LAYOUT_BA = 0, 1
 OBS_NONE, OBS_RAW, OBS_FLAT, OBS_PLANES, OBS_PERSP = 0, 1, 2, 3, 4
+OBS_PERSP_ROOM, OBS_PERSP_ROOM_MASK = 5, 6  # the Perspective views under the observer's room mask: susnet_featurize only
 E_INVALID, E_HIP, E_STATE, E_ACTION_ASSERT, E_ACTION_INDEX, E_TAPE, E_ROW = -1, -2, -3, -4, -5, -6, -7
 
 RECORD_DEFAULT, RECORD_COMPACT = 0, 1

@@ -333,6 +333,54 @@ __global__ __launch_bounds__(kBlock) void k_featurize(Consts c, const void *rows
     write_obs<S>(c, o, T, st, tid, e, active, b0, nrows, 0);
 }
 
+// k_featurize for the two room-masked Perspective modes (SUSNET_OBS_PERSP_ROOM / _ROOM_MASK): the same row parser, then write_obs_room.  A
+// kernel of its own, and k_featurize left word for word as it was: write_obs is what every stepping kernel compiles, and sharing the
+// parser through an inlined helper changed k_featurize's machine code (4 instructions), which this addition must not.
+__global__ __launch_bounds__(kBlock) void k_featurize_room(Consts c, const void *rows, int dtype, int64_t n_rows, int S_row, uint32_t *err, ObsArgs o) {
+    using S = GenericSpec;
+    extern __shared__ uint32_t smem[];
+    const int tid = threadIdx.x;
+    const int64_t b0 = (int64_t)blockIdx.x * kBlock, b = b0 + tid;
+    bool active = b < n_rows;
+    LdsStore st;
+    Tables T = setup_lds<S, false>(c, smem, tid, st);
+    if (tid < 16) T.comp[tid] = (uint32_t)o.comp[tid];
+    wave_lds_fence();
+    Env e = {};
+    if (active) {
+        const int A = c.A, J = c.J, N = c.N;
+        const bool tagging = c.variant == SUSNET_VARIANT_TAGGING;
+        const int64_t base = b * S_row;
+        bool ok = true;
+        int k = 0;
+        for (int i = 0; i < A; i++, k += 2) {
+            const int x = row_value(rows, dtype, base + k), y = row_value(rows, dtype, base + k + 1);
+            ok = ok && (unsigned)x < (unsigned)N && (unsigned)y < (unsigned)N;
+            st.set_agent(i, (uint32_t)(x & 15) | ((uint32_t)(y & 15) << 4), 0u);
+        }
+        for (int i = 0; i < A; i++, k++) e.alive |= (row_value(rows, dtype, base + k) != 0 ? 1u : 0u) << i;
+        if (J > 0 || tagging) {
+            for (int j = 0; j < J; j++, k += 2) {
+                const int x = row_value(rows, dtype, base + k), y = row_value(rows, dtype, base + k + 1);
+                ok = ok && (unsigned)x < (unsigned)N && (unsigned)y < (unsigned)N;
+                st.set_job(j, (uint32_t)(x & 15) | ((uint32_t)(y & 15) << 4));
+            }
+            for (int j = 0; j < J; j++, k++) e.jd |= (row_value(rows, dtype, base + k) != 0 ? 1u : 0u) << j;
+        }
+        if (tagging) { // tagging.py:220-230: used[A], tag_counts[A], interval - timer
+            for (int i = 0; i < A; i++, k++) e.used |= (row_value(rows, dtype, base + k) != 0 ? 1u : 0u) << i;
+            for (int i = 0; i < A; i++, k++) st.set_cnt(i, (uint32_t)row_value(rows, dtype, base + k) & 15u);
+            e.timer = (uint32_t)(c.tag_interval - row_value(rows, dtype, base + k));
+        }
+        if (!ok) {
+            atomicOr(err, SUSNET_ERRBIT_ROW);
+            active = false; // the row stays all zeros
+        }
+    }
+    const int nrows = (int)((n_rows - b0) < kBlock ? (n_rows - b0) : kBlock);
+    write_obs_room<S>(c, o, T, st, tid, e, active, b0, nrows);
+}
+
 // susnet_featurize for the two compiled-in float32 FlatFeaturizer layouts (susnet_flat.h): a lane parses the few fields its row
 // needs (cells and alive flags lead every flattened state, base.py:234-235), builds the row's bit mask, and the wave writes its 64
 // rows cooperatively.  The generic kernel above zero-fills a byte image, walks a run-time component list and expands the image;
@@ -742,9 +790,22 @@ extern "C" int susnet_seed(susnet_env *env, uint64_t seed, uint64_t cursor, void
 // packed LDS image of `elements` elements of `bits` bits each, in words, rounded to 16 bytes
 static inline int img_words(int elements, int bits) { return (int)(((size_t)elements * bits + 127) / 128 * 4); }
 
-static int build_obs(const susnet_env *env, const susnet_obs_spec *spec, ObsArgs &o, int64_t ticks_batch) {
+static inline bool is_room_mode(int mode) { return mode == SUSNET_OBS_PERSP_ROOM || mode == SUSNET_OBS_PERSP_ROOM_MASK; }
+
+// The room-masked Perspective modes are served by susnet_featurize / susnet_obs_size alone (the stepping kernels, susnet_reset and
+// susnet_observe share write_obs, which does not know them): every other entry point that takes an observation asks here first, before
+// it looks at the handle's state or launches anything; build_obs (rows_only = false) refuses them again.
+static int refuse_room_mode(const char *who, const susnet_obs_spec *spec) {
+    if (!spec || !is_room_mode(spec->mode)) return SUSNET_OK;
+    return fail(SUSNET_E_INVALID, std::string(who) + ": " + (spec->mode == SUSNET_OBS_PERSP_ROOM ? "SUSNET_OBS_PERSP_ROOM" : "SUSNET_OBS_PERSP_ROOM_MASK") +
+                                      " is served by susnet_featurize (and susnet_obs_size) only: featurize raw state rows");
+}
+
+static int build_obs(const susnet_env *env, const susnet_obs_spec *spec, ObsArgs &o, int64_t ticks_batch, bool rows_only = false) {
     std::memset(&o, 0, sizeof(o));
     if (!spec || spec->mode == SUSNET_OBS_NONE) return SUSNET_OK;
+    if (!rows_only)
+        if (int rc = refuse_room_mode("observation", spec)) return rc;
     const Consts &c = env->c;
     if (spec->dtype != SUSNET_F32 && spec->dtype != SUSNET_U8) return fail(SUSNET_E_INVALID, "obs dtype must be F32 or U8");
     o.mode = spec->mode;
@@ -776,7 +837,7 @@ static int build_obs(const susnet_env *env, const susnet_obs_spec *spec, ObsArgs
                 o.comp[2] == SUSNET_F_CLOSEST_CREW)
                 o.flat_feat = FEAT_ONEHOT_ALIVE_CLOSEST;
         }
-    } else if (spec->mode == SUSNET_OBS_PLANES || spec->mode == SUSNET_OBS_PERSP) {
+    } else if (spec->mode == SUSNET_OBS_PLANES || spec->mode == SUSNET_OBS_PERSP || is_room_mode(spec->mode)) {
         o.F = (c.A + 2) * c.N * c.N;
         o.F2 = c.A + c.J + (c.variant == SUSNET_VARIANT_TAGGING ? c.A : 0);
         o.words1 = img_words(kBlock * o.F, 1);
@@ -786,13 +847,19 @@ static int build_obs(const susnet_env *env, const susnet_obs_spec *spec, ObsArgs
         if (spec->mode == SUSNET_OBS_PERSP) { // every agent's rotated copy of the same images
             o.F *= c.A;
             o.F2 *= c.A;
+        } else if (is_room_mode(spec->mode)) { // the same images; the mask channel exists in the output only
+            o.F = c.A * (c.A + (spec->mode == SUSNET_OBS_PERSP_ROOM_MASK ? 3 : 2)) * c.N * c.N;
+            o.F2 *= c.A;
         }
     } else {
         return fail(SUSNET_E_INVALID, "unknown obs mode");
     }
-    if (o.mode != SUSNET_OBS_PLANES && o.mode != SUSNET_OBS_PERSP) { o.Fi = o.F; o.F2i = o.F2; }
+    if (o.mode != SUSNET_OBS_PLANES && o.mode != SUSNET_OBS_PERSP && !is_room_mode(o.mode)) { o.Fi = o.F; o.F2i = o.F2; }
     if (!o.out) return fail(SUSNET_E_INVALID, "obs.out is null");
-    if ((uintptr_t)o.out % 16 || (o.out2 && (uintptr_t)o.out2 % 16)) return fail(SUSNET_E_INVALID, "obs buffers must be 16-byte aligned");
+    if (is_room_mode(o.mode)) { // (their expansion stores element by element where a buffer is not vector-aligned)
+        const uintptr_t el = o.dtype == SUSNET_F32 ? 4 : 1;
+        if ((uintptr_t)o.out % el || (o.out2 && (uintptr_t)o.out2 % el)) return fail(SUSNET_E_INVALID, "obs buffers must be aligned to their element type");
+    } else if ((uintptr_t)o.out % 16 || (o.out2 && (uintptr_t)o.out2 % 16)) return fail(SUSNET_E_INVALID, "obs buffers must be 16-byte aligned");
     o.tick_stride = ticks_batch * o.F;
     o.tick_stride2 = ticks_batch * o.F2;
     return SUSNET_OK;
@@ -806,7 +873,7 @@ static size_t lds_bytes(const susnet_env *env, const ObsArgs &o, bool may_reset,
     const bool swar = is_swar_spec(spec);
     size_t core = (size_t)lds_core_words(c.A, c.J, spec == 0, swar, (swar && rollout) ? c.N : 0) * 4;
     size_t perm = (may_reset && env->cfg.rng_mode == SUSNET_RNG_TAPE) ? (size_t)c.n_valid * kBlock : 0;
-    size_t stage = (size_t)(o.words1 + o.words2) * 4;
+    size_t stage = (size_t)(o.words1 + o.words2 + (is_room_mode(o.mode) ? kRoomWords : 0)) * 4; // (+ write_obs_room's room word per row)
     if (spec == 2 && rollout && c.duel_walls) core += (size_t)kDuelWallWords * 4; // the cells' blocked-move bits (susnet_duel.h DuelWallTable)
     return core + (perm > stage ? perm : stage);
 }
@@ -818,7 +885,7 @@ extern "C" int susnet_obs_size(const susnet_env *env, const susnet_obs_spec *obs
     tmp.out = dummy;
     tmp.out2 = nullptr;
     ObsArgs o;
-    if (int rc = build_obs(env, &tmp, o, env->c.B)) return rc;
+    if (int rc = build_obs(env, &tmp, o, env->c.B, true)) return rc;
     if (size_out) *size_out = o.F;
     if (size2_out) *size2_out = o.F2;
     return SUSNET_OK;
@@ -828,6 +895,7 @@ extern "C" int susnet_obs_size(const susnet_env *env, const susnet_obs_spec *obs
     if ((bytes) > 64 * 1024) return fail(SUSNET_E_INVALID, "observation too large for the LDS staging area")
 
 extern "C" int susnet_reset(susnet_env *env, const uint8_t *mask, const susnet_obs_spec *obs, void *stream) {
+    if (int rc = refuse_room_mode("susnet_reset", obs)) return rc;
     if (int rc = check_bound(env)) return rc;
     ObsArgs o;
     if (int rc = build_obs(env, obs, o, env->c.B)) return rc;
@@ -969,6 +1037,7 @@ static int qnet_step_launch(susnet_env *env, bool tape, const QnetFuse &f, const
 // n_ticks > 1 (fuse only: susnet_qnet_policy_rollout): the one-kernel tick repeated inside ONE launch, outputs tick-strided (ts)
 static int step_impl(susnet_env *env, const susnet_step_io *io, const float *q_imp, const float *q_crew, void *stream, const QnetFuse *fuse = nullptr,
                      const susnet_policy_opts *opts = nullptr, int n_ticks = 1, const TickStrides *ts = nullptr) {
+    if (int rc = refuse_room_mode("susnet_step / policy tick", io ? io->obs : nullptr)) return rc;
     if (int rc = check_bound(env)) return rc;
     if (!io || (!io->actions && !q_imp && !fuse)) return fail(SUSNET_E_INVALID, "null actions");
     StepArgs a;
@@ -1215,6 +1284,7 @@ extern "C" int susnet_set_launch_limit(susnet_env *env, uint64_t bytes) {
 }
 
 extern "C" int susnet_rollout(susnet_env *env, const susnet_rollout_io *io, void *stream) {
+    if (int rc = refuse_room_mode("susnet_rollout", io ? io->obs : nullptr)) return rc;
     if (int rc = check_bound(env)) return rc;
     if (!io || io->n_ticks < 1) return fail(SUSNET_E_INVALID, "n_ticks must be >= 1");
     const bool tape = env->cfg.rng_mode == SUSNET_RNG_TAPE;
@@ -1358,6 +1428,7 @@ extern "C" int susnet_scent(susnet_env *env, const void *rows, int32_t rows_dtyp
 
 
 extern "C" int susnet_observe(susnet_env *env, const susnet_obs_spec *obs, void *stream) {
+    if (int rc = refuse_room_mode("susnet_observe", obs)) return rc;
     if (int rc = check_bound(env)) return rc;
     if (!obs || obs->mode == SUSNET_OBS_NONE) return fail(SUSNET_E_INVALID, "nothing to observe");
     ObsArgs o;
@@ -1373,14 +1444,14 @@ extern "C" int susnet_featurize(susnet_env *env, const void *rows, int32_t rows_
                                 void *stream) {
     if (int rc = check_bound(env)) return rc; // the device error word lives in the bound state blob
     if (!rows || n_rows < 0) return fail(SUSNET_E_INVALID, "rows is null / n_rows negative");
-    if (!obs || (obs->mode != SUSNET_OBS_FLAT && obs->mode != SUSNET_OBS_PLANES && obs->mode != SUSNET_OBS_PERSP))
-        return fail(SUSNET_E_INVALID, "susnet_featurize: obs mode must be FLAT, PLANES or PERSP");
+    if (!obs || (obs->mode != SUSNET_OBS_FLAT && obs->mode != SUSNET_OBS_PLANES && obs->mode != SUSNET_OBS_PERSP && !is_room_mode(obs->mode)))
+        return fail(SUSNET_E_INVALID, "susnet_featurize: obs mode must be FLAT, PLANES, PERSP, PERSP_ROOM or PERSP_ROOM_MASK");
     if (rows_dtype != SUSNET_U8 && rows_dtype != SUSNET_I32 && rows_dtype != SUSNET_I64 && rows_dtype != SUSNET_F32 &&
         rows_dtype != SUSNET_F64)
         return fail(SUSNET_E_INVALID, "rows dtype must be U8 / I32 / I64 / F32 / F64");
     if (n_rows == 0) return SUSNET_OK;
     ObsArgs o;
-    if (int rc = build_obs(env, obs, o, n_rows)) return rc;
+    if (int rc = build_obs(env, obs, o, n_rows, true)) return rc;
     const dim3 g((unsigned)((n_rows + kBlock - 1) / kBlock));
     const Consts &c = env->c;
     if (o.mode == SUSNET_OBS_FLAT && o.dtype == SUSNET_F32 && !env->force_generic) { // the compiled-in layouts (susnet_flat.h)
@@ -1401,8 +1472,8 @@ extern "C" int susnet_featurize(susnet_env *env, const void *rows, int32_t rows_
     }
     size_t sh = lds_bytes(env, o, false);
     CHECK_LDS(sh);
-    hipLaunchKernelGGL(k_featurize, g, dim3(kBlock), sh, static_cast<hipStream_t>(stream), env->c, rows, (int)rows_dtype, n_rows,
-                       (int)env->layout.obs_raw_size, env->s.err, o);
+    hipLaunchKernelGGL(is_room_mode(o.mode) ? k_featurize_room : k_featurize, g, dim3(kBlock), sh, static_cast<hipStream_t>(stream), env->c, rows,
+                       (int)rows_dtype, n_rows, (int)env->layout.obs_raw_size, env->s.err, o);
     HIP_TRY(hipGetLastError());
     return SUSNET_OK;
 }

@@ -365,4 +365,92 @@ __device__ __forceinline__ void write_obs_raw8(const Consts &c, const ObsArgs &o
     wave_lds_fence();
 }
 
+// ---- room-masked Perspective views (SUSNET_OBS_PERSP_ROOM / _ROOM_MASK; susnet_featurize only) -------------------------------------
+// PartiallyObservableFeaturizer (component.py:162-197) over ROOM_MASKS (8-17), made total: the room of cell (x, y) is
+// (x <= w, y <= w) with w = (N - 1) / 2 -- a function of N alone.  Two bits: bit 0 = x <= w, bit 1 = y <= w.
+__host__ __device__ inline uint32_t room_of(int x, int y, int w) { return (x <= w ? 1u : 0u) | (y <= w ? 2u : 0u); }
+constexpr int kRoomWords = kWave; // one word per row behind the two images: 2 room bits per agent (A <= 16)
+
+// expand_persp_planes with the observer's room mask: output channels C = A + 2 (+ 1), each element ANDed with room(cell) == room(agent i)
+// of its own row; with MASK the last channel is that predicate itself.  `roomw[row]` holds every agent's room (a dead observer has no bit
+// in the planes image to find it by); `valid` bit `row` is clear for a row the parser rejected, which stays all zeros, mask channel included.
+template <class OUT_T, bool MASK>
+__device__ __forceinline__ void expand_persp_room_planes(const uint32_t *img, const uint32_t *roomw, uint64_t valid, int rows, int A, int N,
+                                                         OUT_T *dst, int lane) {
+    const int NN = N * N, w = (N - 1) >> 1, Ci = A + 2, C = Ci + (MASK ? 1 : 0);
+    const int per_row = A * C * NN, total = rows * per_row, Fi = Ci * NN, Fo = C * NN;
+    const bool vec_ok = (reinterpret_cast<uintptr_t>(dst) & (4 * sizeof(OUT_T) - 1)) == 0;
+    // the room agent i stands in, in row `row` (4 = no room: a rejected row; `row` passes `rows` only in elements that are not stored)
+    auto observer = [&](int row, int i) -> uint32_t { return ((valid >> (row & 63)) & 1u) ? (roomw[row & 63] >> (2 * i)) & 3u : 4u; };
+    for (int g = lane * 4; g < total; g += kWave * 4) {
+        int row = g / per_row, r = g - row * per_row;
+        int i = r / Fo, r2 = r - i * Fo;
+        int ch = r2 / NN, cell = r2 - ch * NN;
+        int x = cell / N, y = cell - x * N;
+        uint32_t mine = observer(row, i);
+        OUT_T v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t q = room_of(x, y, w) == mine ? 1u : 0u;
+            if (!MASK || ch < Ci) {
+                const int src = ch < A ? persp_source(i, ch) : ch;
+                const int bit = (row & 63) * Fi + src * NN + cell; // (never past the image)
+                q &= img[bit >> 5] >> (bit & 31);
+            }
+            v[k] = (OUT_T)q;
+            if (++y == N) { y = 0; x++; }
+            if (++cell == NN) { // next channel / agent / row
+                cell = x = 0;
+                if (++ch == C) {
+                    ch = 0;
+                    if (++i == A) { i = 0; row++; }
+                    mine = observer(row, i);
+                }
+            }
+        }
+        if (vec_ok && g + 3 < total) {
+            if constexpr (sizeof(OUT_T) == 4) *reinterpret_cast<float4 *>(dst + g) = make_float4(v[0], v[1], v[2], v[3]);
+            else *reinterpret_cast<uint32_t *>(dst + g) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+        } else {
+            for (int k = 0; k < 4 && g + k < total; k++) dst[g + k] = v[k];
+        }
+    }
+}
+
+// write_obs for the two room modes: the planes and byte images of PERSP, one room word per row, then the masked expansion
+template <class S, class Store>
+__device__ __forceinline__ void write_obs_room(const Consts &c, const ObsArgs &o, const Tables &T, const Store &st, int tid, const Env &e,
+                                               bool active, int64_t b0, int nrows) {
+    uint32_t *seg1 = T.stage;
+    uint32_t *seg2 = seg1 + o.words1;
+    uint32_t *roomw = seg2 + o.words2;
+    for (int w = tid; w < o.words1 + o.words2; w += kWave) seg1[w] = 0u;
+    wave_lds_fence();
+    const int A = S::A(c), N = c.N;
+    if (active) {
+        uint32_t rw = 0u;
+        for (int i = 0; i < A; i++) { // (the stored position, alive or not)
+            const uint32_t p = st.xy(i);
+            rw |= room_of((int)(p & 15u), (int)((p >> 4) & 15u), (N - 1) >> 1) << (2 * i);
+        }
+        roomw[tid] = rw;
+        fill_planes<S>(c, st, e, seg1, tid * o.Fi, reinterpret_cast<uint8_t *>(seg2) + tid * o.F2i);
+    }
+    wave_lds_fence();
+    const uint64_t valid = __ballot(active);
+    const int nb = S::tagging(c) ? 2 : 1;
+    const bool mask = o.mode == SUSNET_OBS_PERSP_ROOM_MASK;
+    if (o.dtype == SUSNET_F32) {
+        float *d1 = reinterpret_cast<float *>(o.out) + b0 * o.F;
+        if (mask) expand_persp_room_planes<float, true>(seg1, roomw, valid, nrows, A, N, d1, tid);
+        else expand_persp_room_planes<float, false>(seg1, roomw, valid, nrows, A, N, d1, tid);
+        if (o.out2) expand_persp_bytes(seg2, nrows, A, o.F2i, nb, reinterpret_cast<float *>(o.out2) + b0 * o.F2, tid);
+    } else {
+        uint8_t *d1 = reinterpret_cast<uint8_t *>(o.out) + b0 * o.F;
+        if (mask) expand_persp_room_planes<uint8_t, true>(seg1, roomw, valid, nrows, A, N, d1, tid);
+        else expand_persp_room_planes<uint8_t, false>(seg1, roomw, valid, nrows, A, N, d1, tid);
+        if (o.out2) expand_persp_bytes(seg2, nrows, A, o.F2i, nb, reinterpret_cast<uint8_t *>(o.out2) + b0 * o.F2, tid);
+    }
+}
+
 } // namespace susnet

@@ -107,12 +107,15 @@ class ObsConfig:
     """Which fused observation the kernels write next to every step / reset / rollout tick.
 
     mode: ``None`` | ``"raw"`` (``flatten_state``) | ``"flat"`` (FlatFeaturizer over ``components``) |
-    ``"planes"`` (GlobalFeaturizer) | ``"persp"`` (PerspectiveFeaturizer: every agent's rotated channel order, fused).  dtype ``torch.float32`` reproduces the reference tensors,
+    ``"planes"`` (GlobalFeaturizer) | ``"persp"`` (PerspectiveFeaturizer: every agent's rotated channel order, fused) | ``"persp_room"`` / ``"persp_room_mask"`` (the same views
+    under partial observability: every plane times the mask of the room the observing agent stands in, ``features.room_mask_views``; with
+    ``_mask`` the mask itself is the last channel.  ``env.featurize`` serves these two -- raw rows in, views out; no step, reset, rollout or
+    ``observe`` writes them, and an env cannot be built with one as its fused ``obs=``).  dtype ``torch.float32`` reproduces the reference tensors,
     ``torch.uint8`` stores the same integers in a quarter of the bytes.
     """
 
     def __init__(self, mode: Optional[str] = None, components: Sequence[str] = (), dtype=torch.float32):
-        assert mode in (None, "raw", "flat", "planes", "persp"), mode
+        assert mode in (None, "raw", "flat", "planes", "persp", "persp_room", "persp_room_mask"), mode
         assert dtype in (torch.float32, torch.uint8, torch.int8)
         self.mode, self.components, self.dtype = mode, list(components), dtype
         if mode == "flat":
@@ -121,7 +124,10 @@ class ObsConfig:
 
     @property
     def code(self):
-        return {None: L.OBS_NONE, "raw": L.OBS_RAW, "flat": L.OBS_FLAT, "planes": L.OBS_PLANES, "persp": L.OBS_PERSP}[self.mode]
+        return {None: L.OBS_NONE, "raw": L.OBS_RAW, "flat": L.OBS_FLAT, "planes": L.OBS_PLANES, "persp": L.OBS_PERSP,
+                "persp_room": L.OBS_PERSP_ROOM, "persp_room_mask": L.OBS_PERSP_ROOM_MASK}[self.mode]
+
+    ROOM_MODES = ("persp_room", "persp_room_mask")
 
 
 class BatchedFourRoomEnv:
@@ -165,6 +171,10 @@ class BatchedFourRoomEnv:
     ):
         self._validate_init_args(n_imposters, n_crew, n_jobs)
         assert rng in ("philox", "numpy", "tape")
+        if obs is not None and obs.mode in ObsConfig.ROOM_MODES:
+            raise ValueError(f"obs=ObsConfig({obs.mode!r}): the room-masked views are not a fused observation (no step, reset or rollout "
+                             "kernel writes them): build the env with obs=ObsConfig('raw', dtype=torch.uint8) and featurize raw rows "
+                             "(env.featurize, features.PerspectiveFeaturizer(env, partially_observable=True))")
         self.lib = L.lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -303,8 +313,10 @@ class BatchedFourRoomEnv:
         L.check(rc)
         lead = (rows,) if rows is not None else ((ticks, self.batch) if ticks > 1 else (self.batch,))
         A, N = self.n_agents, self.n_rows
-        shape1 = (*lead, A + 2, N, N) if oc.mode == "planes" else (*lead, A, A + 2, N, N) if oc.mode == "persp" else (*lead, f1.value)
-        shape2 = (*lead, A, f2.value // A) if oc.mode == "persp" else (*lead, f2.value)
+        persp = oc.mode == "persp" or oc.mode in ObsConfig.ROOM_MODES  # per-agent views; the mask channel is the room modes' last
+        shape1 = ((*lead, A + 2, N, N) if oc.mode == "planes" else
+                  (*lead, A, A + (3 if oc.mode == "persp_room_mask" else 2), N, N) if persp else (*lead, f1.value))
+        shape2 = (*lead, A, f2.value // A) if persp else (*lead, f2.value)
         # (every observation kernel writes every row in full -- rows it rejects as zeros -- so the buffers are not pre-filled:
         # a memset of a 700 MB feature batch cost as much as the kernel that fills it)
         out = torch.empty(shape1, dtype=oc.dtype, device=self.device)
@@ -992,7 +1004,7 @@ class BatchedFourRoomEnv:
         ``flattened_state_size``) instead of the env's own state: the reference's
         ``SequenceStateFeaturizer.fit(state_sequence[B, T, S])`` (src/features/model_ready.py:41-57) for a window
         or a replay batch.  Returns tensors with the same leading dimensions as ``states``."""
-        assert obs.mode in ("flat", "planes", "persp"), "featurize() produces the flat / planes / perspective feature layouts"
+        assert obs.mode in ("flat", "planes", "persp", *ObsConfig.ROOM_MODES), "featurize() produces the flat / planes / perspective feature layouts"
         assert states.shape[-1] == self.flattened_state_size, (
             f"expected rows of {self.flattened_state_size} values, got {states.shape[-1]}")
         assert states.dtype in self._ROW_DTYPES, f"unsupported state dtype {states.dtype}"

@@ -12,11 +12,14 @@ one ``(spatial, non_spatial)`` pair per agent with the reference shapes and chan
   (+ ``imposter_scent``: component.py:336-380, the one real-valued component: the ``susnet_scent`` kernel)
 * ``GlobalFeaturizer``      model_ready.py:219-306   -> ``(spatial[B, T, A+2, N, N], [alive, job_status, onehot(agent)])``
 * ``PerspectiveFeaturizer`` model_ready.py:82-216    -> per-agent channel rotation (self first) of the same planes
+  (``partially_observable=True``: every agent's view under the mask of the room it stands in, component.py:8-17 and 162-197;
+  ``room_mask_views`` is the definition, restated on the host)
 """
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .env import ObsConfig
@@ -112,19 +115,81 @@ class GlobalFeaturizer:
         return out
 
 
+def room_index(n: int) -> np.ndarray:
+    """``[n, n]`` int: the room of every cell of an n x n grid, ``(x <= w) + 2 * (y <= w)`` with ``w = (n - 1) // 2``.  At n = 9 the four
+    quadrants of the reference's ``ROOM_MASKS`` (component.py:8-17: ``[:5]`` / ``[5:]``; the wall row and column belong to the top and
+    the left rooms).  A function of n alone, not of the wall map, as the reference's masks are."""
+    w = (n - 1) // 2
+    low = (np.arange(n) <= w).astype(np.int64)
+    return low[:, None] + 2 * low[None, :]
+
+
+def room_mask_views(env, raw_rows, add_mask: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """The DEFINITION of the observation modes ``"persp_room"`` / ``"persp_room_mask"``, restated in numpy on the host (test
+    infrastructure; what ``PerspectiveFeaturizer(env, partially_observable=True)`` has the kernel write): the reference's
+    ``PartiallyObservableFeaturizer`` (component.py:162-197: "zeros everything that is not visible to the agent") applied to every
+    agent's Perspective view, made total.
+
+    ``raw_rows``: ``[..., S]`` flattened states (``flatten_state`` order; numpy or torch, any integer-valued dtype).  Returns
+    ``(spatial uint8 [..., A, A + 2 (+ 1), N, N], non_spatial uint8 [..., A, F2])``.
+
+    * Agent i's view of one state: the agent channels in the order i, 0, .., i-1, i+1, .., A-1 (a dead agent's channel is blank), then
+      the two job channels (not done, done).
+    * Every plane is multiplied by the mask of the room (``room_index``) that holds agent i's position IN THAT STATE: each state of a
+      window is masked by its own positions.  A dead agent keeps its stored position: its own channel is blank, its mask is its room's.
+    * ``add_mask`` (the reference's ``add_obs_mask_feature``, default True): the mask itself is the last channel.
+    * The non-spatial block is the Perspective featurizer's, unmasked -- the reference masks spatial features only: alive flags (and tag
+      counts) of every agent remain globally visible."""
+    rows = raw_rows.detach().cpu().numpy() if isinstance(raw_rows, torch.Tensor) else np.asarray(raw_rows)
+    lead, rows = rows.shape[:-1], rows.reshape(-1, rows.shape[-1]).astype(np.int64)
+    A, J, N = env.n_agents, env.n_jobs, env.n_rows
+    tagging = rows.shape[1] > 3 * A + 3 * J  # tagging.py:42-60 appends used[A], tag_counts[A], time left
+    assert rows.shape[1] == 3 * A + 3 * J + (2 * A + 1 if tagging else 0), rows.shape
+    R = rows.shape[0]
+    pos, alive = rows[:, :2 * A].reshape(R, A, 2), rows[:, 2 * A:3 * A] != 0
+    jobs, done = rows[:, 3 * A:3 * A + 2 * J].reshape(R, J, 2), rows[:, 3 * A + 2 * J:3 * A + 3 * J] != 0
+    planes = np.zeros((R, A + 2, N, N), dtype=np.uint8)
+    r = np.arange(R)
+    for a in range(A):
+        planes[r[alive[:, a]], a, pos[alive[:, a], a, 0], pos[alive[:, a], a, 1]] = 1
+    for j in range(J):
+        planes[r, A + done[:, j].astype(np.int64), jobs[:, j, 0], jobs[:, j, 1]] = 1
+    blocks = [alive.astype(np.uint8)] + ([rows[:, 3 * A + 3 * J + A:3 * A + 3 * J + 2 * A].astype(np.uint8)] if tagging else [])
+    rooms = room_index(N)
+    spatial = np.zeros((R, A, A + 2 + int(add_mask), N, N), dtype=np.uint8)
+    non_spatial = np.zeros((R, A, len(blocks) * A + J), dtype=np.uint8)
+    for i in range(A):
+        order = [i] + [a for a in range(A) if a != i]
+        mask = (rooms[None] == rooms[pos[:, i, 0], pos[:, i, 1]][:, None, None]).astype(np.uint8)  # [R, N, N]
+        spatial[:, i, :A + 2] = planes[:, order + [A, A + 1]] * mask[:, None]
+        if add_mask:
+            spatial[:, i, A + 2] = mask
+        non_spatial[:, i] = np.concatenate([b[:, order] for b in blocks] + [done.astype(np.uint8)], axis=1)
+    return spatial.reshape(*lead, *spatial.shape[1:]), non_spatial.reshape(*lead, *non_spatial.shape[1:])
+
+
 class PerspectiveFeaturizer:
     """model_ready.py:82-216.  The kernels write every agent's view directly (observation mode ``"persp"``: the agent
     channels in the order i, 0, .., i-1, i+1, .., A-1 -- what the reference's mutated order list reads after iteration i,
     model_ready.py:184-193 -- and the per-agent non-spatial blocks in that same order), so ``generate_featurized_states``
-    only slices."""
+    only slices.
 
-    def __init__(self, env):
+    ``partially_observable=True``: hidden information -- every plane of agent i's view is multiplied by the mask of the room agent i stands
+    in (``room_mask_views``: the reference's ``PartiallyObservableFeaturizer`` over ``ROOM_MASKS``, component.py:8-17, 162-197); with
+    ``add_obs_mask_feature`` (the reference's default) the mask itself is the last channel, so the views have A + 3 channels, else A + 2.
+    The non-spatial block is unchanged: alive flags remain global.  ``config`` is then ``"persp_room_mask"`` / ``"persp_room"``, which
+    ``susnet_featurize`` alone writes: ``fit(None)`` featurizes the env's current raw state.  The default is the fully observable object."""
+
+    def __init__(self, env, partially_observable: bool = False, add_obs_mask_feature: bool = True):
         self.env = env
-        self.config = ObsConfig("persp")
+        self.partially_observable, self.add_obs_mask_feature = bool(partially_observable), bool(add_obs_mask_feature)
+        self.config = ObsConfig(("persp_room_mask" if add_obs_mask_feature else "persp_room") if partially_observable else "persp")
         self.spatial = self.non_spatial = None  # [B, T, A, C, N, N], [B, T, A, F2]
 
     def fit(self, state_sequence=None) -> None:
-        if state_sequence is None:
+        if state_sequence is None and self.partially_observable:  # (env.observe does not serve the room modes)
+            self.spatial, self.non_spatial = self.env.featurize(self.env.observe(ObsConfig("raw", dtype=torch.uint8)).unsqueeze(1), self.config)
+        elif state_sequence is None:
             sp, non = self.env.observe(self.config)
             self.spatial, self.non_spatial = sp.unsqueeze(1), non.unsqueeze(1)
         else:

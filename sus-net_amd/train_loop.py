@@ -370,7 +370,8 @@ def _build_member(variant: Optional[int], env, models, components, featurizer, s
         policy = WindowedPolicyRollout(env, featurizer, imposter_model, crew_model, sequence_length=T, mask_dead=True, kernels=True,
                                        act_dropout_seed=s.act_dropout_seed)
         learner = {"featurizer": featurizer, "spatial": True, "rnn_dropout_seed": s.rnn_dropout_seed}
-        featurizer_type = "global" if isinstance(featurizer, GlobalFeaturizer) else "perspective"
+        # (a partially observable Perspective featurizer is on record as what it is: "perspective_room" / "perspective_room_mask")
+        featurizer_type = "global" if isinstance(featurizer, GlobalFeaturizer) else "perspective" + featurizer.config.mode[len("persp"):]
     trainer = DeviceDQNTeamTrainer(env, imposter_model, crew_model, components, lr=s.learning_rate, gamma=s.gamma, train_imposter=s.train_imposter,
                                    train_crew=s.train_crew, policy=policy, **learner)
     if featurizer is None and T > 1 and any(trainer.trained) and not trainer.dense:

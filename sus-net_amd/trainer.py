@@ -260,12 +260,13 @@ class DeviceDQNTeamTrainer:
 
     # ---- the spatial step's configuration ----
     def _spatial_featurizer(self):
-        """"global" / "persp" for a ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of this env, else None."""
+        """"global" / the observation mode ("persp"; "persp_room" / "persp_room_mask" under partial observability) for a
+        ``GlobalFeaturizer`` / ``PerspectiveFeaturizer`` of this env, else None."""
         from .features import GlobalFeaturizer, PerspectiveFeaturizer
 
         f = self._featurizer
         if isinstance(f, (GlobalFeaturizer, PerspectiveFeaturizer)) and f.env is self.env:
-            return "global" if isinstance(f, GlobalFeaturizer) else "persp"
+            return "global" if isinstance(f, GlobalFeaturizer) else f.config.mode
         return None
 
     def _spatial_net(self, model, dropout: bool = False):
