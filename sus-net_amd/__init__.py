@@ -22,6 +22,7 @@ from .trainer import DeviceDQNSweepTrainer, DeviceDQNTeamTrainer, torch_train_st
 from .episodes import EpisodeLog  # noqa: F401,E402
 from .scheduler import ExponentialSchedule  # noqa: F401,E402
 from .train_loop import evaluate, evaluate_checkpoints, plan_blocks, run_experiment, run_sweep, train, train_sweep  # noqa: F401,E402
+from .train_loop import read_run_state, snapshot_boundaries, stop_boundary, write_run_state  # noqa: F401,E402
 from .policy import MLP, DenseQNet, PolicyRollout, RandomEquiprobable, SpatialDQN, SpatialQNet, WindowedPolicyRollout  # noqa: F401,E402
 from .features import FlatFeaturizer, GlobalFeaturizer, PerspectiveFeaturizer  # noqa: F401,E402
 

@@ -1093,6 +1093,7 @@ class BatchedFourRoomEnv:
         per-call value and a captured hipGraph of them can be replayed.  ``env.tick`` keeps working (it synchronises)."""
         with self._on_device():
             L.check(self.lib.susnet_device_tick(self._h, int(bool(enable)), self._stream()))
+        self._device_tick = bool(enable)  # (which of susnet_tick's two forms the env uses: state_dict records it)
 
     def capture_random_step(self, n_ticks: int = 1) -> "torch.cuda.CUDAGraph":
         """hipGraph of ``n_ticks`` drop-in ticks ``a = env.sample_actions(); env.step(a)`` (two kernel nodes each): the
@@ -1146,6 +1147,71 @@ class BatchedFourRoomEnv:
         with torch.cuda.device(self.device):
             L.check(self.lib.susnet_reduce_lifetime(self._h, self._life_sum.data_ptr(), self._stream()))
         return self._life_sum
+
+    # ---- snapshot / restore -----------------------------------------------------------------
+    def _identity(self) -> dict:
+        """What a ``state_dict`` and the env it is loaded into must agree on: the ctor arguments as the handle got them (``susnet_config``
+        without the device ordinal), batch, seed and rng kind, the fused observation, ``SUSNET_ABI_VERSION`` and the ``susnet_get_layout``
+        sizes -- plain Python values under the names ``load_state_dict`` reports."""
+        out = {}
+        for name, _ in L.Config._fields_:
+            if name in ("struct_bytes", "device", "reserved", "seed", "rng_mode"):
+                continue
+            v = getattr(self._cfg, name)
+            out[name] = [int(x) for x in v] if name == "grid_rows" else (float(v) if isinstance(v, float) else int(v))
+        out["seed"], out["rng"] = int(self.seed), self.rng_kind
+        oc = self.obs_config
+        out["obs"] = [oc.mode, list(oc.components), str(oc.dtype)]
+        out["reward_dtype"], out["export_state"] = str(self.reward_dtype), bool(self.export_state)
+        for name, _ in L.Layout._fields_:
+            out["layout." + name] = int(getattr(self._layout, name))
+        return out
+
+    def state_dict(self) -> dict:
+        """The env between two calls, as host tensors and plain Python values: the bound state blob verbatim (every word the handle keeps
+        in device memory lies inside it: state, cursors, per-env metrics, lifetime accumulators, the error word and -- with
+        ``device_tick`` -- the per-env step counters), the handle's step counter (``susnet_tick``, in the form the env uses),
+        ``reset_generation``, the outputs of the last ``step`` and the configuration ``load_state_dict`` compares.  Synchronises.  PHILOX
+        envs only: a tape is the caller's."""
+        if self.rng_kind != "philox":
+            raise ValueError(f"state_dict: rng={self.rng_kind!r}: only envs on the production stream (rng='philox') are saved; a tape is the "
+                             "caller's to keep and to bind again")
+        device_tick = bool(getattr(self, "_device_tick", False))
+        tick = self.tick  # (with the counter in device memory this reads it back, ordered on the stream)
+        with self._on_device():
+            host = {name: getattr(self, name).cpu() for name in ("_state", "_rewards", "_done", "_trunc", "_actions")}
+        return {"identity": self._identity(), "blob": host["_state"], "tick": int(tick), "device_tick": device_tick,
+                "reset_generation": int(getattr(self, "reset_generation", 0)), "rewards": host["_rewards"], "done": host["_done"],
+                "truncated": host["_trunc"], "actions": host["_actions"]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Put the env into the state ``sd`` was taken in.  The env must have been built as the saved one was: a dict from another
+        configuration is a ``ValueError`` that names the field that differs (nothing has been changed then).  The step counter is set
+        through ``susnet_tick`` in the saved form, the blob copied back into the bound buffer, the Python object's views of the state
+        (roles, positions, metrics) exported again, and ``env.obs`` rewritten from the restored state (``refresh_obs``)."""
+        if self.rng_kind != "philox":
+            raise ValueError(f"load_state_dict: rng={self.rng_kind!r}: only envs on the production stream (rng='philox') are restored; a "
+                             "tape is the caller's to keep and to bind again")
+        mine, theirs = self._identity(), sd["identity"]
+        for key in sorted(set(mine) | set(theirs)):
+            if key not in mine or key not in theirs or mine[key] != theirs[key]:
+                what = "SUSNET_ABI_VERSION" if key == "abi_version" else key
+                raise ValueError(f"load_state_dict: the state was saved from another configuration: {what} is {theirs.get(key)!r} there, "
+                                 f"{mine.get(key)!r} here")
+        blob = sd["blob"]
+        if blob.dtype != torch.uint8 or blob.numel() != self._state.numel():
+            raise ValueError(f"load_state_dict: the state blob holds {blob.numel()} bytes, this env's {self._state.numel()}")
+        with torch.cuda.device(self.device):
+            self.device_tick(bool(sd["device_tick"]))
+            self.tick = int(sd["tick"])  # the handle's host-side counter (with the counter in device memory also the per-env copies, which
+            self._state.copy_(blob)      # the blob, copied last, then holds verbatim -- the padding rows included)
+            for name, key in (("_rewards", "rewards"), ("_done", "done"), ("_trunc", "truncated"), ("_actions", "actions")):
+                getattr(self, name).copy_(sd[key])
+            self.reset_generation = int(sd["reset_generation"])
+            self._export(full=True)
+            if self._obs_spec is not None:
+                self.refresh_obs()
+            torch.cuda.current_stream(self.device).synchronize()  # (the host copies above die with this call)
 
     def compute_action(self, agent_idx, action_idx, env_idx: int = 0):  # base.py:581-582
         return str(self.agent_action_map[agent_idx, env_idx][action_idx])

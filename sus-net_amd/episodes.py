@@ -139,6 +139,57 @@ class EpisodeLog:
             self.ticks = 0
             self.has_info = None
 
+    # ---- snapshot / restore ----
+    def state_dict(self) -> dict:
+        """The log between two ``update`` calls as host tensors and plain values, on both paths: the carry, the counters and the used part
+        of the log and of the parallel info log (HIP path: ``_carry``, ``_counters``, ``_log``, ``_info_log``, copied to the host, which
+        synchronises; numpy path: ``_G``, ``_t_episode``, ``_host_log``, ``_count``, ``_dropped``, the record arrays as their bytes), plus
+        ``ticks`` and ``has_info``.  The workspace is scratch and is not saved."""
+        sd = {"form": self.device.type, "n_agents": self.n_agents, "batch": self.batch, "gamma": self.gamma, "capacity": self.capacity,
+              "ticks": int(self.ticks), "has_info": self.has_info}
+        if self.device.type == "cuda":
+            counters = self._counters.cpu()
+            count = int(counters[0])
+            sd.update(carry=self._carry.cpu(), counters=counters, log=self._log[:count * (RECORD_DTYPE.itemsize // 8)].cpu(),
+                      info_log=None if self._info_log is None else self._info_log[:count].cpu())
+        else:
+            as_bytes = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy())
+            sd.update(G=torch.from_numpy(self._G.copy()), t_episode=torch.from_numpy(self._t_episode.copy()), count=int(self._count),
+                      dropped=int(self._dropped), log=as_bytes(self._host_log[:self._count]),
+                      info_log=None if self._info_log is None else as_bytes(self._info_log[:self._count]))
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore ``state_dict()``'s log into this one, built alike (form, agents, batch, gamma and capacity must agree: a difference is a
+        ``ValueError`` that names it).  The next ``update`` continues the episodes in flight and appends behind the restored records."""
+        mine = {"form": self.device.type, "n_agents": self.n_agents, "batch": self.batch, "gamma": self.gamma, "capacity": self.capacity}
+        for k, v in mine.items():
+            if sd[k] != v:
+                raise ValueError(f"load_state_dict: the episode log was saved with {k} = {sd[k]!r}, this one has {v!r}")
+        self.ticks, self.has_info = int(sd["ticks"]), sd["has_info"]
+        info = sd["info_log"]
+        if self.device.type == "cuda":
+            self._carry.copy_(sd["carry"])
+            self._counters.copy_(sd["counters"])
+            self._log[:sd["log"].numel()].copy_(sd["log"])
+            if info is None:
+                self._info_log = None
+            else:
+                if self._info_log is None:
+                    self._info_log = torch.zeros(max(self.capacity, 1), 4, dtype=torch.int32, device=self.device)
+                self._info_log[:info.shape[0]].copy_(info)
+        else:
+            self._G[...] = sd["G"].numpy()
+            self._t_episode[...] = sd["t_episode"].numpy()
+            self._count, self._dropped = int(sd["count"]), int(sd["dropped"])
+            self._host_log[:self._count] = sd["log"].numpy().view(RECORD_DTYPE)
+            if info is None:
+                self._info_log = None
+            else:
+                if self._info_log is None:
+                    self._info_log = np.zeros(self.capacity, dtype=INFO_DTYPE)
+                self._info_log[:self._count] = info.numpy().view(INFO_DTYPE)
+
     # ---- one feed block ----
     def update(self, feed: Dict[str, torch.Tensor], n_ticks: Optional[int] = None, tick_base: Optional[int] = None) -> None:
         n = int(feed["rewards"].shape[0] if n_ticks is None else n_ticks)

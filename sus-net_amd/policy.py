@@ -819,6 +819,21 @@ class PolicyRollout:
         self._packed_version = ver
         return self.fused_imposter is not None or self.fused_crew is not None
 
+    def state_dict(self) -> dict:
+        """What a ``PolicyRollout`` keeps between two ``collect`` calls that nothing else holds: nothing.  The weights are
+        the modules' (the trainer saves them), the packed images are re-packed from them, and the feature window is derived from the
+        ring's carried raw window at the start of every ``collect``."""
+        return {"kind": "PolicyRollout", "sequence_length": self.sequence_length}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """After the models' weights were restored: a forced ``refresh_weights``, so that the fused images are re-packed from them, and a
+        feature window that belongs to no episode generation (the next ``collect`` / ``q_rows`` fills it)."""
+        if sd.get("kind") != "PolicyRollout" or int(sd["sequence_length"]) != self.sequence_length:
+            raise ValueError(f"load_state_dict: saved from a {sd.get('kind')} with sequence_length = {sd.get('sequence_length')}, this is a "
+                             f"PolicyRollout with sequence_length = {self.sequence_length}")
+        self._window_generation = None
+        self.refresh_weights(force=True)
+
     @torch.no_grad()
     def q_rows(self):
         """The teams' Q rows on the current observation: ``(q_imposter [B, n_imposter_actions], q_crew or None)``."""
@@ -1051,6 +1066,26 @@ class WindowedPolicyRollout:
     def refresh_weights(self, force: bool = False) -> bool:
         """Nothing to do: ``SpatialQNet`` reads the modules' parameters in place at every forward."""
         return False
+
+    def state_dict(self) -> dict:
+        """What the policy keeps between two ``collect`` calls that nothing else holds: ``act_ticks``, the mask offset of acting under
+        dropout, and the state of the generator ``act()`` explores with.  The acting window is not part of it: ``collect`` loads it from
+        the ring's carried raw window at the start of every call."""
+        return {"kind": "WindowedPolicyRollout", "sequence_length": self.T, "act_ticks": int(self.act_ticks),
+                "act_dropout_seed": self.act_dropout_seed, "generator": self._gen.get_state()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore ``act_ticks`` and the exploration generator, drop the acting window (the next ``collect`` loads it) and -- for the
+        interface's sake, it packs nothing -- ``refresh_weights(force=True)``.  A policy of another kind, window length or
+        ``act_dropout_seed`` is a ``ValueError``."""
+        mine = {"kind": "WindowedPolicyRollout", "sequence_length": self.T, "act_dropout_seed": self.act_dropout_seed}
+        for k, v in mine.items():
+            if sd.get(k) != v:
+                raise ValueError(f"load_state_dict: the policy was saved with {k} = {sd.get(k)!r}, this one has {v!r}")
+        self.act_ticks = int(sd["act_ticks"])
+        self._gen.set_state(sd["generator"])
+        self.window = None
+        self.refresh_weights(force=True)
 
     @torch.no_grad()
     def q_rows(self):

@@ -239,6 +239,39 @@ class DeviceReplayBuffer:
         env it is given is another one, or has been ``reset()`` since the last call.)"""
         self._collect_window = None
 
+    # ---- snapshot / restore ----
+    _SHAPE = ("max_size", "state_size", "trajectory_size", "n_agents", "n_imposters")
+
+    def state_dict(self) -> dict:
+        """The ring as host tensors and plain values: the filled rows of the six tensors (rows ``0 .. size - 1``: the ring fills from row
+        0), ``idx`` and ``size``, and the raw window ``collect`` carries between calls (None before the first ``collect``, or after
+        ``reset_collection``).  The feed block is not part of it: take the snapshot after ``EpisodeLog.update`` has consumed it."""
+        window = self._collect_window
+        host = lambda x: x.cpu() if x.is_cuda else x.clone()  # (a copy either way: the dict does not alias the live ring)
+        return {"shape": {k: int(getattr(self, k)) for k in self._SHAPE}, "idx": int(self.idx), "size": int(self.size),
+                "rows": {f: host(getattr(self, f)[:self.size]) for f in self._FIELDS},
+                "collect_window": None if window is None else host(window)}
+
+    def load_state_dict(self, sd: dict, env=None) -> None:
+        """Restore ``state_dict()``'s ring into this one (built with the same sizes: a difference is a ``ValueError`` that names it).  The
+        carried window is re-keyed to ``env`` -- the env the next ``collect`` will be given, in the state it was saved in
+        (``env.load_state_dict`` first: its ``reset_generation`` is part of the key) -- so that ``collect`` continues from the restored
+        window and does not start over from the current state.  Without ``env`` the window is dropped (``reset_collection``)."""
+        for k in self._SHAPE:
+            if int(sd["shape"][k]) != int(getattr(self, k)):
+                raise ValueError(f"load_state_dict: the ring was saved with {k} = {sd['shape'][k]}, this one has {getattr(self, k)}")
+        size = int(sd["size"])
+        for f in self._FIELDS:
+            getattr(self, f)[:size].copy_(sd["rows"][f])
+        self.idx, self.size = int(sd["idx"]), size
+        window = sd["collect_window"]
+        self._collect_feed, self._collect_feed_ticks = None, 0
+        if env is None or window is None:
+            self._collect_owner, self._collect_window = (None, None, None), None
+        else:
+            self._collect_owner = (id(env), str(env.device), getattr(env, "reset_generation", 0))
+            self._collect_window = window.to(env.device).contiguous()
+
     @torch.no_grad()
     def populate(self, env, num_steps: int) -> int:
         """Random-policy rollout into the ring: ``num_steps`` lockstep ticks of ``env`` (B transitions each).

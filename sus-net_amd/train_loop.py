@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import os
 import pathlib
 from collections import namedtuple
 from datetime import datetime
@@ -58,6 +59,87 @@ def plan_blocks(num_steps: int, train_step_interval: int = 5, target_update_inte
         blocks.append(Block(t0, n, tuple(range(first_sync, end + 1, u)), tuple(t for t in saves if t0 <= t <= end), end % k == 0))
         t0 = end + 1
     return blocks
+
+
+def stop_boundary(blocks: List[Block], stop_after: int) -> Optional[int]:
+    """Where ``stop_after=t`` stops a run of ``blocks``: the completed ticks at the first block boundary with at least ``t`` of them (a
+    boundary lies behind a block's train step, or behind its collect when the block does not train: 1, k+1, 2k+1, ... and the run's
+    end), or None when ``t`` lies beyond the run -- it then finishes."""
+    t = int(stop_after)
+    for blk in blocks:
+        if blk.t0 + blk.n_ticks >= t:
+            return blk.t0 + blk.n_ticks
+    return None
+
+
+def snapshot_boundaries(blocks: List[Block], snapshot_interval: int) -> List[int]:
+    """Where ``snapshot_interval=n`` writes ``run_state.pt``: the completed ticks at the first block boundary at or beyond every ``n``
+    completed ticks.  The run's end is no such boundary: the run finishes there instead."""
+    n = int(snapshot_interval)
+    if n < 1:
+        raise ValueError(f"snapshot_interval = {snapshot_interval}: a positive number of ticks")
+    out, due = [], n
+    for blk in blocks[:-1]:
+        done = blk.t0 + blk.n_ticks
+        if done >= due:
+            out.append(done)
+            due = n * (done // n + 1)
+    return out
+
+
+RUN_STATE_FILE = "run_state.pt"
+RUN_STATE_FORMAT = 1
+
+
+def write_run_state(directory, state: dict) -> pathlib.Path:
+    """``state`` as ``directory/run_state.pt``, atomically: written under a temporary name in the same directory, then ``os.replace``d.
+    A write that fails leaves no partial file under the final name, and the previous snapshot where it was."""
+    directory = pathlib.Path(directory)
+    path, tmp = directory / RUN_STATE_FILE, directory / f".{RUN_STATE_FILE}.{os.getpid()}.tmp"
+    try:
+        with open(tmp, "wb") as f:
+            torch.save(state, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    finally:
+        if tmp.exists():
+            tmp.unlink()
+    return path
+
+
+def read_run_state(directory) -> dict:
+    """The snapshot ``directory/run_state.pt`` as ``write_run_state`` wrote it (host tensors and plain values).  Refused, each with its
+    own message: a directory without the file (``FileNotFoundError``), a file written under another ``SUSNET_ABI_VERSION`` or snapshot
+    format, and the snapshot of a finished run (``ValueError``)."""
+    path = pathlib.Path(directory) / RUN_STATE_FILE
+    if not path.is_file():
+        raise FileNotFoundError(f"resume_from={str(directory)!r}: there is no {RUN_STATE_FILE} (a run writes one with snapshot_interval= or "
+                                "stop_after=)")
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(state, dict) or state.get("format") != RUN_STATE_FORMAT:
+        raise ValueError(f"{path}: not a run snapshot of format {RUN_STATE_FORMAT} (format: {state.get('format') if isinstance(state, dict) else None!r})")
+    if state.get("abi_version") != L.ABI_VERSION:
+        raise ValueError(f"{path}: written under SUSNET_ABI_VERSION {state.get('abi_version')}, this library is version {L.ABI_VERSION}: the "
+                         "state blob of one version is not read by another")
+    if state.get("finished"):
+        raise ValueError(f"{path}: the snapshot of a finished run ({state.get('completed_ticks')} ticks, checkpoints and metrics written): "
+                         "there is nothing to resume")
+    return state
+
+
+def check_resume_config(who: str, config: dict, directory) -> None:
+    """``ValueError`` unless the ``config.json`` this call would write equals the one in ``directory`` on every key but
+    ``experiment_base_dir``; the message names the key and both values.  Reads only."""
+    path = pathlib.Path(directory) / "config.json"
+    if not path.is_file():
+        raise FileNotFoundError(f"{who}: resume_from={str(directory)!r}: there is no config.json: not a run's directory")
+    theirs, mine = json.loads(path.read_text()), json.loads(json.dumps(config, default=str))
+    absent = "<absent>"
+    for key in list(mine) + [k for k in theirs if k not in mine]:
+        if key != "experiment_base_dir" and mine.get(key, absent) != theirs.get(key, absent):
+            raise ValueError(f"{who}: resume_from={str(directory)!r}: {key} is {mine.get(key, absent)!r} in this call and "
+                             f"{theirs.get(key, absent)!r} in the run's config.json: a run is resumed with the arguments it was started with")
 
 
 def model_type(model) -> str:
@@ -107,7 +189,7 @@ class _Run:
     ``train_sweep()`` several in lockstep -- the same methods in the same order per member."""
 
     def __init__(self, who, env, metrics, num_steps, replay_buffer, policy, trainer, scheduler, save_directory_path, blocks, generator=None,
-                 episode_log=None, per_episode_info=False):
+                 episode_log=None, per_episode_info=False, schedule=None, resume=None):
         if not env.auto_reset:
             raise ValueError(f"{who}: the env must be built with auto_reset=True (episodes restart inside the rollout launch)")
         if policy.env is not env or trainer.env is not env:
@@ -127,8 +209,15 @@ class _Run:
         self.save_dir = pathlib.Path(save_directory_path)
         self.trains = any(trainer.trained)
         self.losses = torch.zeros(sum(b.trains for b in blocks), 2, dtype=torch.float32, device=env.device)
+        self.who, self.schedule, self.finished = who, dict(schedule or {}, num_steps=int(num_steps), per_episode_info=bool(per_episode_info)), False
+        if resume is not None:  # (its checks come before the first write: a refused resume leaves the directory as it was)
+            self._check_resume(resume)
         self.save_dir.mkdir(parents=True, exist_ok=True)
 
+        if resume is not None:  # no env.reset(): the env, like everything else, goes on from the snapshot
+            self.episode_log = episode_log if episode_log is not None else EpisodeLog(env, gamma=trainer.gamma)
+            self._load(resume)
+            return
         env.reset()  # train.py:316
         self.first_record = 0
         if episode_log is None:
@@ -138,6 +227,57 @@ class _Run:
             episode_log.reset(keep_log=True)
         self.episode_log = episode_log
         self.life0 = None if per_episode_info else env.lifetime_totals().clone()
+
+    # ---- snapshot / resume ----
+    def state_dict(self, completed_ticks: int, train_steps: int) -> dict:
+        """The run at a block boundary, as host tensors and plain values: every object's ``state_dict`` (env, ring, trainer, policy,
+        episode log), the sample generator's state (the caller's generator, or without one the device's global generator), and the
+        run's own: completed ticks, the rows of the loss history written so far, ``first_record`` and the lifetime baseline.  The one
+        place where the loop waits for the device and copies to the host."""
+        env, g = self.env, self.generator
+        with torch.cuda.device(env.device):
+            return {"format": RUN_STATE_FORMAT, "abi_version": L.ABI_VERSION, "finished": bool(self.finished), "schedule": dict(self.schedule),
+                    "completed_ticks": int(completed_ticks), "train_steps": int(train_steps), "losses": self.losses[:train_steps].cpu(),
+                    "first_record": int(self.first_record), "life0": None if self.life0 is None else self.life0.cpu(),
+                    "env": env.state_dict(), "ring": self.ring.state_dict(), "trainer": self.trainer.state_dict(),
+                    "policy": self.policy.state_dict(), "episode_log": self.episode_log.state_dict(),
+                    "generator": {"own": g is not None, "state": g.get_state() if g is not None else torch.cuda.get_rng_state(env.device)}}
+
+    def snapshot(self, completed_ticks: int, train_steps: int) -> pathlib.Path:
+        return write_run_state(self.save_dir, self.state_dict(completed_ticks, train_steps))
+
+    def _check_resume(self, state: dict) -> None:
+        """What can be told without touching an object: the snapshot's schedule is this run's, and it has a sample generator of the kind
+        this run draws from."""
+        for key, mine in self.schedule.items():
+            theirs = state["schedule"].get(key)
+            if theirs != mine:
+                raise ValueError(f"{self.who}: resume: {key} is {mine!r} in this call and {theirs!r} in the snapshot: a run is resumed with "
+                                 "the arguments it was started with")
+        if bool(state["generator"]["own"]) != (self.generator is not None):
+            raise ValueError(f"{self.who}: resume: the run drew its samples from " + ("a generator of its own" if state["generator"]["own"] else
+                             "the device's global generator") + ": pass " + ("one" if state["generator"]["own"] else "none") + " again")
+        if int(state["completed_ticks"]) > self.num_steps or int(state["train_steps"]) > self.losses.shape[0]:
+            raise ValueError(f"{self.who}: resume: the snapshot holds {state['completed_ticks']} ticks, the run has {self.num_steps}")
+
+    def _load(self, state: dict) -> None:
+        """The snapshot into the freshly built objects: env first (the ring keys its carried window to the env's ``reset_generation``),
+        then ring, trainer (in place: the policy's models are the trainer's), policy (its forced ``refresh_weights``), episode log,
+        generator, and the run's own values."""
+        env = self.env
+        env.load_state_dict(state["env"])
+        self.ring.load_state_dict(state["ring"], env)
+        self.trainer.load_state_dict(state["trainer"])
+        self.policy.load_state_dict(state["policy"])
+        self.episode_log.load_state_dict(state["episode_log"])
+        if self.generator is not None:
+            self.generator.set_state(state["generator"]["state"])
+        else:
+            torch.cuda.set_rng_state(state["generator"]["state"], env.device)
+        k = int(state["train_steps"])
+        self.losses[:k].copy_(state["losses"])
+        self.first_record = int(state["first_record"])
+        self.life0 = None if state["life0"] is None else state["life0"].to(env.device)
 
     def before_train_step(self, blk: Block) -> None:
         """The block up to its train step: checkpoints and target sync due inside it, the collect, the episode bookkeeping."""
@@ -152,6 +292,7 @@ class _Run:
 
     def finish(self) -> EpisodeLog:
         env, metrics, first_record = self.env, self.metrics, self.first_record
+        self.finished = True
         _save(self.trainer.models, self.save_dir, "100%")  # train.py:453-457 (written whether or not anything trained, as there)
         # ---- the only read-back: the episode log (records and info counters) and the loss history ----
         rec = self.episode_log.records()
@@ -168,23 +309,56 @@ class _Run:
         return self.episode_log
 
 
-def _run_blocks(runs: List[_Run], blocks: List[Block], train_step) -> List[EpisodeLog]:
+def _run_blocks(runs: List[_Run], blocks: List[Block], train_step, snapshot_interval=None, stop_after=None, completed: int = 0) -> List[EpisodeLog]:
     """THE block loop: per block every run's ``before_train_step``, then -- where the block ends on a train tick -- ``train_step(k)``, which
-    writes row ``k`` of the training runs' loss histories."""
-    k_train = 0
+    writes row ``k`` of the training runs' loss histories.  ``completed``: the ticks a resumed run has behind it (a block boundary: its
+    blocks are skipped).  At the boundaries ``snapshot_boundaries`` / ``stop_boundary`` name every run writes its ``run_state.pt`` -- the
+    only place where the loop waits for the device --; at ``stop_after``'s the loop then returns without finishing the runs.  With both
+    None no boundary is named and the loop is the one above, launch for launch."""
+    snaps = frozenset(snapshot_boundaries(blocks, snapshot_interval)) if snapshot_interval is not None else frozenset()
+    stop = stop_boundary(blocks, stop_after) if stop_after is not None else None
+    if stop is not None and stop <= completed:
+        raise ValueError(f"stop_after = {stop_after} stops at {stop} completed ticks, and the resumed run has {completed} behind it")
+    k_train = sum(blk.trains for blk in blocks if blk.t0 < completed)
     for blk in blocks:
+        if blk.t0 < completed:
+            continue
         for run in runs:
             run.before_train_step(blk)
         if blk.trains:  # train.py:402-416
             train_step(k_train)
             k_train += 1
+        done = blk.t0 + blk.n_ticks
+        if done == stop or done in snaps:
+            for run in runs:  # (a sweep: one file per member directory, all at this boundary)
+                run.snapshot(done, k_train)
+            if done == stop:
+                return [run.episode_log for run in runs]
     return [run.finish() for run in runs]
+
+
+def _resume_states(who: str, resume_from, n: int, blocks: List[Block]):
+    """``resume_from`` of ``train`` (one run directory, or the dict ``read_run_state`` returned) / ``train_sweep`` (a list of them, one per
+    member) as ``(states, completed ticks)``; ``([None] * n, 0)`` without one.  The members of a sweep must stand at one boundary."""
+    if resume_from is None:
+        return [None] * n, 0
+    items = list(resume_from) if isinstance(resume_from, (list, tuple)) else [resume_from]
+    if len(items) != n:
+        raise ValueError(f"{who}: resume_from names {len(items)} run(s), the call has {n}")
+    states = [item if isinstance(item, dict) else read_run_state(item) for item in items]
+    done = sorted(set(int(s["completed_ticks"]) for s in states))
+    if len(done) != 1:
+        raise ValueError(f"{who}: the members' snapshots stand at different ticks {done}: a sweep is stopped and resumed as one")
+    if done[0] != 0 and done[0] not in [blk.t0 + blk.n_ticks for blk in blocks]:
+        raise ValueError(f"{who}: the snapshot stands at {done[0]} completed ticks, which is no block boundary of this schedule")
+    return states, done[0]
 
 
 def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: DeviceReplayBuffer, policy: PolicyRollout,
           trainer: DeviceDQNTeamTrainer, scheduler: ExponentialSchedule, save_directory_path, train_step_interval: int = 5,
           batch_size: int = 32, num_saves: int = 5, target_update_interval: int = 10_000, generator: Optional[torch.Generator] = None,
-          episode_log: Optional[EpisodeLog] = None, per_episode_info: bool = False) -> EpisodeLog:
+          episode_log: Optional[EpisodeLog] = None, per_episode_info: bool = False, snapshot_interval: Optional[int] = None,
+          stop_after: Optional[int] = None, resume_from=None) -> EpisodeLog:
     """``train()`` of src/train.py:284-471.  ``num_steps`` counts lockstep ticks: each adds ``env.batch`` transitions.  ``policy``: the
     ``PolicyRollout`` the teams act by (reference MLPs a network kernel serves -- the fused kernels on the compiled-in layouts, the dense
     kernel on every other game / component set / layer stack, where the learner is ``torch_train_step``; a crew model of None = random crew); ``trainer``: the
@@ -195,20 +369,36 @@ def train(env, metrics: EpisodicMetricHandler, num_steps: int, replay_buffer: De
     returns with one entry per episode, the loss per train step, and the nine info counters -- with ``per_episode_info=True`` one entry
     per episode, in episode order (what ``metrics.step(info)`` appends at every episode end, train.py:419-427; ``run_experiment`` asks for
     it); by default ONE entry each, the mean per finished episode over the run.  The ``EpisodeLog`` (returned) keeps tick, env, length, cause
-    and info counters of every episode as well."""
+    and info counters of every episode as well.
+
+    Stopping and carrying on (all three None by default: nothing below happens, and the loop is launch for launch the one it was).
+    ``snapshot_interval=n``: at the first block boundary at or beyond every ``n`` completed ticks (``snapshot_boundaries``) the run's whole
+    state goes to ``save_directory_path/run_state.pt`` -- written under a temporary name, then ``os.replace``d; one file, the latest.
+    ``stop_after=t``: the run stops at the first block boundary with at least ``t`` completed ticks (``stop_boundary``), writes the
+    snapshot and returns WITHOUT the ``100%`` checkpoints and without filling ``metrics``: it is not finished (the checkpoints and target
+    syncs of the completed blocks have happened).  ``resume_from``: the directory of such a snapshot (or the dict ``read_run_state``
+    returned).  Build env, models, ring, policy and trainer as for the first call -- any initial weights -- and pass the same arguments:
+    there is no ``env.reset()``; the snapshot is loaded into the objects and the loop continues with the first block it has not done, to
+    the end an uninterrupted run reaches, bit for bit (the torch learner, ``torch_train_step``, is restored like the others, but its
+    kernels are torch's, not pinned here).  Stopping on wall-clock time is not offered: the loop never waits for the device, so the
+    host clock says nothing about progress -- choose ``stop_after`` from a measured tick rate."""
     blocks = plan_blocks(num_steps, train_step_interval, target_update_interval, num_saves)
+    (state,), completed = _resume_states("train", resume_from, 1, blocks)
+    schedule = dict(train_step_interval=int(train_step_interval), batch_size=int(batch_size), num_saves=int(num_saves),
+                    target_update_interval=int(target_update_interval))
     run = _Run("train", env, metrics, num_steps, replay_buffer, policy, trainer, scheduler, save_directory_path, blocks, generator, episode_log,
-               per_episode_info)
+               per_episode_info, schedule, state)
 
     def train_step(k):
         if run.trains:
             run.losses[k].copy_(trainer.train_step(replay_buffer, batch_size, generator))
 
-    return _run_blocks([run], blocks, train_step)[0]
+    return _run_blocks([run], blocks, train_step, snapshot_interval, stop_after, completed)[0]
 
 
 def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_size: int = 32, num_saves: int = 5,
-                target_update_interval: int = 10_000, per_episode_info: bool = False) -> List[EpisodeLog]:
+                target_update_interval: int = 10_000, per_episode_info: bool = False, snapshot_interval: Optional[int] = None,
+                stop_after: Optional[int] = None, resume_from=None) -> List[EpisodeLog]:
     """``train()`` for the members of a sweep in lockstep -- the reference's loop over ``run_experiment(**config)``
     (notebooks/experiment_1v1.ipynb, notebooks/experiment_mlp.ipynb) with the runs side by side.  ``members``: one
     ``(env, metrics, replay_buffer, policy, trainer, scheduler, save_directory_path, generator)`` per run, each with its own env, ring,
@@ -219,15 +409,21 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
     ``susnet_mlp_train_sweep``: the launches of one learner's step).  The schedule (``num_steps``, ``train_step_interval``,
     ``batch_size``, ``num_saves``, ``target_update_interval``) is shared.  Each member's metrics, losses, checkpoints and ``EpisodeLog``
     (returned, in member order) are what ``train()`` alone produces for it: its step is bitwise its own, and its random streams are
-    its own (give every member a generator: without one the draws come from the device's global generator, in member order)."""
+    its own (give every member a generator: without one the draws come from the device's global generator, in member order).
+    ``snapshot_interval``, ``stop_after``, ``resume_from`` (the list of the members' run directories, in member order): as in ``train``;
+    the sweep is stopped and resumed as one -- every member writes its ``run_state.pt`` into its own directory at the same boundary.
+    (A snapshot holds the global generator's state per member; members without a generator of their own are restored in member order.)"""
     members = [tuple(m) for m in members]
     if not members:
         raise ValueError("train_sweep: no members")
     if len(set(id(m[0]) for m in members)) != len(members) or len(set(id(m[2]) for m in members)) != len(members):
         raise ValueError("train_sweep: every member needs its own env and its own replay buffer")
     blocks = plan_blocks(num_steps, train_step_interval, target_update_interval, num_saves)
+    states, completed = _resume_states("train_sweep", resume_from, len(members), blocks)
+    schedule = dict(train_step_interval=int(train_step_interval), batch_size=int(batch_size), num_saves=int(num_saves),
+                    target_update_interval=int(target_update_interval))
     runs = [_Run(f"train_sweep: member {k}", env, metrics, num_steps, ring, policy, trainer, scheduler, save_dir, blocks, generator, None,
-                 per_episode_info)
+                 per_episode_info, schedule, states[k])
             for k, (env, metrics, ring, policy, trainer, scheduler, save_dir, generator) in enumerate(members)]
     training = [run for run in runs if run.trains]  # (a member with no trained team takes no step and draws no sample, as in train())
     sweep = DeviceDQNSweepTrainer([run.trainer for run in training]) if training else None
@@ -238,7 +434,7 @@ def train_sweep(members, num_steps: int, train_step_interval: int = 5, batch_siz
             for j, run in enumerate(training):
                 run.losses[k].copy_(out[j])
 
-    return _run_blocks(runs, blocks, train_step)
+    return _run_blocks(runs, blocks, train_step, snapshot_interval, stop_after, completed)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -406,6 +602,21 @@ def _start(members: List[_Member], s: _Settings) -> None:
             m.ring.populate_fused(m.env, s.replay_prepopulate_steps)
 
 
+def _resume(who: str, members: List[_Member]) -> List[dict]:
+    """The resume of freshly built members from their directories: every member's ``config.json`` comparison (``check_resume_config``),
+    then every member's snapshot (``read_run_state``).  Nothing is written and no object is touched: a refusal leaves all as it was."""
+    for m in members:
+        check_resume_config(who, m.config, m.directory)
+    return [read_run_state(m.directory) for m in members]
+
+
+def _stops(s: "_Settings", stop_after) -> bool:
+    """Whether ``stop_after`` stops a run of these settings before its end (``stop_boundary`` on its block plan)."""
+    if stop_after is None:
+        return False
+    return stop_boundary(plan_blocks(s.num_steps, s.train_step_interval, s.target_update_interval, s.num_checkpoint_saves), stop_after) is not None
+
+
 def _base_dir(experiment_base_dir) -> pathlib.Path:
     return pathlib.Path(experiment_base_dir) if experiment_base_dir is not None else pathlib.Path.cwd() / "model_registry" / "experiments"
 
@@ -417,7 +628,8 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
                    train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
                    generator: Optional[torch.Generator] = None, episode_log: Optional[EpisodeLog] = None,
                    dense_train: bool = False, featurizer=None, rnn_dropout_seed: Optional[int] = None,
-                   act_dropout_seed: Optional[int] = None) -> EpisodicMetricHandler:
+                   act_dropout_seed: Optional[int] = None, snapshot_interval: Optional[int] = None, stop_after: Optional[int] = None,
+                   resume_from=None) -> EpisodicMetricHandler:
     """``run_experiment`` of src/train.py:152-281 with the models given as modules: builds ring, policy, trainer and schedule
     (``_build_member``; a run that is refused there has written nothing), writes ``config.json``, pre-populates the ring with
     ``replay_prepopulate_steps`` random ticks, runs ``train()`` (with ``per_episode_info=True``: the nine info
@@ -446,18 +658,31 @@ def run_experiment(env, num_steps: int, imposter_model, crew_model, components: 
     a model in ``eval()`` acts without.  The models are left in the mode the caller gave them (the device train step changes no mode),
     and ``config.json`` carries ``act_dropout_seed`` only when it is given.  ``evaluate()`` / ``evaluate_checkpoints()`` stay eval-mode --
     evaluation is greedy play -- and keep refusing a training-mode model; ``run_sweep`` has no such argument, as it has no
-    ``rnn_dropout_seed``; torch's own mask stream cannot be reproduced (include/susnet.h)."""
+    ``rnn_dropout_seed``; torch's own mask stream cannot be reproduced (include/susnet.h).
+
+    ``snapshot_interval`` / ``stop_after`` / ``resume_from`` (all None by default): as in ``train()`` -- ``run_state.pt`` lies in the run's
+    directory; a run that ``stop_after`` stops writes neither the ``100%`` checkpoints nor ``metrics.json`` and returns the (empty) handler.
+    ``resume_from=<the run's directory>``: build env and models exactly as for the first call (any initial weights) and pass the same
+    arguments.  The run is built as always; the ``config.json`` it would write is compared with the directory's on every key but
+    ``experiment_base_dir`` (a difference: ``ValueError`` naming key and both values; nothing has been written then); ``config.json``, the
+    prepopulation and ``env.reset()`` are skipped, the snapshot is loaded and the run continues IN THAT DIRECTORY with the first block the
+    snapshot has not done, and finishes as an uninterrupted run does -- bit for bit on the HIP learners."""
     sequence_length = int(sequence_length)
     if act_dropout_seed is not None and featurizer is None:
         raise ValueError("run_experiment: act_dropout_seed is for SpatialDQN runs (featurizer=...): reference MLPs have no dropout")
     s = _Settings.of(locals())
     base = _base_dir(experiment_base_dir)
-    m = _build_member(None, env, (imposter_model, crew_model), list(components), featurizer, s, (base, base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")),
-                      generator)
-    _start([m], s)
+    directory = pathlib.Path(resume_from) if resume_from is not None else base / datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+    m = _build_member(None, env, (imposter_model, crew_model), list(components), featurizer, s, (base, directory), generator)
+    state = None
+    if resume_from is not None:
+        (state,) = _resume("run_experiment", [m])
+    else:
+        _start([m], s)
     train(env, m.metrics, num_steps, m.ring, m.policy, m.trainer, m.scheduler, m.directory, generator=generator, episode_log=episode_log,
-          **s.train_keywords())
-    m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
+          snapshot_interval=snapshot_interval, stop_after=stop_after, resume_from=state, **s.train_keywords())
+    if not _stops(s, stop_after):
+        m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
     return m.metrics
 
 
@@ -490,7 +715,8 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
               gamma: float = 0.99, scheduler_start_eps: float = 1.0, scheduler_end_eps: float = 0.05, scheduler_time_steps: int = 1_000_000,
               train_imposter: bool = True, train_crew: bool = True, experiment_base_dir=None, learning_rate: float = 0.0001,
               train_step_interval: int = 5, num_checkpoint_saves: int = 5, target_update_interval: int = 10_000,
-              seed: int = 0, dense_train: bool = False, featurizer_factory=None) -> List[EpisodicMetricHandler]:
+              seed: int = 0, dense_train: bool = False, featurizer_factory=None, snapshot_interval: Optional[int] = None,
+              stop_after: Optional[int] = None, resume_from=None) -> List[EpisodicMetricHandler]:
     """The reference's sweeps -- ``for config in configs: run_experiment(**config)`` (notebooks/experiment_1v1.ipynb,
     notebooks/experiment_mlp.ipynb: gamma 0.99 / 0.9 / 0.8 on one game and one MLP) -- as ONE run: the members collect one after another
     and take their train steps together (``train_sweep``).  The shared arguments are ``run_experiment``'s.  ``variants``: one dict per
@@ -514,7 +740,13 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
       (``config.json`` says None): members with dropout between their RNN layers take ``torch_train_step`` one after another (a
       ``DeviceDQNSweepTrainer`` over trainers built with ``rnn_dropout_seed`` does sweep them);
     * ``train_step`` in a ``SpatialDQN`` member's ``config.json`` is ``susnet_spatial_train_sweep`` -- one call per chunk of
-      ``SPATIAL_SWEEP_MAX_LEARNERS`` -- where that serves the training members, else the member's own learner."""
+      ``SPATIAL_SWEEP_MAX_LEARNERS`` -- where that serves the training members, else the member's own learner.
+
+    ``snapshot_interval`` / ``stop_after`` / ``resume_from`` (all None by default): as in ``run_experiment``, for the sweep as one -- every
+    member writes ``run_state.pt`` into its own directory at the same boundary.  ``resume_from``: the list of the members' directories in
+    variant order, or ONE path ``<experiment_base_dir>/<timestamp>`` that stands for ``<experiment_base_dir>/<name or index>/<timestamp>``
+    of every member; the factories are called as for the first call, every member's ``config.json`` is compared before anything is
+    loaded."""
     components, variants, spatial = list(components), check_variants(variants), featurizer_factory is not None
     if not spatial and not dense_train and sequence_length != 1:
         raise ValueError("run_sweep: a window of one state is served (sequence_length=1): the Q-network kernel and "
@@ -522,7 +754,14 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
     sequence_length = int(sequence_length)
     shared = _Settings.of(locals())
     base = _base_dir(experiment_base_dir)
-    dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+    if resume_from is None:
+        dirs = sweep_member_dirs(base, variants, datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
+    elif isinstance(resume_from, (list, tuple)):
+        dirs = [pathlib.Path(d) for d in resume_from]
+        if len(dirs) != len(variants):
+            raise ValueError(f"run_sweep: resume_from names {len(dirs)} member directories, the sweep has {len(variants)} variants")
+    else:  # <base>/<timestamp>: the members' common base with the timestamp
+        dirs = sweep_member_dirs(pathlib.Path(resume_from).parent, variants, pathlib.Path(resume_from).name)
     members = []
     for k, (variant, experiment_dir) in enumerate(zip(variants, dirs)):
         s = dataclasses.replace(shared, **{key: val for key, val in variant.items() if key != "name"})
@@ -544,10 +783,16 @@ def run_sweep(env_factory, variants, num_steps: int, imposter_model_factory, cre
         for m in members:
             if m.config.get("train_step") is not None and swept:
                 m.config["train_step"] = "susnet_mlp_train_sweep"
-    _start(members, shared)
-    train_sweep([m[:8] for m in members], num_steps, **shared.train_keywords())
-    for m in members:
-        m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
+    states = None
+    if resume_from is not None:
+        states = _resume("run_sweep", members)
+    else:
+        _start(members, shared)
+    train_sweep([m[:8] for m in members], num_steps, snapshot_interval=snapshot_interval, stop_after=stop_after, resume_from=states,
+                **shared.train_keywords())
+    if not _stops(shared, stop_after):
+        for m in members:
+            m.metrics.save_metrics(save_file_path=m.directory / "metrics.json")
     return [m.metrics for m in members]
 
 

@@ -546,6 +546,94 @@ class DeviceDQNTeamTrainer:
             off += n
         self.step_count[team].fill_(step)
 
+    # ---- snapshot / restore ----
+    @staticmethod
+    def _module_tensors(module) -> dict:
+        return {k: v.detach().cpu().clone() for k, v in module.state_dict().items()}
+
+    @staticmethod
+    @torch.no_grad()
+    def _load_module_tensors(module, tensors: dict, who: str) -> None:
+        """``tensors`` into ``module``'s parameters and buffers IN PLACE (``copy_`` into the storage they have: views stay views)."""
+        own = module.state_dict()
+        if list(own) != list(tensors):
+            raise ValueError(f"load_state_dict: the {who} was saved with the entries {list(tensors)}, this module has {list(own)}")
+        for k, v in own.items():
+            if tuple(v.shape) != tuple(tensors[k].shape):
+                raise ValueError(f"load_state_dict: {who}: {k} was saved as {tuple(tensors[k].shape)}, this module's is {tuple(v.shape)}")
+            v.copy_(tensors[k])
+
+    def state_dict(self) -> dict:
+        """The learner between two train steps, as host tensors and plain values.  Per team with a model: whether it trains, the modules'
+        train / eval mode (model and target); of a trained team the online and target parameters (``flat``, ``target_flat``), the Adam
+        moments and ``step_count`` as the flat buffers hold them, which side owns the Adam state (``_owner``) and -- where that is the
+        torch optimizer -- its ``state_dict`` (``optimizer_state_dict``); of a team that acts without training the modules' own tensors,
+        so that a run restored into fresh models acts with the saved ones.  Plus ``dropout_steps``.  Synchronises."""
+        teams = []
+        for t, m in enumerate(self.models):
+            if m is None:
+                teams.append(None)
+                continue
+            target = self.targets[t]
+            team = {"trained": self.trained[t], "training": bool(m.training), "target_training": None if target is None else bool(target.training)}
+            if self.trained[t]:
+                team.update(flat=self.flat[t].cpu(), target_flat=self.target_flat[t].cpu(), exp_avg=self.exp_avg[t].cpu(),
+                            exp_avg_sq=self.exp_avg_sq[t].cpu(), step_count=self.step_count[t].cpu(), owner=self._owner[t],
+                            optimizer=self.optimizer_state_dict(t) if self._owner[t] == "optim" else None)
+                if team["optimizer"] is not None:
+                    team["optimizer"] = {"state": {i: {k: v.detach().cpu().clone() if isinstance(v, torch.Tensor) else v for k, v in s.items()}
+                                                   for i, s in team["optimizer"]["state"].items()},
+                                         "param_groups": team["optimizer"]["param_groups"]}
+            else:
+                team.update(model=self._module_tensors(m), target=None if target is None else self._module_tensors(target))
+            teams.append(team)
+        return {"teams": teams, "dropout_steps": int(self.dropout_steps), "lr": self.lr, "gamma": self.gamma,
+                "rnn_dropout_seed": self.rnn_dropout_seed}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore ``state_dict()``'s learner into this one, built over models of the same shapes with the same ``lr``, ``gamma``,
+        ``train_*`` flags and ``rnn_dropout_seed`` (a difference is a ``ValueError`` that names it).  Everything is written into the
+        existing flat buffers IN PLACE: the modules' parameters stay views of them, a policy that reads the parameters in place follows,
+        and one that acts from packed images re-packs them (``policy.refresh_weights(force=True)``, where the trainer was built with its
+        policy).  Where the torch optimizer owned the Adam state it owns it again, with the saved ``state_dict``."""
+        for k in ("lr", "gamma", "rnn_dropout_seed"):
+            if sd[k] != getattr(self, k):
+                raise ValueError(f"load_state_dict: the trainer was saved with {k} = {sd[k]!r}, this one has {getattr(self, k)!r}")
+        for t, (m, team) in enumerate(zip(self.models, sd["teams"])):
+            name = ("imposter", "crew")[t]
+            if (m is None) != (team is None):
+                raise ValueError(f"load_state_dict: the {name} team had {'no' if team is None else 'a'} model when the trainer was saved, "
+                                 f"this one has {'none' if m is None else 'one'}")
+            if m is None:
+                continue
+            if bool(team["trained"]) != self.trained[t]:
+                raise ValueError(f"load_state_dict: the {name} team was saved with trained = {team['trained']}, this one has {self.trained[t]}")
+            if self.trained[t] and team["flat"].numel() != self.flat[t].numel():
+                raise ValueError(f"load_state_dict: the {name} model was saved with {team['flat'].numel()} parameters, this one has "
+                                 f"{self.flat[t].numel()}")
+        for t, (m, team) in enumerate(zip(self.models, sd["teams"])):
+            if m is None:
+                continue
+            target = self.targets[t]
+            if self.trained[t]:
+                for key in ("flat", "target_flat", "exp_avg", "exp_avg_sq", "step_count"):
+                    getattr(self, key)[t].copy_(team[key])
+                self._owner[t] = "flat"
+                if team["owner"] == "optim":  # the torch optimizer holds the state again, as saved (its tensors on the parameters' device)
+                    self.optimizers()[t].load_state_dict(team["optimizer"])
+                    self._owner[t] = "optim"
+            else:
+                self._load_module_tensors(m, team["model"], f"{('imposter', 'crew')[t]} model")
+                if target is not None and team["target"] is not None:
+                    self._load_module_tensors(target, team["target"], f"{('imposter', 'crew')[t]} target model")
+            m.train(bool(team["training"]))
+            if target is not None and team["target_training"] is not None:
+                target.train(bool(team["target_training"]))
+        self.dropout_steps = int(sd["dropout_steps"])
+        if self.policy is not None:
+            self.policy.refresh_weights(force=True)
+
     # ---- target networks ----
     @torch.no_grad()
     def sync_targets(self) -> None:
