@@ -4,6 +4,7 @@ masks (torch ops in the module's dtype, so autograd runs through it), the train 
 What nn.RNN(num_layers=L, dropout=p, batch_first=True) computes in training mode (tests/golden/generate_spatial_dropout.py pins this to the
 reference's module, test_spatial_dropout_host.py checks it): the output sequence of every layer l < L - 1 is multiplied elementwise by
 m_l and the product feeds layer l + 1 only; layer l's own recurrence reads the undropped h_l; the last layer's output is not dropped."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -86,3 +87,45 @@ def export_mask(pkg, env, drop, net, agent, layers, n, T, H):
     out = buf.cpu().numpy()
     assert (out[:32] == -7.0).all() and (out[32 + total:] == -7.0).all(), "susnet_rnn_dropout_mask wrote outside out"
     return out[32:32 + total].reshape(layers - 1, n, T, H).copy()
+
+
+def library_masks(pkg, env, models, drops, n, T, A):
+    """masks[(agent, team)] = (online, target), each [L - 1][n, T, H] float64 read back from the library (row = the position in the batch);
+    (None, None) for a team with one RNN layer.  drops: [imposter, crew] susnet_rnn_dropout."""
+    out = {}
+    for agent in range(A):
+        for team, m in enumerate(models):
+            if m is None:
+                continue
+            rnn = m.rnn.model
+            if rnn.num_layers < 2:
+                out[agent, team] = (None, None)
+                continue
+            get = lambda net: list(torch.as_tensor(export_mask(pkg, env, drops[team], net, agent, rnn.num_layers, n, T, rnn.hidden_size)).double())
+            out[agent, team] = (get(0), get(1))
+    return out
+
+
+def masked_reference(models, targets, batch, gamma, lr, masks, dtype=torch.float64):
+    """One masked_train_step on CPU copies in ``dtype`` (the multipliers are exact in float32: 0 or 1 / (1 - p) rounded once by the library):
+    (losses [2], exp_avg per team as flat float64, Adam step counts)."""
+    from spatial_train_util import agent_feats
+
+    ms = [m and copy.deepcopy(m).cpu().to(dtype) for m in models]
+    ts = [t and copy.deepcopy(t).cpu().to(dtype) for t in targets]
+    opts = [m and torch.optim.Adam(m.parameters(), lr=lr) for m in ms]
+    cast = lambda m: None if m is None else [x.to(dtype) for x in m]
+    masks = {k: (cast(on), cast(tg)) for k, (on, tg) in masks.items()}
+    idx = torch.as_tensor(batch["idx"])
+    sf, nf = agent_feats(batch, "spatial", dtype), agent_feats(batch, "next_spatial", dtype)
+    losses = masked_train_step(ms, ts, opts, gamma, sf, nf, torch.as_tensor(batch["actions"])[idx].long(),
+                               torch.as_tensor(batch["rewards"])[idx].to(dtype), torch.as_tensor(batch["dones"])[idx].bool().reshape(-1, 1),
+                               torch.as_tensor(batch["imposters"])[idx].to(torch.int16).reshape(-1, 1), masks)
+    ea, counts = [], []
+    for m, o in zip(ms, opts):
+        if m is None:
+            ea.append(None), counts.append(0.0)
+            continue
+        ea.append(np.concatenate([(o.state[p]["exp_avg"].double().numpy().reshape(-1) if p in o.state else np.zeros(p.numel())) for p in m.parameters()]))
+        counts.append(float(next(iter(o.state.values()))["step"]) if o.state else 0.0)
+    return np.asarray(losses, dtype=np.float64), ea, counts
